@@ -69,7 +69,56 @@ def _parse_args():
         "across MI300X/MI325X/MI355X (default shape); config5 = 4096 models "
         "x 8 variants (sharded)",
     )
+    p.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, write what the last timed reconcile "
+        "returned (global winner arrays + per-type aggregates) to "
+        "DIR/<name>.npy; same arguments give the same inputs, so two builds "
+        "can be compared output for output",
+    )
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also run the extended measurements (everything beyond the "
+        "headline figure: baselines, other configurations, comparisons). "
+        "A plain run only sets up, warms up, times the steps and prints the "
+        "result line; there is currently nothing extra, every other "
+        "configuration is selected explicitly (--preset, --limited, "
+        "--backend cpu, ...)",
+    )
     return p.parse_args()
+
+
+def dump_outputs(out_dir, result):
+    """Write the arrays a caller of the timed path receives (ShardResult:
+    global winners in sorted-server order, per-accelerator-type aggregates
+    in sorted-type order) as float .npy files. A few KB per 512 models."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    w = result.winners
+    arrays = {
+        # integer-valued fields go out as float64 (exact), the kernel's
+        # fp32 results stay fp32
+        "winner_acc_idx": w.acc_idx.astype(np.float64),
+        "winner_num_replicas": w.num_replicas.astype(np.float64),
+        "winner_batch": w.batch.astype(np.float64),
+        "winner_valid": w.valid.astype(np.float64),
+        "winner_cost": w.cost.astype(np.float32),
+        "winner_itl": w.itl.astype(np.float32),
+        "winner_ttft": w.ttft.astype(np.float32),
+    }
+    types = sorted(result.allocation_by_type)
+    arrays["by_type_count"] = np.array(
+        [result.allocation_by_type[t].count for t in types], dtype=np.float64
+    )
+    arrays["by_type_cost"] = np.array(
+        [result.allocation_by_type[t].cost for t in types], dtype=np.float64
+    )
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def preset_fleet(preset, models_per_gpu, world, seed):
@@ -265,6 +314,13 @@ def main():
         total_cells_per_step = int(cells_t.item())
     else:
         total_cells_per_step = cells_per_step
+
+    if args.dump_outputs and rank == 0:
+        if args.steps < 1:
+            print("ERROR: --dump-outputs needs at least one timed step",
+                  file=sys.stderr)
+            sys.exit(2)
+        dump_outputs(args.dump_outputs, r)
 
     allocations_per_sec = total_cells_per_step * args.steps / elapsed
     p50 = statistics.median(step_times)

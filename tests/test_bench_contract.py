@@ -60,6 +60,34 @@ class TestBenchContract:
         assert "greedy limited" in d["config"]["solver"]
 
 
+    def test_dump_outputs_reproducible(self, tmp_path):
+        """--dump-outputs writes the last timed step's results as float .npy
+        files; the same arguments give the same inputs, hence (on one build)
+        the same outputs. --full is accepted and keeps the result line."""
+        import numpy as np
+
+        a, b = tmp_path / "a", tmp_path / "b"
+        da = run_bench("--dump-outputs", str(a), "--full")
+        db = run_bench("--dump-outputs", str(b))
+        assert da["metric"] == db["metric"] and da["steps"] == db["steps"] == 2
+        names = sorted(p.name for p in a.iterdir())
+        assert names == sorted(p.name for p in b.iterdir())
+        for key in ("winner_acc_idx", "winner_num_replicas", "winner_cost",
+                    "winner_itl", "winner_ttft", "winner_valid",
+                    "by_type_count", "by_type_cost"):
+            assert key + ".npy" in names
+        total = 0
+        for n in names:
+            xa, xb = np.load(a / n), np.load(b / n)
+            assert xa.dtype in (np.float32, np.float64), (n, xa.dtype)
+            assert np.array_equal(xa, xb), n
+            total += xa.nbytes
+        assert total <= 64 * 2**20
+        assert np.load(a / "winner_valid.npy").shape == (4,)  # 4 models
+        assert np.load(a / "winner_valid.npy").all()
+        assert (np.load(a / "winner_num_replicas.npy") > 0).any()
+
+
 class TestBenchDistributedContract:
     """The driver launches bench.py through torch.distributed.run for N>1 —
     validate that exact invocation on CPU (gloo, world 2)."""

@@ -688,12 +688,17 @@ class TestInventoryCollection:
         result = rec.reconcile()
         assert result.processed == 1  # no inventory -> unlimited as before
 
-    def test_no_gpu_no_swap(self):
+    def test_no_gpu_no_swap(self, monkeypatch):
         """On a box with no visible device, the re-probe never swaps a
         broken GPU engine in (would churn the fallback path)."""
+        import inferno_amd.controller.reconciler as rmod
+
         kube, prom, em, reg, rec = build_world(arrival_per_sec=2.0)
         rec.engine.degraded_from_gpu = True
         rec.gpu_reprobe_interval = 1
-        rec._maybe_reprobe_gpu()  # container has no GPU -> _gpu_ready False
+        # the precondition is "no visible device": pin it, so the test means
+        # the same on a host that does have a GPU
+        monkeypatch.setattr(rmod, "_gpu_ready", lambda: False)
+        rec._maybe_reprobe_gpu()
         assert rec.engine.backend == "cpu"
         assert rec.engine.degraded_from_gpu is True

@@ -117,10 +117,10 @@ class TestCrdWireCompat:
             assert r.status_code == 201, r.text
 
     def test_reference_sample_va_applies_unchanged(self, kubeapi):
-        """The acid test: the reference's own sample VA, byte-for-byte."""
-        ref = "/root/reference/deploy/examples/vllm-emulator/vllme-setup/vllme-variantautoscaling.yaml"
-        if not os.path.exists(ref):
-            pytest.skip("reference checkout not present")
+        """The acid test: the reference's own sample VA, byte-for-byte (kept
+        as a fixture under tests/golden/)."""
+        ref = os.path.join(REPO, "tests", "golden",
+                           "reference_sample_variantautoscaling.yaml")
         client, _ = kubeapi
         with open(ref) as f:
             docs = [d for d in yaml.safe_load_all(f) if d]
