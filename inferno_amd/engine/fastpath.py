@@ -401,6 +401,27 @@ class FastSweep:
         if rc != 0:
             raise HipKernelError(f"wva_reconcile failed: {rc}")
 
+    def memo_stats(self) -> Optional[tuple[int, int]]:
+        """(hits, misses) of the native context's sizing memo since the
+        context was created, or None when there is no context yet or the
+        memo is off (INFERNO_SIZING_MEMO=0). Synchronous; diagnostics only."""
+        import ctypes
+
+        st = getattr(self, "_gpu", None)
+        if not st or "ctx" not in st:
+            return None
+        hits, misses = ctypes.c_uint(0), ctypes.c_uint(0)
+        rc = st["ctx_lib"].wva_ctx_memo_stats(
+            st["ctx"], ctypes.byref(hits), ctypes.byref(misses)
+        )
+        if rc < 0:
+            from ..ops.sweep import HipKernelError
+
+            raise HipKernelError(f"wva_ctx_memo_stats failed: {rc}")
+        if rc != 0:
+            return None
+        return int(hits.value), int(misses.value)
+
     def reconcile_cells(self) -> Optional[dict]:
         """Run the sweep and return PER-CELL output arrays (numpy) plus the
         cell metadata — the input the greedy limited-mode solver needs (full

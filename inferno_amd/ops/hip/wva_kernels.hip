@@ -35,6 +35,11 @@
 //       analyzer_mode 1 selects the closed-form M/G/1/K evaluator
 //       (mg1_eval: O(1) per evaluation, no chain/LDS — BASELINE config 4).
 //
+//       Under the native reconcile context the sizing result of each cell
+//       is memoized across ticks, keyed on the bits of everything the sizing
+//       reads and validated on the device (see "Sizing memo" below): a hit
+//       keeps the geometry build and ONE chain evaluation.
+//
 //   K2 wva_argmin: segmented argmin over the sweep output per server
 //       (value = transition-penalty-adjusted cost), deterministic
 //       lowest-cell-index tie-break.
@@ -578,6 +583,63 @@ __device__ void dual_bisect(double lam_min, double lam_max, float t_ttft, float 
 }
 
 // ---------------------------------------------------------------------------
+// Sizing memo: one record per cell, owned by the native reconcile context.
+// The SLO sizing phase (dual_bisect + the sized-rate evaluation) reads only
+// the fields in the key below — never the arrival rate, the current
+// allocation or min_replicas — so while the key repeats from tick to tick
+// its fp64 result and feasibility verdict repeat bit for bit. The key is
+// compared as raw 32-bit patterns ON THE DEVICE every tick, so a record can
+// never be replayed for different inputs. NT is part of the key because the
+// reduction order (hence the last bits of tput) depends on the block width.
+// ---------------------------------------------------------------------------
+#define WVA_MEMO_KEY_WORDS 13
+#define WVA_MEMO_EMPTY 0u
+#define WVA_MEMO_FEASIBLE 1u
+#define WVA_MEMO_INFEASIBLE 2u  // SLO-infeasible or degenerate service rates
+
+struct alignas(16) WvaMemoRec {
+  unsigned key[WVA_MEMO_KEY_WORDS];
+  unsigned status;  // written last
+  double tput;      // tput_at_lam (req/msec); meaningful for status 1 only
+};
+static_assert(sizeof(WvaMemoRec) == 64, "memo record is one 64-byte line");
+
+struct WvaMemoKey {
+  unsigned w[WVA_MEMO_KEY_WORDS];
+};
+
+__device__ __forceinline__ WvaMemoKey memo_make_key(int in_tok, int out_tok, int N, float alpha,
+                                                    float beta, float gamma, float delta,
+                                                    float t_ttft, float t_itl, float t_tps,
+                                                    float cv2, int analyzer_mode, int nt) {
+  WvaMemoKey k;
+  k.w[0] = (unsigned)in_tok;
+  k.w[1] = (unsigned)out_tok;
+  k.w[2] = (unsigned)N;
+  k.w[3] = __float_as_uint(alpha);
+  k.w[4] = __float_as_uint(beta);
+  k.w[5] = __float_as_uint(gamma);
+  k.w[6] = __float_as_uint(delta);
+  k.w[7] = __float_as_uint(t_ttft);
+  k.w[8] = __float_as_uint(t_itl);
+  k.w[9] = __float_as_uint(t_tps);
+  k.w[10] = __float_as_uint(cv2);
+  k.w[11] = (unsigned)analyzer_mode;
+  k.w[12] = (unsigned)nt;
+  return k;
+}
+
+// called by thread 0 only, on a miss: payload and key first, status last
+__device__ __forceinline__ void memo_store(WvaMemoRec *rec, const WvaMemoKey &k, double tput,
+                                           unsigned status) {
+#pragma unroll
+  for (int q = 0; q < WVA_MEMO_KEY_WORDS; ++q) rec->key[q] = k.w[q];
+  rec->tput = tput;
+  __threadfence();
+  rec->status = status;
+}
+
+// ---------------------------------------------------------------------------
 // K1: allocate-sweep — one block per cell; cell_ids selects this launch's
 // N-bucket (nullptr = identity).
 // dynamic LDS: S[0..maxN] prefix, then scratch[2*NT/64] for reductions.
@@ -592,7 +654,10 @@ template <int NT, bool GMEM>
 __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut out, int n_blocks,
                                                   const int *cell_ids, int max_n,
                                                   int analyzer_mode, float cv2,
-                                                  float *g_inv, double *g_anchor) {
+                                                  float *g_inv, double *g_anchor,
+                                                  WvaMemoRec *memo, unsigned *memo_cnt) {
+  // memo: per-cell sizing records (nullptr = memo off: every cell is sized
+  // from scratch and nothing is recorded); memo_cnt: [0] hits, [1] misses
   extern __shared__ double smem[];
   if ((int)blockIdx.x >= n_blocks) return;
   const int cell = cell_ids ? cell_ids[blockIdx.x] : (int)blockIdx.x;
@@ -671,6 +736,45 @@ __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut 
     }
     return;
   }
+
+  // ---- sizing memo lookup: every thread loads the cell's record (same
+  // address block-wide) and compares the key, so the verdict is uniform and
+  // every barrier below stays uniform. The only writer is this block's
+  // thread 0 at one of the miss exits, which all lie behind a barrier (or,
+  // for the single-wave block, later in the same wave's program order).
+  WvaMemoRec *const rec = memo ? memo + cell : nullptr;
+  unsigned memo_status = WVA_MEMO_EMPTY;
+  double memo_tput = 0.0;
+  if (rec) {
+    const WvaMemoRec r = *rec;
+    const WvaMemoKey k = memo_make_key(in_tok, out_tok, N, alpha, beta, gamma, delta, t_ttft,
+                                       t_itl, t_tps, cv2, analyzer_mode, NT);
+    bool same = r.status == WVA_MEMO_FEASIBLE || r.status == WVA_MEMO_INFEASIBLE;
+#pragma unroll
+    for (int q = 0; q < WVA_MEMO_KEY_WORDS; ++q) same = same && (r.key[q] == k.w[q]);
+    if (same) {
+      memo_status = r.status;
+      memo_tput = r.tput;
+    }
+    if (tid == 0) atomicAdd(memo_cnt + (same ? 0 : 1), 1u);
+    if (memo_status == WVA_MEMO_INFEASIBLE) {
+      // replay of the infeasible verdict: no geometry, no evaluations
+      if (tid == 0) {
+        out.feasible[cell] = 0;
+        out.zero_empty[cell] = 0;
+      }
+      return;
+    }
+  }
+  // miss exits (degenerate, infeasible, sized) record their outcome; the key
+  // is rebuilt here rather than kept live across the sizing phase
+  auto memo_miss_store = [&](double tput, unsigned status) {
+    if (rec && tid == 0)
+      memo_store(rec,
+                 memo_make_key(in_tok, out_tok, N, alpha, beta, gamma, delta, t_ttft, t_itl,
+                               t_tps, cv2, analyzer_mode, NT),
+                 tput, status);
+  };
 
   const int K = out_tok;
   int num_decode = out_tok - 1;
@@ -757,6 +861,7 @@ __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut 
       out.feasible[cell] = 0;
       out.zero_empty[cell] = 0;
     }
+    memo_miss_store(0.0, WVA_MEMO_INFEASIBLE);
     return;
   }
   const double logsN = log((double)sN);
@@ -767,39 +872,46 @@ __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut 
   const double cv2d = (double)cv2;
   const int Kstates = 11 * N;  // maxQueue (10N) + N  (ref allocation.go:87)
 
-  // ---- SLO sizing: concurrent TTFT+ITL bisections (queueanalyzer.go:185-255)
-  double lam_star[2];
-  int inds[2];
-  dual_bisect<NT>(lam_min, lam_max, t_ttft, t_itl, geom, logsN, N, Kstates, gamma, delta,
-                  alpha, beta, in_tok, out_tok, scratch, total_slot + 1, lam_star, inds,
-                  analyzer_mode, cv2d, mu);
-  bool feasible = true;
-  double lam_ttft = lam_max;
-  if (t_ttft > 0.0f) {
-    lam_ttft = lam_star[0];
-    if (inds[0] < 0) feasible = false;
-  }
-  double lam_itl = lam_max;
-  if (feasible && t_itl > 0.0f) {
-    lam_itl = lam_star[1];
-    if (inds[1] < 0) feasible = false;
-  }
-  if (!feasible) {
-    if (tid == 0) {
-      out.feasible[cell] = 0;
-      out.zero_empty[cell] = 0;
-    }
-    return;
-  }
-  double lam_tps = (t_tps > 0.0f) ? lam_max * (1.0 - WVA_STABILITY_FRACTION) : lam_max;
-  double lam = fmin(fmin(lam_ttft, lam_itl), lam_tps);
-
-  // ---- analyze at sized rate -> rate* (ref allocation.go:126-131) ----
   double tput_at_lam;
-  if (analyzer_mode == 1) {
-    tput_at_lam = mg1_eval(lam, mu, Kstates, cv2d, N).throughput;
+  if (memo_status == WVA_MEMO_FEASIBLE) {
+    // memo hit (block-uniform): the sizing below would reproduce this value
+    tput_at_lam = memo_tput;
   } else {
-    tput_at_lam = chain_eval<NT, 1>(lam, geom, logsN, N, Kstates, scratch).throughput;
+    // ---- SLO sizing: concurrent TTFT+ITL bisections (queueanalyzer.go:185-255)
+    double lam_star[2];
+    int inds[2];
+    dual_bisect<NT>(lam_min, lam_max, t_ttft, t_itl, geom, logsN, N, Kstates, gamma, delta,
+                    alpha, beta, in_tok, out_tok, scratch, total_slot + 1, lam_star, inds,
+                    analyzer_mode, cv2d, mu);
+    bool feasible = true;
+    double lam_ttft = lam_max;
+    if (t_ttft > 0.0f) {
+      lam_ttft = lam_star[0];
+      if (inds[0] < 0) feasible = false;
+    }
+    double lam_itl = lam_max;
+    if (feasible && t_itl > 0.0f) {
+      lam_itl = lam_star[1];
+      if (inds[1] < 0) feasible = false;
+    }
+    if (!feasible) {
+      if (tid == 0) {
+        out.feasible[cell] = 0;
+        out.zero_empty[cell] = 0;
+      }
+      memo_miss_store(0.0, WVA_MEMO_INFEASIBLE);
+      return;
+    }
+    double lam_tps = (t_tps > 0.0f) ? lam_max * (1.0 - WVA_STABILITY_FRACTION) : lam_max;
+    double lam = fmin(fmin(lam_ttft, lam_itl), lam_tps);
+
+    // ---- analyze at sized rate -> rate* (ref allocation.go:126-131) ----
+    if (analyzer_mode == 1) {
+      tput_at_lam = mg1_eval(lam, mu, Kstates, cv2d, N).throughput;
+    } else {
+      tput_at_lam = chain_eval<NT, 1>(lam, geom, logsN, N, Kstates, scratch).throughput;
+    }
+    memo_miss_store(tput_at_lam, WVA_MEMO_FEASIBLE);
   }
   const double rate_star = tput_at_lam * 1000.0;  // req/sec
 
@@ -923,7 +1035,7 @@ static int wva_optin_lds(const void *func, size_t lds) {
 static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_ids,
                               int analyzer_mode, float cv2, hipStream_t s,
                               const WvaCellsIn &in, const WvaCellsOut &out, float *g_inv,
-                              double *g_anchor) {
+                              double *g_anchor, WvaMemoRec *memo, unsigned *memo_cnt) {
   if (n_blocks <= 0) return 0;
   const bool gmem = g_inv != nullptr && g_anchor != nullptr;
   if (max_n < 1) return -2;
@@ -941,7 +1053,8 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
     int orc = wva_optin_lds(reinterpret_cast<const void *>(&wva_sweep_t<NTV, GM>), lds);    \
     if (orc != 0) return orc;                                                               \
     hipLaunchKernelGGL((wva_sweep_t<NTV, GM>), dim3(n_blocks), dim3(NTV), lds, s, in, out,  \
-                       n_blocks, cell_ids, max_n, analyzer_mode, cv2, g_inv, g_anchor);     \
+                       n_blocks, cell_ids, max_n, analyzer_mode, cv2, g_inv, g_anchor,      \
+                       memo, memo_cnt);                                                     \
   } while (0)
   if (gmem) {
     switch (nt) {
@@ -980,7 +1093,8 @@ extern "C" int wva_sweep_launch_bucket(
   WvaCellsOut out = {feasible, zero_empty, num_replicas, batch, cost, value, itl, ttft, rho,
                      max_rate};
   return wva_sweep_dispatch(n_blocks, max_n, nt, cell_ids, analyzer_mode, cv2,
-                            (hipStream_t)stream, in, out, (float *)g_inv, (double *)g_anchor);
+                            (hipStream_t)stream, in, out, (float *)g_inv, (double *)g_anchor,
+                            nullptr, nullptr);  // one-shot API: no sizing memo
 }
 
 // single-bucket convenience wrapper (whole sweep with one block size)
@@ -1090,6 +1204,12 @@ struct WvaCtx {
   // failed once -> stay on the eager path. Invalidated by set_buckets.
   hipGraphExec_t graph_exec;
   int graph_state;
+  // sizing memo (one device allocation: n_cells records, then the hit and
+  // miss counters). nullptr = memo off (INFERNO_SIZING_MEMO=0 or the
+  // allocation failed). Stable for the life of the ctx, so a captured graph
+  // stays valid.
+  WvaMemoRec *memo;
+  unsigned *memo_cnt;
 };
 
 // pointer-slot order for wva_ctx_create (host mirrors in ops/sweep.py):
@@ -1111,6 +1231,8 @@ extern "C" void *wva_ctx_create(int n_cells, int n_srv, void **p) {
   c->n_buckets = 0;
   c->graph_exec = nullptr;
   c->graph_state = 0;
+  c->memo = nullptr;
+  c->memo_cnt = nullptr;
   char *di = (char *)p[0];
   char *df = (char *)p[1];
   size_t ci = (size_t)n_cells * sizeof(int);
@@ -1162,7 +1284,47 @@ extern "C" void *wva_ctx_create(int n_cells, int n_srv, void **p) {
     delete c;
     return nullptr;
   }
+  // sizing memo: INFERNO_SIZING_MEMO=0 is the kill switch (A/B measurement,
+  // tests) — read per call, never cached. Any failure here leaves the memo
+  // off; the context itself is still good.
+  const char *memo_env = getenv("INFERNO_SIZING_MEMO");
+  const bool memo_on = !(memo_env != nullptr && memo_env[0] == '0' && memo_env[1] == '\0');
+  if (memo_on && n_cells > 0) {
+    // allocate on the device that owns dev_i (the kernels' inputs)
+    int prev_dev = -1, dev = -1;
+    hipPointerAttribute_t attr;
+    if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
+    if (hipPointerGetAttributes(&attr, p[0]) == hipSuccess) dev = attr.device;
+    const bool switched = dev >= 0 && prev_dev >= 0 && dev != prev_dev &&
+                          hipSetDevice(dev) == hipSuccess;
+    const size_t bytes = (size_t)n_cells * sizeof(WvaMemoRec) + 2 * sizeof(unsigned);
+    void *m = nullptr;
+    if (hipMalloc(&m, bytes) == hipSuccess && m != nullptr) {
+      if (hipMemsetAsync(m, 0, bytes, c->s0) == hipSuccess) {
+        c->memo = (WvaMemoRec *)m;
+        c->memo_cnt = (unsigned *)((char *)m + (size_t)n_cells * sizeof(WvaMemoRec));
+      } else {
+        (void)hipFree(m);
+      }
+    }
+    if (c->memo == nullptr) (void)hipGetLastError();  // clear the non-fatal error
+    if (switched) (void)hipSetDevice(prev_dev);
+  }
   return c;
+}
+
+// hit/miss counters of the sizing memo since the context was created
+// (unsigned, wrapping). Synchronous small D2H — diagnostics only, never on
+// the hot path. Returns 1 when the memo is off, <0 on a runtime error.
+extern "C" int wva_ctx_memo_stats(void *ctx, unsigned *hits, unsigned *misses) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || c->memo == nullptr) return 1;
+  unsigned h[2] = {0u, 0u};
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -1;
+  if (hipMemcpy(h, c->memo_cnt, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -2;
+  if (hits) *hits = h[0];
+  if (misses) *misses = h[1];
+  return 0;
 }
 
 extern "C" int wva_ctx_set_buckets(void *ctx, int n_buckets, const int *nts,
@@ -1191,7 +1353,7 @@ extern "C" int wva_ctx_set_buckets(void *ctx, int n_buckets, const int *nts,
 
 static int wva_launch_bucket_on(WvaCtx *c, const WvaBucket &b, hipStream_t s) {
   return wva_sweep_dispatch(b.n_blocks, b.max_n, b.nt, b.cell_ids, c->analyzer_mode, c->cv2, s,
-                            c->in, c->out, b.g_inv, b.g_anchor);
+                            c->in, c->out, b.g_inv, b.g_anchor, c->memo, c->memo_cnt);
 }
 
 // enqueue the whole per-tick pipeline on the ctx's streams (used both for
@@ -1308,5 +1470,6 @@ extern "C" void wva_ctx_destroy(void *ctx) {
     (void)hipStreamDestroy(c->side[i]);
     (void)hipEventDestroy(c->e_b[i]);
   }
+  if (c->memo != nullptr) (void)hipFree(c->memo);
   delete c;
 }

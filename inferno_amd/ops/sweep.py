@@ -163,6 +163,12 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
     lib.wva_greedy_solve.restype = ctypes.c_int
     lib.wva_ctx_destroy.restype = None
     lib.wva_ctx_destroy.argtypes = [ctypes.c_void_p]
+    lib.wva_ctx_memo_stats.restype = ctypes.c_int
+    lib.wva_ctx_memo_stats.argtypes = [
+        ctypes.c_void_p,
+        ctypes.POINTER(ctypes.c_uint),  # hits
+        ctypes.POINTER(ctypes.c_uint),  # misses
+    ]
     _lib = lib
     return lib
 
