@@ -3,6 +3,7 @@ pkg/config wire format) and print the allocation solution.
 
   python -m inferno_amd.cli solve system.json [--backend cpu|gpu] [--json]
   python -m inferno_amd.cli analyze system.json --server NAME:NS
+  python -m inferno_amd.cli plan system.json --scales 0.5,1,1.5,2 [--backend ...] [--json]
 """
 from __future__ import annotations
 
@@ -63,6 +64,62 @@ def cmd_solve(args) -> int:
     return 0
 
 
+def _parse_scales(text: str) -> list[float]:
+    try:
+        scales = [float(t) for t in text.split(",") if t.strip()]
+    except ValueError:
+        raise SystemExit(f"--scales: not a comma-separated list of numbers: {text!r}")
+    if not scales:
+        raise SystemExit("--scales: at least one scale is required")
+    return scales
+
+
+def cmd_plan(args) -> int:
+    """What-if load plan: the unlimited-mode solution at each load scale."""
+    import numpy as np
+
+    from .engine import FastSweep, SweepEngine
+
+    scales = _parse_scales(args.scales)
+    system, _ = _load_system(args.spec)
+    backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
+    fs = FastSweep(system, backend=backend)
+    try:
+        res = fs.plan(scales=scales)
+    except ValueError as e:
+        print(f"plan: {e}", file=sys.stderr)
+        return 2
+    # servers whose accelerator differs from the scale-1.0 scenario (the
+    # first scale when 1.0 is not among them)
+    ref = scales.index(1.0) if 1.0 in scales else 0
+    acc = res.winners.acc_idx
+    rows = []
+    for s, scale in enumerate(scales):
+        rows.append({
+            "scale": scale,
+            "totalCost": round(float(res.cost_total[s]), 2),
+            "replicas": {
+                name: int(res.replicas_by_acc[s, j]) for j, name in enumerate(fs.acc_names)
+            },
+            "infeasibleServers": int(res.infeasible_servers[s]),
+            "acceleratorChanges": int(np.count_nonzero(acc[s] != acc[ref])),
+        })
+    if args.json:
+        print(json.dumps({"backend": backend, "referenceScale": scales[ref],
+                          "servers": len(fs.server_names), "scenarios": rows}, indent=2))
+        return 0
+    names = fs.acc_names
+    print(f"{'scale':>8} {'cost':>12} " + " ".join(f"{n:>10}" for n in names)
+          + f" {'infeasible':>10} {'acc-changes':>11}")
+    for r in rows:
+        print(f"{r['scale']:>8g} {r['totalCost']:>12.2f} "
+              + " ".join(f"{r['replicas'][n]:>10}" for n in names)
+              + f" {r['infeasibleServers']:>10} {r['acceleratorChanges']:>11}")
+    print(f"({len(fs.server_names)} servers, backend {backend}; acc-changes are "
+          f"relative to scale {scales[ref]:g})")
+    return 0
+
+
 def cmd_analyze(args) -> int:
     from .api import v1alpha1 as api
     from .controller.modelanalyzer import ModelAnalyzer
@@ -92,6 +149,13 @@ def main() -> None:
     ps.add_argument("--backend", choices=["auto", "gpu", "cpu"], default="auto")
     ps.add_argument("--json", action="store_true")
     ps.set_defaults(fn=cmd_solve)
+    pp = sub.add_parser("plan", help="what-if plan: the fleet at several load scales")
+    pp.add_argument("spec")
+    pp.add_argument("--scales", required=True,
+                    help="comma-separated load factors, e.g. 0.5,1,1.5,2")
+    pp.add_argument("--backend", choices=["auto", "gpu", "cpu"], default="auto")
+    pp.add_argument("--json", action="store_true")
+    pp.set_defaults(fn=cmd_plan)
     pa = sub.add_parser("analyze", help="per-variant candidate allocations")
     pa.add_argument("spec")
     pa.add_argument("--server", required=True, help="name:namespace")

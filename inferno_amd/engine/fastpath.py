@@ -46,6 +46,23 @@ class WinnerRecord:
     max_rate: np.ndarray
 
 
+@dataclass
+class PlanResult:
+    """What-if load plan: the unlimited-mode solution of S arrival-rate
+    scenarios of one fleet (FastSweep.plan)."""
+
+    winners: WinnerRecord  # every array [S, n_servers]
+    replicas_by_acc: np.ndarray  # int64 [S, n_acc], columns = FastSweep.acc_names
+    cost_total: np.ndarray  # float64 [S]: fp64 sum of the winners' fp32 cost
+    infeasible_servers: np.ndarray  # int64 [S]: servers with acc_idx == -1
+    arrival: np.ndarray  # float32 [S, n_servers]: the scenarios evaluated
+    cells: Optional[dict] = None  # reconcile_cells() layout, arrays [S, n_cells]
+
+
+_WINNER_FIELDS = ("acc_idx", "num_replicas", "batch", "cost", "value", "itl", "ttft", "rho",
+                  "max_rate")
+
+
 class FastSweep:
     def __init__(self, system: System, server_names: Optional[list[str]] = None,
                  backend: str = "gpu", device: str = "cuda"):
@@ -119,8 +136,9 @@ class FastSweep:
     load_override = None
     cur_override = None
 
-    def _refresh_dynamic(self) -> dict:
-        """Gather per-server dynamic state into per-cell arrays (vectorized)."""
+    def _base_load(self):
+        """(arrival f32, in_tok i32, out_tok i32) per server: the load
+        override when set, else the server objects."""
         n_srv = len(self.server_names)
         if self.load_override is not None:
             arrival, in_tok, out_tok = self.load_override
@@ -136,6 +154,19 @@ class FastSweep:
                 arrival[i] = load.arrivalRate if load is not None else 0.0
                 in_tok[i] = load.avgInTokens if load is not None else 0
                 out_tok[i] = load.avgOutTokens if load is not None else 0
+        return arrival, in_tok, out_tok
+
+    def _refresh_dynamic(self, plan_arrival: Optional[np.ndarray] = None) -> dict:
+        """Gather per-server dynamic state into per-cell arrays (vectorized).
+
+        ``plan_arrival`` ([S, n_servers] fp32, scenario planning) replaces the
+        per-server arrival rate by its maximum over the scenarios: a cell then
+        counts as zero-load only where no scenario loads it, so every loaded
+        cell keeps the batch size a single reconcile of that scenario uses."""
+        n_srv = len(self.server_names)
+        arrival, in_tok, out_tok = self._base_load()
+        if plan_arrival is not None:
+            arrival = plan_arrival.max(axis=0).astype(np.float32)
         if self.cur_override is not None:
             cur_acc, cur_rep, cur_cost = self.cur_override
             cur_acc = np.asarray(cur_acc, dtype=np.int32)
@@ -466,6 +497,184 @@ class FastSweep:
             rho=of[4].copy(),
             max_rate=of[5].copy(),
         )
+
+    # ------------------------------------------------------------------
+    # What-if load planning
+    # ------------------------------------------------------------------
+    def plan(self, scales=None, arrival=None, return_cells: bool = False) -> PlanResult:
+        """Solve S arrival-rate scenarios of the fleet in one pass.
+
+        Exactly one of ``scales`` (S non-negative factors applied to the base
+        arrival rates, as ``float32(base) * float32(scale)``) and ``arrival``
+        (explicit [S, n_servers] float32 rates, req/min) is given; 1 <= S <=
+        256. Token averages, current allocations and everything else are the
+        same in every scenario. Scenario s of the result is what reconcile()
+        returns with that scenario's arrival rates as the load.
+
+        On the GPU each cell is sized once (or takes its sizing-memo hit) and
+        every scenario is evaluated against that sizing; the memo is shared
+        with reconcile(), so planning's hits and misses — one per loaded cell
+        and call, not per scenario — show up in memo_stats(). Planning does
+        not change what a following reconcile() returns.
+        """
+        scen = self._plan_scenarios(scales, arrival)
+        if self.backend == "gpu":
+            winners, totals, cells = self._plan_gpu(scen, return_cells)
+        else:
+            winners, totals, cells = self._plan_cpu(scen), None, None
+        n_acc = len(self.acc_names)
+        has = winners.acc_idx != -1
+        if totals is None:
+            totals = np.zeros((scen.shape[0], n_acc), dtype=np.int64)
+            for s in range(scen.shape[0]):
+                on = winners.acc_idx[s] >= 0
+                np.add.at(totals[s], winners.acc_idx[s][on],
+                          winners.num_replicas[s][on].astype(np.int64))
+        # fp64 sum of the fp32 costs in server order (the device keeps no
+        # fp32 running total: its order of additions would not be fixed)
+        cost_total = np.array(
+            [winners.cost[s][has[s]].astype(np.float64).sum() for s in range(scen.shape[0])],
+            dtype=np.float64,
+        )
+        return PlanResult(
+            winners=winners,
+            replicas_by_acc=totals,
+            cost_total=cost_total,
+            infeasible_servers=(~has).sum(axis=1).astype(np.int64),
+            arrival=scen,
+            cells=cells,
+        )
+
+    def _plan_scenarios(self, scales, arrival) -> np.ndarray:
+        """Validate plan()'s input and return the [S, n_servers] fp32 rates."""
+        from ..ops.sweep import PLAN_MAX_S
+
+        if (scales is None) == (arrival is None):
+            raise ValueError("plan() takes exactly one of scales and arrival")
+        n_srv = len(self.server_names)
+        if scales is not None:
+            try:
+                sc = np.asarray(scales, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"scales is not numeric: {e}") from None
+            if sc.ndim != 1:
+                raise ValueError(f"scales must be 1-D, got shape {sc.shape}")
+            vals, what = sc, "scales"
+        else:
+            try:
+                arr = np.asarray(arrival, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"arrival is not numeric: {e}") from None
+            if arr.ndim != 2 or arr.shape[1] != n_srv:
+                raise ValueError(
+                    f"arrival must have shape [S, {n_srv}], got {arr.shape}"
+                )
+            vals, what = arr, "arrival"
+        n_scen = vals.shape[0]
+        if not 1 <= n_scen <= PLAN_MAX_S:
+            raise ValueError(f"plan() takes 1..{PLAN_MAX_S} scenarios, got {n_scen}")
+        if not np.isfinite(vals).all() or (vals < 0).any():
+            raise ValueError(f"{what} must be finite and non-negative")
+        if scales is not None:
+            base = self._base_load()[0]
+            scen = base[None, :] * vals.astype(np.float32)[:, None]
+        else:
+            scen = vals.astype(np.float32)
+        scen = np.ascontiguousarray(scen, dtype=np.float32)
+        if not np.isfinite(scen).all():
+            raise ValueError(f"{what} overflows float32")
+        return scen
+
+    def _plan_gpu(self, scen: np.ndarray, return_cells: bool):
+        import ctypes
+
+        from ..ops.sweep import HipKernelError
+
+        n_scen, n_srv = scen.shape
+        n_acc = len(self.acc_names)
+        if self.n_cells == 0 or n_acc == 0:
+            w = _empty_winner(n_srv)
+            winners = WinnerRecord(**{
+                f: np.repeat(getattr(w, f)[None, :], n_scen, axis=0) for f in _WINNER_FIELDS
+            })
+            return winners, np.zeros((n_scen, n_acc), dtype=np.int64), None
+        if not hasattr(self, "_gpu"):
+            self._init_gpu_state()
+        st = self._gpu
+        arrs = self._refresh_dynamic(plan_arrival=scen)
+        self._ensure_ctx()
+        self._fill_pinned(arrs)
+        self._sync_buckets(arrs["batch_n"])
+        cell_scen = np.ascontiguousarray(scen[:, self.cell_server], dtype=np.float32)
+        p_f, p_i, p_t = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        rc = st["ctx_lib"].wva_ctx_plan(
+            st["ctx"], ctypes.c_int(n_scen), ctypes.c_int(n_acc),
+            cell_scen.ctypes.data_as(ctypes.c_void_p),
+            ctypes.byref(p_f), ctypes.byref(p_i), ctypes.byref(p_t),
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_plan failed: {rc}")
+
+        def view(ptr, ctype, shape):
+            n = int(np.prod(shape))
+            buf = (ctype * n).from_address(ptr.value)
+            return np.ctypeslib.as_array(buf).reshape(shape).copy()
+
+        of = view(p_f, ctypes.c_float, (n_scen, 6, n_srv))
+        oi = view(p_i, ctypes.c_int32, (n_scen, 4, n_srv))
+        totals = view(p_t, ctypes.c_uint64, (n_scen, n_acc)).astype(np.int64)
+        winners = WinnerRecord(
+            acc_idx=oi[:, 0].copy(), num_replicas=oi[:, 1].copy(), batch=oi[:, 2].copy(),
+            cost=of[:, 0].copy(), value=of[:, 1].copy(), itl=of[:, 2].copy(),
+            ttft=of[:, 3].copy(), rho=of[:, 4].copy(), max_rate=of[:, 5].copy(),
+        )
+        cells = None
+        if return_cells:
+            keys = ("feasible", "zero_empty", "num_replicas", "batch", "cost", "value",
+                    "itl", "ttft", "rho", "max_rate")
+            dtypes = (np.uint8, np.uint8, np.int32, np.int32) + (np.float32,) * 6
+            cells = {k: np.empty((n_scen, self.n_cells), dtype=d) for k, d in zip(keys, dtypes)}
+            dst = (ctypes.c_void_p * len(keys))(
+                *[cells[k].ctypes.data_as(ctypes.c_void_p) for k in keys]
+            )
+            rc = st["ctx_lib"].wva_ctx_plan_cells(st["ctx"], dst)
+            if rc != 0:
+                raise HipKernelError(f"wva_ctx_plan_cells failed: {rc}")
+            cells["cell_server"] = self.cell_server
+            cells["cell_acc_idx"] = self.cell_acc_idx
+            cells["seg_start"] = self.seg_start
+        return winners, totals, cells
+
+    def _plan_cpu(self, scen: np.ndarray) -> WinnerRecord:
+        """Golden path: one _reconcile_cpu per scenario with the scenario's
+        arrival rate (and the load override's token averages, when set) put
+        on the server objects, which are restored afterwards in any case."""
+        n_scen, n_srv = scen.shape
+        _, in_tok, out_tok = self._base_load()
+        saved = [
+            None if srv.load is None
+            else (srv.load.arrivalRate, srv.load.avgInTokens, srv.load.avgOutTokens)
+            for srv in self._srv_objs
+        ]
+        rows = []
+        try:
+            for s in range(n_scen):
+                for i, srv in enumerate(self._srv_objs):
+                    if srv.load is None:
+                        continue  # no load: zero-traffic whatever the scenario says
+                    srv.load.arrivalRate = float(scen[s, i])
+                    if self.load_override is not None:
+                        srv.load.avgInTokens = int(in_tok[i])
+                        srv.load.avgOutTokens = int(out_tok[i])
+                rows.append(self._reconcile_cpu())
+        finally:
+            for srv, old in zip(self._srv_objs, saved):
+                if old is not None:
+                    (srv.load.arrivalRate, srv.load.avgInTokens,
+                     srv.load.avgOutTokens) = old
+        return WinnerRecord(**{
+            f: np.stack([getattr(r, f) for r in rows]) for f in _WINNER_FIELDS
+        })
 
     def _reconcile_cpu(self) -> WinnerRecord:
         """Golden scalar path returning the same winner records."""

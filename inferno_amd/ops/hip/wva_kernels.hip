@@ -52,6 +52,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #define WVA_WAVE 64
 // max LDS-resident batch size per cell (bounds the LDS chain geometry:
 // chunk*NT fp32 reciprocals + NT*ksub fp64 anchors + a 40-double header).
@@ -639,6 +641,142 @@ __device__ __forceinline__ void memo_store(WvaMemoRec *rec, const WvaMemoKey &k,
   rec->status = status;
 }
 
+// Zero-traffic result of one cell (ref allocation.go:73-75, 259-288) into
+// output slot o: the empty allocation when the server may scale to zero, else
+// min_replicas at the profile's max batch. Called by thread 0 only.
+template <typename SlotT>
+__device__ __forceinline__ void wva_write_zero(const WvaCellsOut &out, SlotT o, int min_rep,
+                                               const int *perf_max_batch, int cell,
+                                               float acc_cost, float alpha, float beta,
+                                               float gamma, float delta, bool has_cur,
+                                               bool cur_same, bool cur_empty, int cur_rep,
+                                               float cur_cost) {
+  if (min_rep == 0) {
+    out.feasible[o] = 1;
+    out.zero_empty[o] = 1;
+    out.num_replicas[o] = 0;
+    out.batch[o] = 0;
+    out.cost[o] = 0.0f;
+    out.itl[o] = 0.0f;
+    out.ttft[o] = 0.0f;
+    out.rho[o] = 0.0f;
+    out.max_rate[o] = 0.0f;
+    float value = 0.0f;
+    if (has_cur) {
+      if (cur_empty)
+        value = (cur_rep == 0) ? 0.0f : (0.0f - cur_cost);
+      else
+        value = WVA_ACCEL_PENALTY * cur_cost + (0.0f - cur_cost);
+    }
+    out.value[o] = value;
+  } else {
+    int max_batch = perf_max_batch[cell];
+    float cost = acc_cost * (float)min_rep;
+    float decode1 = alpha + beta;
+    // product rounded before the add in EVERY instantiation: the compiler
+    // otherwise fuses it in some (planning) and not in others (it packs this
+    // add with decode1's in the single-scenario kernels), and a scenario
+    // slice must equal the single-scenario result bit for bit
+    float max_decode;
+    {
+#pragma clang fp contract(off)
+      max_decode = alpha + beta * (float)max_batch;
+    }
+    float prefill1 = gamma + delta;
+    float max_serv = prefill1 + max_decode;
+    out.feasible[o] = 1;
+    out.zero_empty[o] = 0;
+    out.num_replicas[o] = min_rep;
+    out.batch[o] = max_batch;
+    out.cost[o] = cost;
+    out.itl[o] = decode1;
+    out.ttft[o] = prefill1;
+    out.rho[o] = 0.0f;
+    out.max_rate[o] = (max_serv > 0.0f) ? (float)max_batch / max_serv : 0.0f;
+    float value = cost;
+    if (has_cur) {
+      if (cur_same)
+        value = (cur_rep == min_rep) ? 0.0f : (cost - cur_cost);
+      else
+        value = WVA_ACCEL_PENALTY * (cur_cost + cost) + (cost - cur_cost);
+    }
+    out.value[o] = value;
+  }
+}
+
+// Replicas, cost and the per-replica analysis of one sized cell at arrival
+// rate arr (req/min), written to output slot o (ref allocation.go:134-163).
+// rate_star is the sized per-replica rate (req/sec). Every thread of the block
+// calls this with the same arguments.
+template <int NT, typename SlotT>
+__device__ __forceinline__ void wva_eval_scenario(
+    const WvaCellsOut &out, SlotT o, float arr, int tid, float t_tps, int K, double rate_star,
+    int min_rep, float acc_cost, int analyzer_mode, double mu, int Kstates, double cv2d, int N,
+    const ChainGeom &geom, double logsN, double *scratch, float gamma, float delta, float alpha,
+    float beta, int in_tok, int out_tok, bool has_cur, bool cur_same, bool cur_empty,
+    int cur_rep, float cur_cost) {
+  double total_rate;  // req/sec (ref allocation.go:134-139)
+  if (t_tps == 0.0f)
+    total_rate = (double)arr / 60.0;
+  else
+    total_rate = (double)t_tps / (double)K;
+  double reps_d = ceil(total_rate / rate_star);
+  if (!(reps_d > 0.0)) reps_d = 0.0;
+  if (reps_d > 2147483000.0) reps_d = 2147483000.0;
+  int num_replicas = (int)reps_d;
+  if (num_replicas < min_rep) num_replicas = min_rep;
+
+  const float cost = acc_cost * (float)num_replicas;
+
+  // ---- per-replica analyze (ref allocation.go:148-157) ----
+  const double rate = total_rate / (double)num_replicas;
+  double wait2, eff, rho;
+  if (analyzer_mode == 1) {
+    Mg1Out o2 = mg1_eval(rate / 1000.0, mu, Kstates, cv2d, N);
+    wait2 = o2.wait;
+    eff = o2.eff;
+    rho = o2.rho;
+  } else {
+    ChainOut c2 = chain_eval<NT, 1>(rate / 1000.0, geom, logsN, N, Kstates, scratch);
+    wait2 = c2.wait;
+    eff = effective_concurrency(c2.serv, gamma, alpha, delta, beta, in_tok, out_tok, N);
+    rho = fmin(fmax(c2.in_servers / (double)N, 0.0), 1.0);
+  }
+  const float prefill_t = prefill_time_f(gamma, delta, in_tok, (float)eff);
+  const float token_t = decode_time_f(alpha, beta, (float)eff);
+
+  if (tid == 0) {
+    out.feasible[o] = 1;
+    out.zero_empty[o] = 0;
+    out.num_replicas[o] = num_replicas;
+    out.batch[o] = N;
+    out.cost[o] = cost;
+    out.itl[o] = token_t;
+    out.ttft[o] = (float)wait2 + prefill_t;
+    out.rho[o] = (float)rho;
+    out.max_rate[o] = (float)(rate_star / 1000.0);
+    float value = cost;
+    if (has_cur) {
+      if (cur_same && !cur_empty)
+        value = (cur_rep == num_replicas) ? 0.0f : (cost - cur_cost);
+      else
+        value = WVA_ACCEL_PENALTY * (cur_cost + cost) + (cost - cur_cost);
+    }
+    out.value[o] = value;
+  }
+}
+
+// scenario-planning arguments of the sweep body; the single-scenario
+// instantiation takes an empty struct in their place
+struct WvaPlanArgs {
+  int n_cells;
+  int n_scen;
+  const float *scen_arrival;  // device, [n_scen][n_cells]
+};
+struct WvaNoPlan {};
+template <bool PLAN>
+using WvaPlanParam = typename std::conditional<PLAN, WvaPlanArgs, WvaNoPlan>::type;
+
 // ---------------------------------------------------------------------------
 // K1: allocate-sweep — one block per cell; cell_ids selects this launch's
 // N-bucket (nullptr = identity).
@@ -650,12 +788,21 @@ __device__ __forceinline__ void memo_store(WvaMemoRec *rec, const WvaMemoKey &k,
 // bit-identical results; used for the rare huge-N cells so the sweep stays
 // uncapped like the reference. The slab layout mirrors the LDS layout
 // (chunk-transposed reciprocals), which is also the coalesced global layout.
-template <int NT, bool GMEM>
-__global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut out, int n_blocks,
-                                                  const int *cell_ids, int max_n,
-                                                  int analyzer_mode, float cv2,
-                                                  float *g_inv, double *g_anchor,
-                                                  WvaMemoRec *memo, unsigned *memo_cnt) {
+//
+// PLAN=true is the scenario-planning variant: the cell is sized ONCE (or takes its memo hit) and then every one of n_scen arrival
+// rates (scen_arrival[s * n_cells + cell]) is evaluated against that sizing;
+// outputs are [n_scen][n_cells], scenario-major. Nothing the sizing phase
+// reads depends on the arrival rate (see the memo key), so slice s is bit for
+// bit what a single-scenario launch with that arrival rate writes. Both
+// variants compile from this one body; every difference is an
+// `if constexpr (PLAN)`.
+template <int NT, bool GMEM, bool PLAN>
+__device__ __forceinline__ void wva_sweep_body(const WvaCellsIn &in, const WvaCellsOut &out,
+                                               int n_blocks, const int *cell_ids, int max_n,
+                                               int analyzer_mode, float cv2, float *g_inv,
+                                               double *g_anchor, WvaMemoRec *memo,
+                                               unsigned *memo_cnt,
+                                               const WvaPlanParam<PLAN> &plan) {
   // memo: per-cell sizing records (nullptr = memo off: every cell is sized
   // from scratch and nothing is recorded); memo_cnt: [0] hits, [1] misses
   extern __shared__ double smem[];
@@ -688,53 +835,48 @@ __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut 
   const bool has_cur = flags & 4;
 
   // ---- zero-traffic path (ref allocation.go:73-75, 259-288) ----
-  if (arrival == 0.0f || out_tok == 0) {
-    if (tid == 0) {
-      if (min_rep == 0) {
-        out.feasible[cell] = 1;
-        out.zero_empty[cell] = 1;
-        out.num_replicas[cell] = 0;
-        out.batch[cell] = 0;
-        out.cost[cell] = 0.0f;
-        out.itl[cell] = 0.0f;
-        out.ttft[cell] = 0.0f;
-        out.rho[cell] = 0.0f;
-        out.max_rate[cell] = 0.0f;
-        float value = 0.0f;
-        if (has_cur) {
-          if (cur_empty)
-            value = (cur_rep == 0) ? 0.0f : (0.0f - cur_cost);
-          else
-            value = WVA_ACCEL_PENALTY * cur_cost + (0.0f - cur_cost);
-        }
-        out.value[cell] = value;
-      } else {
-        int max_batch = in.perf_max_batch[cell];
-        float cost = acc_cost * (float)min_rep;
-        float decode1 = alpha + beta;
-        float max_decode = alpha + beta * (float)max_batch;
-        float prefill1 = gamma + delta;
-        float max_serv = prefill1 + max_decode;
-        out.feasible[cell] = 1;
-        out.zero_empty[cell] = 0;
-        out.num_replicas[cell] = min_rep;
-        out.batch[cell] = max_batch;
-        out.cost[cell] = cost;
-        out.itl[cell] = decode1;
-        out.ttft[cell] = prefill1;
-        out.rho[cell] = 0.0f;
-        out.max_rate[cell] = (max_serv > 0.0f) ? (float)max_batch / max_serv : 0.0f;
-        float value = cost;
-        if (has_cur) {
-          if (cur_same)
-            value = (cur_rep == min_rep) ? 0.0f : (cost - cur_cost);
-          else
-            value = WVA_ACCEL_PENALTY * (cur_cost + cost) + (cost - cur_cost);
-        }
-        out.value[cell] = value;
-      }
+  // (thread 0 only) the zero-traffic result into output slot o
+#define WVA_WRITE_ZERO(o)                                                                   \
+  wva_write_zero(out, (o), min_rep, in.perf_max_batch, cell, acc_cost, alpha, beta, gamma,  \
+                 delta, has_cur, cur_same, cur_empty, cur_rep, cur_cost)
+  // (thread 0 only) the "no allocation on this accelerator" verdict. Planning:
+  // per scenario the zero-traffic decision still comes first, exactly as a
+  // single-scenario launch orders it.
+#define WVA_WRITE_INFEASIBLE()                                                              \
+  do {                                                                                      \
+    if constexpr (PLAN) {                                                                   \
+      for (int s = 0; s < plan.n_scen; ++s) {                                               \
+        const size_t o = (size_t)s * (size_t)plan.n_cells + (size_t)cell;                   \
+        if (plan.scen_arrival[o] == 0.0f) {                                                 \
+          WVA_WRITE_ZERO(o);                                                                \
+        } else {                                                                            \
+          out.feasible[o] = 0;                                                              \
+          out.zero_empty[o] = 0;                                                            \
+        }                                                                                   \
+      }                                                                                     \
+    } else {                                                                                \
+      out.feasible[cell] = 0;                                                               \
+      out.zero_empty[cell] = 0;                                                             \
+    }                                                                                       \
+  } while (0)
+  if constexpr (PLAN) {
+    // zero-traffic in EVERY scenario (block-uniform: depends on the cell only)
+    bool any_load = false;
+    if (out_tok != 0)
+      for (int s = 0; s < plan.n_scen; ++s)
+        any_load = any_load ||
+                   (plan.scen_arrival[(size_t)s * (size_t)plan.n_cells + (size_t)cell] != 0.0f);
+    if (!any_load) {
+      if (tid == 0)
+        for (int s = 0; s < plan.n_scen; ++s)
+          WVA_WRITE_ZERO((size_t)s * (size_t)plan.n_cells + (size_t)cell);
+      return;
     }
-    return;
+  } else {
+    if (arrival == 0.0f || out_tok == 0) {
+      if (tid == 0) WVA_WRITE_ZERO(cell);
+      return;
+    }
   }
 
   // ---- sizing memo lookup: every thread loads the cell's record (same
@@ -759,10 +901,7 @@ __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut 
     if (tid == 0) atomicAdd(memo_cnt + (same ? 0 : 1), 1u);
     if (memo_status == WVA_MEMO_INFEASIBLE) {
       // replay of the infeasible verdict: no geometry, no evaluations
-      if (tid == 0) {
-        out.feasible[cell] = 0;
-        out.zero_empty[cell] = 0;
-      }
+      if (tid == 0) WVA_WRITE_INFEASIBLE();
       return;
     }
   }
@@ -857,10 +996,7 @@ __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut 
   // golden's AnalyzerError guard)
   const double any_bad = red_max_p<NT, 1>(bad_rate ? 1.0 : 0.0, scratch);
   if (any_bad > 0.0 || !(s1 > 0.0f) || !(sN > 0.0f) || !isfinite(s1) || !isfinite(sN)) {
-    if (tid == 0) {
-      out.feasible[cell] = 0;
-      out.zero_empty[cell] = 0;
-    }
+    if (tid == 0) WVA_WRITE_INFEASIBLE();
     memo_miss_store(0.0, WVA_MEMO_INFEASIBLE);
     return;
   }
@@ -895,10 +1031,7 @@ __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut 
       if (inds[1] < 0) feasible = false;
     }
     if (!feasible) {
-      if (tid == 0) {
-        out.feasible[cell] = 0;
-        out.zero_empty[cell] = 0;
-      }
+      if (tid == 0) WVA_WRITE_INFEASIBLE();
       memo_miss_store(0.0, WVA_MEMO_INFEASIBLE);
       return;
     }
@@ -915,55 +1048,64 @@ __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut 
   }
   const double rate_star = tput_at_lam * 1000.0;  // req/sec
 
-  double total_rate;  // req/sec (ref allocation.go:134-139)
-  if (t_tps == 0.0f)
-    total_rate = (double)arrival / 60.0;
-  else
-    total_rate = (double)t_tps / (double)K;
-  double reps_d = ceil(total_rate / rate_star);
-  if (!(reps_d > 0.0)) reps_d = 0.0;
-  if (reps_d > 2147483000.0) reps_d = 2147483000.0;
-  int num_replicas = (int)reps_d;
-  if (num_replicas < min_rep) num_replicas = min_rep;
-
-  const float cost = acc_cost * (float)num_replicas;
-
-  // ---- per-replica analyze (ref allocation.go:148-157) ----
-  const double rate = total_rate / (double)num_replicas;
-  double wait2, eff, rho;
-  if (analyzer_mode == 1) {
-    Mg1Out o2 = mg1_eval(rate / 1000.0, mu, Kstates, cv2d, N);
-    wait2 = o2.wait;
-    eff = o2.eff;
-    rho = o2.rho;
-  } else {
-    ChainOut c2 = chain_eval<NT, 1>(rate / 1000.0, geom, logsN, N, Kstates, scratch);
-    wait2 = c2.wait;
-    eff = effective_concurrency(c2.serv, gamma, alpha, delta, beta, in_tok, out_tok, N);
-    rho = fmin(fmax(c2.in_servers / (double)N, 0.0), 1.0);
-  }
-  const float prefill_t = prefill_time_f(gamma, delta, in_tok, (float)eff);
-  const float token_t = decode_time_f(alpha, beta, (float)eff);
-
-  if (tid == 0) {
-    out.feasible[cell] = 1;
-    out.zero_empty[cell] = 0;
-    out.num_replicas[cell] = num_replicas;
-    out.batch[cell] = N;
-    out.cost[cell] = cost;
-    out.itl[cell] = token_t;
-    out.ttft[cell] = (float)wait2 + prefill_t;
-    out.rho[cell] = (float)rho;
-    out.max_rate[cell] = (float)(rate_star / 1000.0);
-    float value = cost;
-    if (has_cur) {
-      if (cur_same && !cur_empty)
-        value = (cur_rep == num_replicas) ? 0.0f : (cost - cur_cost);
-      else
-        value = WVA_ACCEL_PENALTY * (cur_cost + cost) + (cost - cur_cost);
+  // ---- per scenario: replicas, cost and the per-replica analysis (the
+  // single-scenario instantiations evaluate the cell's own arrival rate).
+  // Block-uniform: the arrival rate depends only on (cell, scenario), so every
+  // barrier inside chain_eval stays uniform; consecutive chain_eval calls are
+  // ordered as the sized-rate and per-replica evaluations always were (single-
+  // wave blocks only READ LDS there, wider blocks enter each reduction through
+  // a barrier).
+  if constexpr (PLAN) {
+    for (int s = 0; s < plan.n_scen; ++s) {
+      // output slot s * n_cells + cell (up to 256 scenarios of the fleet)
+      const size_t o = (size_t)s * (size_t)plan.n_cells + (size_t)cell;
+      const float arr = plan.scen_arrival[o];
+      if (arr == 0.0f) {
+        if (tid == 0) WVA_WRITE_ZERO(o);
+        continue;
+      }
+      wva_eval_scenario<NT>(out, o, arr, tid, t_tps, K, rate_star, min_rep, acc_cost,
+                            analyzer_mode, mu, Kstates, cv2d, N, geom, logsN, scratch, gamma, delta,
+                            alpha, beta, in_tok, out_tok, has_cur, cur_same, cur_empty, cur_rep,
+                            cur_cost);
     }
-    out.value[cell] = value;
+  } else {
+    wva_eval_scenario<NT>(out, cell, arrival, tid, t_tps, K, rate_star, min_rep, acc_cost,
+                          analyzer_mode, mu, Kstates, cv2d, N, geom, logsN, scratch, gamma, delta,
+                          alpha, beta, in_tok, out_tok, has_cur, cur_same, cur_empty, cur_rep,
+                          cur_cost);
   }
+#undef WVA_WRITE_INFEASIBLE
+#undef WVA_WRITE_ZERO
+}
+
+template <int NT, bool GMEM>
+__global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut out, int n_blocks,
+                                                  const int *cell_ids, int max_n,
+                                                  int analyzer_mode, float cv2,
+                                                  float *g_inv, double *g_anchor,
+                                                  WvaMemoRec *memo, unsigned *memo_cnt) {
+  wva_sweep_body<NT, GMEM, false>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2, g_inv,
+                                  g_anchor, memo, memo_cnt, WvaNoPlan{});
+}
+
+// scenario-planning sweep: out arrays are [n_scen][n_cells]; in.arrival_rate
+// is not read. WVA_PLAN_MIN_WAVES is the occupancy the register budget is
+// sized for. The reconcile kernels use 4 (128 VGPRs); the scenario loop keeps
+// more state live, and at 4 it spills 116-176 B/lane. At 2 it takes 162-175
+// VGPRs with no scratch and measured 5-7% faster end to end
+// (docs/design/kernels.md, "Scenario planning").
+#ifndef WVA_PLAN_MIN_WAVES
+#define WVA_PLAN_MIN_WAVES 2
+#endif
+template <int NT, bool GMEM>
+__global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES) wva_plan_t(WvaCellsIn in, WvaCellsOut out, int n_blocks,
+                                                 const int *cell_ids, int max_n,
+                                                 int analyzer_mode, float cv2, float *g_inv,
+                                                 double *g_anchor, WvaMemoRec *memo,
+                                                 unsigned *memo_cnt, WvaPlanArgs plan) {
+  wva_sweep_body<NT, GMEM, true>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2, g_inv,
+                                 g_anchor, memo, memo_cnt, plan);
 }
 
 // ---------------------------------------------------------------------------
@@ -1011,10 +1153,10 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_argmin(
 static int wva_optin_lds(const void *func, size_t lds) {
   constexpr size_t kDefaultCap = 64 * 1024;
   if (lds <= kDefaultCap) return 0;
-  static const void *funcs[8] = {};
-  static size_t sizes[8] = {};
+  static const void *funcs[16] = {};
+  static size_t sizes[16] = {};
   int slot = -1;
-  for (int i = 0; i < 8; ++i) {
+  for (int i = 0; i < 16; ++i) {
     if (funcs[i] == func) {
       if (sizes[i] >= lds) return 0;
       slot = i;
@@ -1035,7 +1177,8 @@ static int wva_optin_lds(const void *func, size_t lds) {
 static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_ids,
                               int analyzer_mode, float cv2, hipStream_t s,
                               const WvaCellsIn &in, const WvaCellsOut &out, float *g_inv,
-                              double *g_anchor, WvaMemoRec *memo, unsigned *memo_cnt) {
+                              double *g_anchor, WvaMemoRec *memo, unsigned *memo_cnt,
+                              const WvaPlanArgs *plan = nullptr) {
   if (n_blocks <= 0) return 0;
   const bool gmem = g_inv != nullptr && g_anchor != nullptr;
   if (max_n < 1) return -2;
@@ -1048,8 +1191,19 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
   size_t lds = gmem ? (size_t)40 * sizeof(double)
                     : (size_t)(40 + (chunk * nt + 1) / 2 + (size_t)nt * ksub) * sizeof(double);
   if (lds > 160 * 1024) return -5;  // exceeds the CU's LDS
+  // the >64 KiB opt-in is per function, so the planning instantiation of a
+  // width opts in separately from the reconcile one
 #define WVA_LAUNCH(NTV, GM)                                                                 \
   do {                                                                                      \
+    if (plan != nullptr) {                                                                  \
+      int prc =                                                                             \
+          wva_optin_lds(reinterpret_cast<const void *>(&wva_plan_t<NTV, GM>), lds);  \
+      if (prc != 0) return prc;                                                             \
+      hipLaunchKernelGGL((wva_plan_t<NTV, GM>), dim3(n_blocks), dim3(NTV), lds, s,   \
+                         in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2, g_inv,     \
+                         g_anchor, memo, memo_cnt, *plan);                                  \
+      break;                                                                                \
+    }                                                                                       \
     int orc = wva_optin_lds(reinterpret_cast<const void *>(&wva_sweep_t<NTV, GM>), lds);    \
     if (orc != 0) return orc;                                                               \
     hipLaunchKernelGGL((wva_sweep_t<NTV, GM>), dim3(n_blocks), dim3(NTV), lds, s, in, out,  \
@@ -1156,6 +1310,69 @@ extern "C" __global__ void __launch_bounds__(256) wva_gather(
 }
 
 // ---------------------------------------------------------------------------
+// K4 wva_plan_reduce: winner selection + winner record + per-accelerator
+// replica totals for every (server, scenario) of a planning sweep in one
+// launch. Grid (n_srv, n_scen), one wave each. The selection is wva_argmin's
+// rule on scenario slice s (minimum value over feasible cells, lowest cell
+// index on ties), the record is wva_gather's, written into
+// pf[n_scen][6][n_srv] / pi[n_scen][4][n_srv]. totals[n_scen][n_acc] must be
+// zero on entry; the winner's replica count is added with a 64-bit integer
+// atomic (a cell may hold 2 147 483 000 replicas, and integer adds make the
+// sum independent of execution order).
+// ---------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_reduce(
+    const float *value, const uint8_t *feasible, const uint8_t *zero_empty, const int *cell_acc,
+    const int *num_replicas, const int *batch, const float *cost, const float *itl,
+    const float *ttft, const float *rho, const float *max_rate, const int *seg_start, int n_srv,
+    int n_cells, int n_scen, int n_acc, float *pf, int *pi, unsigned long long *totals) {
+  const int srv = blockIdx.x;
+  const int sc = blockIdx.y;
+  if (srv >= n_srv || sc >= n_scen) return;
+  const int lane = threadIdx.x;
+  const size_t base = (size_t)sc * (size_t)n_cells;
+  const int beg = seg_start[srv], end = seg_start[srv + 1];
+  float best = INFINITY;
+  int best_i = -1;
+  for (int i = beg + lane; i < end; i += WVA_WAVE) {
+    if (!feasible[base + i]) continue;
+    float v = value[base + i];
+    if (best_i == -1 || v < best) {
+      best = v;
+      best_i = i;
+    }
+  }
+#pragma unroll
+  for (int off = WVA_WAVE / 2; off > 0; off >>= 1) {
+    float ov = __shfl_down(best, off, WVA_WAVE);
+    int oi = __shfl_down(best_i, off, WVA_WAVE);
+    if (oi != -1 && (best_i == -1 || ov < best || (ov == best && oi < best_i))) {
+      best = ov;
+      best_i = oi;
+    }
+  }
+  if (lane != 0) return;
+  const int w = best_i;
+  const bool has = w >= 0;
+  const size_t wc = base + (size_t)(has ? w : 0);
+  float *gf = pf + (size_t)sc * 6 * (size_t)n_srv;
+  int *gi = pi + (size_t)sc * 4 * (size_t)n_srv;
+  const int acc = has ? (zero_empty[wc] ? -2 : cell_acc[w]) : -1;
+  const int reps = has ? num_replicas[wc] : 0;
+  gf[0 * n_srv + srv] = has ? cost[wc] : 0.0f;
+  gf[1 * n_srv + srv] = has ? value[wc] : 0.0f;
+  gf[2 * n_srv + srv] = has ? itl[wc] : 0.0f;
+  gf[3 * n_srv + srv] = has ? ttft[wc] : 0.0f;
+  gf[4 * n_srv + srv] = has ? rho[wc] : 0.0f;
+  gf[5 * n_srv + srv] = has ? max_rate[wc] : 0.0f;
+  gi[0 * n_srv + srv] = acc;
+  gi[1 * n_srv + srv] = reps;
+  gi[2 * n_srv + srv] = has ? batch[wc] : 0;
+  gi[3 * n_srv + srv] = w;
+  if (acc >= 0 && acc < n_acc && reps > 0)
+    atomicAdd(totals + (size_t)sc * (size_t)n_acc + (size_t)acc, (unsigned long long)reps);
+}
+
+// ---------------------------------------------------------------------------
 // Native reconcile context: the whole per-tick device pipeline behind ONE C
 // call (H2D copies, regime-bucketed sweep launches overlapped via events on
 // three streams, argmin, gather, D2H, sync) — no per-step host dispatch
@@ -1210,6 +1427,22 @@ struct WvaCtx {
   // stays valid.
   WvaMemoRec *memo;
   unsigned *memo_cnt;
+  // scenario planning (wva_ctx_plan): buffers allocated on first use, grown
+  // to the largest scenario count / accelerator count seen, freed in destroy
+  int plan_cap;      // scenarios the buffers hold (0 = not allocated)
+  int plan_acc_cap;  // accelerators per totals row the buffers hold
+  int plan_s;        // scenario count of the last successful plan (0 = none)
+  void *plan_dev;    // one device allocation, carved up below
+  void *plan_pin;    // one pinned host allocation, carved up below
+  float *plan_scen;  // device [S][n_cells]
+  WvaCellsOut plan_out;  // device, each [S][n_cells]
+  float *plan_pf;    // device [S][6][n_srv]
+  int *plan_pi;      // device [S][4][n_srv]
+  unsigned long long *plan_tot;  // device [S][n_acc]
+  float *plan_pin_scen;  // pinned mirrors of plan_scen / pf / pi / tot
+  float *plan_pin_pf;
+  int *plan_pin_pi;
+  unsigned long long *plan_pin_tot;
 };
 
 // pointer-slot order for wva_ctx_create (host mirrors in ops/sweep.py):
@@ -1233,6 +1466,11 @@ extern "C" void *wva_ctx_create(int n_cells, int n_srv, void **p) {
   c->graph_state = 0;
   c->memo = nullptr;
   c->memo_cnt = nullptr;
+  c->plan_cap = 0;
+  c->plan_acc_cap = 0;
+  c->plan_s = 0;
+  c->plan_dev = nullptr;
+  c->plan_pin = nullptr;
   char *di = (char *)p[0];
   char *df = (char *)p[1];
   size_t ci = (size_t)n_cells * sizeof(int);
@@ -1460,6 +1698,190 @@ extern "C" int wva_reconcile(void *ctx) {
   return (int)hipStreamSynchronize(c->s0);
 }
 
+// ---------------------------------------------------------------------------
+// Scenario planning: S arrival-rate scenarios of the whole fleet in one pass.
+// Shares the context's static arrays, dynamic int arrays, buckets and sizing
+// memo with wva_reconcile; owns only the scenario arrivals, the [S][n_cells]
+// outputs and the reduce outputs. The hipGraph path is not involved.
+// ---------------------------------------------------------------------------
+#define WVA_PLAN_MAX_S 256
+
+static void wva_plan_release(WvaCtx *c) {
+  if (c->plan_dev != nullptr) (void)hipFree(c->plan_dev);
+  if (c->plan_pin != nullptr) (void)hipHostFree(c->plan_pin);
+  c->plan_dev = nullptr;
+  c->plan_pin = nullptr;
+  c->plan_cap = 0;
+  c->plan_acc_cap = 0;
+  c->plan_s = 0;
+}
+
+static size_t wva_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// (re)allocate the planning buffers for n_scen scenarios and n_acc
+// accelerators; on failure nothing is held and the context is otherwise intact
+static int wva_plan_reserve(WvaCtx *c, int n_scen, int n_acc) {
+  if (n_scen <= c->plan_cap && n_acc <= c->plan_acc_cap) return 0;
+  const int cap = n_scen > c->plan_cap ? n_scen : c->plan_cap;
+  const int acap = n_acc > c->plan_acc_cap ? n_acc : c->plan_acc_cap;
+  wva_plan_release(c);
+  const size_t cells = (size_t)cap * (size_t)c->n_cells;
+  const size_t b_scen = wva_align256(cells * sizeof(float));
+  const size_t b_w = wva_align256(cells * 4);  // one 4-byte per-cell array
+  const size_t b_b = wva_align256(cells);      // one 1-byte per-cell array
+  const size_t b_pf = wva_align256((size_t)cap * 6 * c->n_srv * sizeof(float));
+  const size_t b_pi = wva_align256((size_t)cap * 4 * c->n_srv * sizeof(int));
+  const size_t b_tot = wva_align256((size_t)cap * acap * sizeof(unsigned long long));
+  const size_t dev_bytes = b_scen + 8 * b_w + 2 * b_b + b_pf + b_pi + b_tot;
+  const size_t pin_bytes = b_scen + b_pf + b_pi + b_tot;
+
+  int prev_dev = -1, dev = -1;
+  hipPointerAttribute_t attr;
+  if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
+  if (hipPointerGetAttributes(&attr, c->dev_i) == hipSuccess) dev = attr.device;
+  const bool switched = dev >= 0 && prev_dev >= 0 && dev != prev_dev &&
+                        hipSetDevice(dev) == hipSuccess;
+  void *d = nullptr, *h = nullptr;
+  bool ok = hipMalloc(&d, dev_bytes) == hipSuccess && d != nullptr;
+  ok = ok && hipHostMalloc(&h, pin_bytes, hipHostMallocDefault) == hipSuccess && h != nullptr;
+  // infeasible cells write only their two flags; start from zeros so the
+  // other fields of such cells are defined
+  ok = ok && hipMemsetAsync(d, 0, dev_bytes, c->s0) == hipSuccess;
+  if (switched) (void)hipSetDevice(prev_dev);
+  if (!ok) {
+    if (d != nullptr) (void)hipFree(d);
+    if (h != nullptr) (void)hipHostFree(h);
+    (void)hipGetLastError();  // the context stays usable for wva_reconcile
+    return -30;
+  }
+  c->plan_dev = d;
+  c->plan_pin = h;
+  c->plan_cap = cap;
+  c->plan_acc_cap = acap;
+  char *q = (char *)d;
+  c->plan_scen = (float *)q;             q += b_scen;
+  c->plan_out.num_replicas = (int *)q;   q += b_w;
+  c->plan_out.batch = (int *)q;          q += b_w;
+  c->plan_out.cost = (float *)q;         q += b_w;
+  c->plan_out.value = (float *)q;        q += b_w;
+  c->plan_out.itl = (float *)q;          q += b_w;
+  c->plan_out.ttft = (float *)q;         q += b_w;
+  c->plan_out.rho = (float *)q;          q += b_w;
+  c->plan_out.max_rate = (float *)q;     q += b_w;
+  c->plan_out.feasible = (uint8_t *)q;   q += b_b;
+  c->plan_out.zero_empty = (uint8_t *)q; q += b_b;
+  c->plan_pf = (float *)q;               q += b_pf;
+  c->plan_pi = (int *)q;                 q += b_pi;
+  c->plan_tot = (unsigned long long *)q;
+  q = (char *)h;
+  c->plan_pin_scen = (float *)q;         q += b_scen;
+  c->plan_pin_pf = (float *)q;           q += b_pf;
+  c->plan_pin_pi = (int *)q;             q += b_pi;
+  c->plan_pin_tot = (unsigned long long *)q;
+  return 0;
+}
+
+// One planning pass. scen_arrival: host, [n_scen][n_cells] fp32 (req/min).
+// The caller has filled the context's pinned dynamic arrays and set the
+// buckets, exactly as for wva_reconcile. On success the three out pointers
+// name the context's pinned result buffers, valid until the next
+// wva_ctx_plan or wva_ctx_destroy: pf [n_scen][6][n_srv] fp32 (cost, value,
+// itl, ttft, rho, max_rate), pi [n_scen][4][n_srv] i32 (acc code, replicas,
+// batch, winner cell), totals [n_scen][n_acc] u64.
+extern "C" int wva_ctx_plan(void *ctx, int n_scen, int n_acc, const float *scen_arrival,
+                            const void **out_pf, const void **out_pi,
+                            const void **out_totals) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || scen_arrival == nullptr) return -31;
+  if (n_scen < 1 || n_scen > WVA_PLAN_MAX_S || n_acc < 1) return -32;
+  if (c->n_cells <= 0 || c->n_srv <= 0) return -33;
+  c->plan_s = 0;
+  int rc = wva_plan_reserve(c, n_scen, n_acc);
+  if (rc != 0) return rc;
+  const size_t cells = (size_t)n_scen * (size_t)c->n_cells;
+  hipError_t err;
+
+  // 1. uploads: scenario arrivals through the pinned staging buffer, then the
+  // dynamic arrays as wva_enqueue_pipeline does
+  for (size_t i = 0; i < cells; ++i) c->plan_pin_scen[i] = scen_arrival[i];
+  err = hipMemcpyAsync(c->plan_scen, c->plan_pin_scen, cells * sizeof(float),
+                       hipMemcpyHostToDevice, c->s0);
+  if (err != hipSuccess) return (int)err;
+  err = hipMemcpyAsync(c->dev_i, c->pin_i, (size_t)6 * c->n_cells * sizeof(int),
+                       hipMemcpyHostToDevice, c->s0);
+  if (err != hipSuccess) return (int)err;
+  err = hipMemcpyAsync(c->dev_f, c->pin_f, (size_t)2 * c->n_cells * sizeof(float),
+                       hipMemcpyHostToDevice, c->s0);
+  if (err != hipSuccess) return (int)err;
+  err = hipMemsetAsync(c->plan_tot, 0, (size_t)n_scen * n_acc * sizeof(unsigned long long),
+                       c->s0);
+  if (err != hipSuccess) return (int)err;
+  if (hipEventRecord(c->e_up, c->s0) != hipSuccess) return -10;
+
+  // 2. planning buckets: same streams, fork/join and order as the reconcile
+  const WvaPlanArgs pa = {c->n_cells, n_scen, c->plan_scen};
+  for (int i = 0; i < c->n_buckets; ++i) {
+    hipStream_t s = (i == 0) ? c->s0 : c->side[i - 1];
+    if (i > 0 && hipStreamWaitEvent(s, c->e_up, 0) != hipSuccess) return -11;
+    const WvaBucket &b = c->buckets[i];
+    rc = wva_sweep_dispatch(b.n_blocks, b.max_n, b.nt, b.cell_ids, c->analyzer_mode, c->cv2, s,
+                            c->in, c->plan_out, b.g_inv, b.g_anchor, c->memo, c->memo_cnt, &pa);
+    if (rc != 0) return rc;
+    if (i > 0 && hipEventRecord(c->e_b[i - 1], s) != hipSuccess) return -12;
+  }
+  for (int i = 1; i < c->n_buckets; ++i)
+    if (hipStreamWaitEvent(c->s0, c->e_b[i - 1], 0) != hipSuccess) return -14;
+
+  // 3. winners, records and totals for all (server, scenario) pairs
+  hipLaunchKernelGGL(wva_plan_reduce, dim3(c->n_srv, n_scen), dim3(WVA_WAVE), 0, c->s0,
+                     c->plan_out.value, c->plan_out.feasible, c->plan_out.zero_empty,
+                     c->cell_acc, c->plan_out.num_replicas, c->plan_out.batch, c->plan_out.cost,
+                     c->plan_out.itl, c->plan_out.ttft, c->plan_out.rho, c->plan_out.max_rate,
+                     c->seg_start, c->n_srv, c->n_cells, n_scen, n_acc, c->plan_pf, c->plan_pi,
+                     c->plan_tot);
+  err = hipGetLastError();
+  if (err != hipSuccess) return (int)err;
+
+  // 4. downloads
+  err = hipMemcpyAsync(c->plan_pin_pf, c->plan_pf, (size_t)n_scen * 6 * c->n_srv * sizeof(float),
+                       hipMemcpyDeviceToHost, c->s0);
+  if (err != hipSuccess) return (int)err;
+  err = hipMemcpyAsync(c->plan_pin_pi, c->plan_pi, (size_t)n_scen * 4 * c->n_srv * sizeof(int),
+                       hipMemcpyDeviceToHost, c->s0);
+  if (err != hipSuccess) return (int)err;
+  err = hipMemcpyAsync(c->plan_pin_tot, c->plan_tot,
+                       (size_t)n_scen * n_acc * sizeof(unsigned long long),
+                       hipMemcpyDeviceToHost, c->s0);
+  if (err != hipSuccess) return (int)err;
+  err = hipStreamSynchronize(c->s0);
+  if (err != hipSuccess) return (int)err;
+  c->plan_s = n_scen;
+  if (out_pf) *out_pf = c->plan_pin_pf;
+  if (out_pi) *out_pi = c->plan_pin_pi;
+  if (out_totals) *out_totals = c->plan_pin_tot;
+  return 0;
+}
+
+// Per-cell outputs of the last successful wva_ctx_plan, copied into ten host
+// arrays of plan_s * n_cells elements each, in WvaCellsOut order (feasible,
+// zero_empty: u8; num_replicas, batch: i32; cost, value, itl, ttft, rho,
+// max_rate: f32). Synchronous; inspection and tests, not the hot path.
+extern "C" int wva_ctx_plan_cells(void *ctx, void **dst) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || dst == nullptr || c->plan_s < 1) return -31;
+  const size_t cells = (size_t)c->plan_s * (size_t)c->n_cells;
+  const void *src[10] = {c->plan_out.feasible, c->plan_out.zero_empty, c->plan_out.num_replicas,
+                         c->plan_out.batch,    c->plan_out.cost,       c->plan_out.value,
+                         c->plan_out.itl,      c->plan_out.ttft,       c->plan_out.rho,
+                         c->plan_out.max_rate};
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -1;
+  for (int i = 0; i < 10; ++i) {
+    const size_t bytes = cells * (i < 2 ? 1 : 4);
+    if (hipMemcpy(dst[i], src[i], bytes, hipMemcpyDeviceToHost) != hipSuccess) return -2;
+  }
+  return 0;
+}
+
 extern "C" void wva_ctx_destroy(void *ctx) {
   WvaCtx *c = (WvaCtx *)ctx;
   if (c == nullptr) return;
@@ -1471,5 +1893,6 @@ extern "C" void wva_ctx_destroy(void *ctx) {
     (void)hipEventDestroy(c->e_b[i]);
   }
   if (c->memo != nullptr) (void)hipFree(c->memo);
+  wva_plan_release(c);
   delete c;
 }

@@ -19,6 +19,7 @@ MAX_N = 8192  # must match WVA_MAX_N in wva_kernels.hip (64KB-LDS limit)
 # (must match WVA_XL_MAX_N); override to MAX_N to force such cells to GMEM
 XL_MAX_N = int(os.environ.get("INFERNO_XL_MAX_N", "32768"))
 HUGE_MAX_N = 1 << 22  # must match WVA_HUGE_MAX_N (global-memory spill limit)
+PLAN_MAX_S = 256  # must match WVA_PLAN_MAX_S (scenarios per planning pass)
 # N-bucket thresholds (must match WVA_N_SMALL / WVA_N_MED): cells are
 # dispatched to 64- and 256-thread blocks by batch size — widths picked by
 # A/B measurement on MI355X (see choose_buckets); small/medium cells run one
@@ -169,6 +170,19 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
         ctypes.POINTER(ctypes.c_uint),  # hits
         ctypes.POINTER(ctypes.c_uint),  # misses
     ]
+    # scenario planning (engine/fastpath.py FastSweep.plan)
+    lib.wva_ctx_plan.restype = ctypes.c_int
+    lib.wva_ctx_plan.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_int,  # n_scen (1..PLAN_MAX_S)
+        ctypes.c_int,  # n_acc
+        ctypes.c_void_p,  # host fp32 [n_scen][n_cells] arrival rates
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned fp32 [n_scen][6][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_scen][4][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][n_acc]
+    ]
+    lib.wva_ctx_plan_cells.restype = ctypes.c_int
+    lib.wva_ctx_plan_cells.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
     _lib = lib
     return lib
 
