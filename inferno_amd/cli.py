@@ -4,6 +4,7 @@ pkg/config wire format) and print the allocation solution.
   python -m inferno_amd.cli solve system.json [--backend cpu|gpu] [--json]
   python -m inferno_amd.cli analyze system.json --server NAME:NS
   python -m inferno_amd.cli plan system.json --scales 0.5,1,1.5,2 [--backend ...] [--json]
+      [--limited] [--capacity TYPE=N,...] [--saturation-policy P] [--delayed-best-effort]
 """
 from __future__ import annotations
 
@@ -74,18 +75,42 @@ def _parse_scales(text: str) -> list[float]:
     return scales
 
 
+def _parse_capacity(text: str) -> dict:
+    cap = {}
+    for item in text.split(","):
+        if not item.strip():
+            continue
+        name, sep, units = item.partition("=")
+        try:
+            cap[name.strip()] = int(units)
+        except ValueError:
+            sep = ""
+        if not sep or not name.strip():
+            raise SystemExit(f"--capacity: expected TYPE=N[,TYPE=N...], got {item!r}")
+    return cap
+
+
 def cmd_plan(args) -> int:
-    """What-if load plan: the unlimited-mode solution at each load scale."""
+    """What-if load plan: the unlimited-mode solution at each load scale, or
+    with --limited / --capacity the capacity-limited one."""
     import numpy as np
 
     from .engine import FastSweep, SweepEngine
 
     scales = _parse_scales(args.scales)
-    system, _ = _load_system(args.spec)
+    system, opt = _load_system(args.spec)
     backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
     fs = FastSweep(system, backend=backend)
+    limited = args.limited or args.capacity is not None
+    kw = {}
+    if limited:
+        kw["capacity"] = (_parse_capacity(args.capacity) if args.capacity is not None
+                          else dict(system.capacity))
+        kw["saturation_policy"] = (args.saturation_policy if args.saturation_policy is not None
+                                   else opt.saturationPolicy)
+        kw["delayed_best_effort"] = args.delayed_best_effort or bool(opt.delayedBestEffort)
     try:
-        res = fs.plan(scales=scales)
+        res = fs.plan(scales=scales, **kw)
     except ValueError as e:
         print(f"plan: {e}", file=sys.stderr)
         return 2
@@ -104,19 +129,37 @@ def cmd_plan(args) -> int:
             "infeasibleServers": int(res.infeasible_servers[s]),
             "acceleratorChanges": int(np.count_nonzero(acc[s] != acc[ref])),
         })
+        if limited:
+            rows[-1]["unallocatedServers"] = int(res.unallocated_servers[s])
+            rows[-1]["partialServers"] = int(res.partial_servers[s])
+            rows[-1]["capacityLeft"] = {
+                t: int(res.capacity_left[s, j]) for j, t in enumerate(res.capacity_types)
+            }
     if args.json:
-        print(json.dumps({"backend": backend, "referenceScale": scales[ref],
-                          "servers": len(fs.server_names), "scenarios": rows}, indent=2))
+        doc = {"backend": backend, "referenceScale": scales[ref],
+               "servers": len(fs.server_names), "scenarios": rows}
+        if limited:
+            doc["saturationPolicy"] = kw["saturation_policy"]
+            doc["delayedBestEffort"] = kw["delayed_best_effort"]
+        print(json.dumps(doc, indent=2))
         return 0
     names = fs.acc_names
+    types = res.capacity_types if limited else []
     print(f"{'scale':>8} {'cost':>12} " + " ".join(f"{n:>10}" for n in names)
-          + f" {'infeasible':>10} {'acc-changes':>11}")
+          + f" {'infeasible':>10} {'acc-changes':>11}"
+          + (f" {'unallocated':>11} {'partial':>7} "
+             + " ".join(f"{'left:' + t:>10}" for t in types) if limited else ""))
     for r in rows:
         print(f"{r['scale']:>8g} {r['totalCost']:>12.2f} "
               + " ".join(f"{r['replicas'][n]:>10}" for n in names)
-              + f" {r['infeasibleServers']:>10} {r['acceleratorChanges']:>11}")
+              + f" {r['infeasibleServers']:>10} {r['acceleratorChanges']:>11}"
+              + (f" {r['unallocatedServers']:>11} {r['partialServers']:>7} "
+                 + " ".join(f"{r['capacityLeft'][t]:>10}" for t in types) if limited else ""))
     print(f"({len(fs.server_names)} servers, backend {backend}; acc-changes are "
           f"relative to scale {scales[ref]:g})")
+    if limited:
+        print(f"(limited mode: saturation policy {kw['saturation_policy']}, "
+              f"delayed best-effort {'on' if kw['delayed_best_effort'] else 'off'})")
     return 0
 
 
@@ -155,6 +198,14 @@ def main() -> None:
                     help="comma-separated load factors, e.g. 0.5,1,1.5,2")
     pp.add_argument("--backend", choices=["auto", "gpu", "cpu"], default="auto")
     pp.add_argument("--json", action="store_true")
+    pp.add_argument("--limited", action="store_true",
+                    help="capacity-limited plan: inventory, saturation policy and "
+                         "delayed best-effort from the spec")
+    pp.add_argument("--capacity", default=None,
+                    help="inventory as TYPE=N,...; implies --limited and replaces the spec's")
+    pp.add_argument("--saturation-policy", default=None,
+                    choices=["None", "PriorityExhaustive", "PriorityRoundRobin", "RoundRobin"])
+    pp.add_argument("--delayed-best-effort", action="store_true")
     pp.set_defaults(fn=cmd_plan)
     pa = sub.add_parser("analyze", help="per-variant candidate allocations")
     pa.add_argument("spec")

@@ -57,10 +57,58 @@ class PlanResult:
     infeasible_servers: np.ndarray  # int64 [S]: servers with acc_idx == -1
     arrival: np.ndarray  # float32 [S, n_servers]: the scenarios evaluated
     cells: Optional[dict] = None  # reconcile_cells() layout, arrays [S, n_cells]
+    # capacity-limited plans only (plan(capacity=...)); None otherwise. The
+    # winners are then the limited-mode solution: num_replicas is the granted
+    # count, cost and value are scaled by granted/desired.
+    desired_replicas: Optional[np.ndarray] = None  # int32 [S, n_servers]: pre-cut count
+    unallocated_servers: Optional[np.ndarray] = None  # int64 [S]: candidates but no grant
+    partial_servers: Optional[np.ndarray] = None  # int64 [S]: 0 < granted < desired
+    capacity_left: Optional[np.ndarray] = None  # int64 [S, n_types]
+    capacity_types: Optional[list] = None  # columns of capacity_left
 
 
 _WINNER_FIELDS = ("acc_idx", "num_replicas", "batch", "cost", "value", "itl", "ttft", "rho",
                   "max_rate")
+
+# the four SaturationPolicy names as ops/native/greedy.cpp numbers them
+_POLICY_CODE = {"None": 0, "PriorityExhaustive": 1, "PriorityRoundRobin": 2, "RoundRobin": 3}
+
+# Which solver a capacity-limited GPU plan uses when INFERNO_PLAN_GREEDY does
+# not say: "device" (wva_plan_greedy, one wave per scenario) or "host" (the
+# native greedy per scenario over the downloaded cells). Both give the same
+# bytes. At 16 scenarios of the flagship fleet the device path measured slower
+# than the host loop, so the host loop is the default and the kernel is the
+# opt-in (docs/design/kernels.md, "Capacity-limited planning").
+PLAN_GREEDY_DEFAULT = "host"
+# The round-robin policies hand out capacity one unit per step on a single
+# lane; above this many units in a scenario's inventory they take the host
+# loop, where a step costs nanoseconds.
+PLAN_GREEDY_RR_MAX_UNITS = 1 << 18
+
+
+def greedy_candidates(feasible, zero_empty, value, num_replicas, cell_server, cell_tidx,
+                      units, n_srv):
+    """Candidate rows of the native greedy (ops/native/greedy.cpp) from
+    per-cell sweep outputs: the feasible cells in a stable order by (server,
+    float64(value)), so ties keep accelerator-name order exactly like
+    sorted(all_allocations.values(), key=value); zero-load cells get type -1
+    and drop like the Python accelerator-lookup miss.
+
+    Returns (order, seg_start, cand_value, cand_type, cand_units,
+    cand_replicas); order[k] is the cell of candidate row k."""
+    idx = np.nonzero(np.asarray(feasible).astype(bool))[0]
+    srv_of = np.asarray(cell_server)
+    order = idx[np.lexsort((value[idx].astype(np.float64), srv_of[idx]))]
+    counts = np.bincount(srv_of[order], minlength=n_srv)
+    seg = np.zeros(n_srv + 1, dtype=np.int32)
+    np.cumsum(counts, out=seg[1:])
+    cand_value = np.ascontiguousarray(value[order], dtype=np.float32)
+    cand_tidx = np.where(
+        np.asarray(zero_empty)[order].astype(bool), -1, cell_tidx[order]
+    ).astype(np.int32)
+    cand_units = np.ascontiguousarray(units[order], dtype=np.int32)
+    cand_reps = np.ascontiguousarray(num_replicas[order], dtype=np.int32)
+    return order, seg, cand_value, cand_tidx, cand_units, cand_reps
 
 
 class FastSweep:
@@ -125,6 +173,40 @@ class FastSweep:
                            "t_itl", "t_ttft", "t_tps") else np.int32)
             for k, v in stat.items()
         }
+
+    def greedy_static(self):
+        """Static greedy (limited-mode) inputs, cached per fleet topology:
+        (type_names, per-cell type index, per-cell units per replica,
+        per-server priority). type_names is the sorted union of the
+        accelerators' types and system.capacity's keys."""
+        cached = getattr(self, "_greedy_static_cache", None)
+        if cached is not None:
+            return cached
+        system = self.system
+        type_names = sorted(
+            {acc.type for acc in system.accelerators.values()} | set(system.capacity)
+        )
+        type_index = {t: i for i, t in enumerate(type_names)}
+        acc_tidx = np.empty(len(self.acc_names), dtype=np.int32)
+        for i, an in enumerate(self.acc_names):
+            acc_tidx[i] = type_index[system.accelerators[an].type]
+        units = np.empty(self.n_cells, dtype=np.int32)
+        for k in range(self.n_cells):
+            srv = self._srv_objs[self.cell_server[k]]
+            acc_name = self.acc_names[self.cell_acc_idx[k]]
+            acc = system.accelerators[acc_name]
+            model = system.models[srv.model_name]
+            units[k] = model.get_num_instances(acc_name) * acc.multiplicity
+        prio = np.array([s.priority(system) for s in self._srv_objs], dtype=np.int32)
+        cell_tidx = acc_tidx[self.cell_acc_idx]
+        cached = (type_names, cell_tidx, units, prio)
+        self._greedy_static_cache = cached
+        return cached
+
+    @property
+    def capacity_types(self) -> list:
+        """Accelerator types in the column order of plan()'s capacity array."""
+        return list(self.greedy_static()[0])
 
     # ------------------------------------------------------------------
     # Array overrides for the steady-state loop: when set, the per-server
@@ -501,7 +583,8 @@ class FastSweep:
     # ------------------------------------------------------------------
     # What-if load planning
     # ------------------------------------------------------------------
-    def plan(self, scales=None, arrival=None, return_cells: bool = False) -> PlanResult:
+    def plan(self, scales=None, arrival=None, return_cells: bool = False, capacity=None,
+             saturation_policy: str = "None", delayed_best_effort: bool = False) -> PlanResult:
         """Solve S arrival-rate scenarios of the fleet in one pass.
 
         Exactly one of ``scales`` (S non-negative factors applied to the base
@@ -516,8 +599,24 @@ class FastSweep:
         with reconcile(), so planning's hits and misses — one per loaded cell
         and call, not per scenario — show up in memo_stats(). Planning does
         not change what a following reconcile() returns.
+
+        ``capacity`` makes it a limited-mode plan: scenario s is solved by the
+        delta-regret greedy (solver/greedy.py) against an inventory of
+        accelerator units, with ``saturation_policy`` (a SaturationPolicy
+        name) and ``delayed_best_effort`` as in OptimizerSpec. A mapping of
+        accelerator type to units applies to every scenario (missing types
+        count as 0); an integer array [S, n_types] with columns in
+        ``capacity_types`` order sets it per scenario. The winners are then
+        the granted allocations (acc_idx -1 where a server got nothing or has
+        zero load) and the result's limited-mode fields are filled in. On the
+        GPU the scenarios are solved by the native host greedy over the
+        downloaded cells; INFERNO_PLAN_GREEDY=device runs one greedy per
+        scenario on the device instead (wva_plan_greedy), with the same result.
         """
         scen = self._plan_scenarios(scales, arrival)
+        if capacity is not None:
+            return self._plan_limited(scen, capacity, saturation_policy, delayed_best_effort,
+                                      return_cells)
         if self.backend == "gpu":
             winners, totals, cells = self._plan_gpu(scen, return_cells)
         else:
@@ -628,22 +727,332 @@ class FastSweep:
             cost=of[:, 0].copy(), value=of[:, 1].copy(), itl=of[:, 2].copy(),
             ttft=of[:, 3].copy(), rho=of[:, 4].copy(), max_rate=of[:, 5].copy(),
         )
-        cells = None
-        if return_cells:
-            keys = ("feasible", "zero_empty", "num_replicas", "batch", "cost", "value",
-                    "itl", "ttft", "rho", "max_rate")
-            dtypes = (np.uint8, np.uint8, np.int32, np.int32) + (np.float32,) * 6
-            cells = {k: np.empty((n_scen, self.n_cells), dtype=d) for k, d in zip(keys, dtypes)}
-            dst = (ctypes.c_void_p * len(keys))(
-                *[cells[k].ctypes.data_as(ctypes.c_void_p) for k in keys]
-            )
-            rc = st["ctx_lib"].wva_ctx_plan_cells(st["ctx"], dst)
-            if rc != 0:
-                raise HipKernelError(f"wva_ctx_plan_cells failed: {rc}")
-            cells["cell_server"] = self.cell_server
-            cells["cell_acc_idx"] = self.cell_acc_idx
-            cells["seg_start"] = self.seg_start
+        cells = self._plan_cells_gpu(n_scen) if return_cells else None
         return winners, totals, cells
+
+    def _plan_cells_gpu(self, n_scen: int) -> dict:
+        """Per-cell outputs of the planning pass that just ran."""
+        import ctypes
+
+        from ..ops.sweep import HipKernelError
+
+        st = self._gpu
+        keys = ("feasible", "zero_empty", "num_replicas", "batch", "cost", "value",
+                "itl", "ttft", "rho", "max_rate")
+        dtypes = (np.uint8, np.uint8, np.int32, np.int32) + (np.float32,) * 6
+        cells = {k: np.empty((n_scen, self.n_cells), dtype=d) for k, d in zip(keys, dtypes)}
+        dst = (ctypes.c_void_p * len(keys))(
+            *[cells[k].ctypes.data_as(ctypes.c_void_p) for k in keys]
+        )
+        rc = st["ctx_lib"].wva_ctx_plan_cells(st["ctx"], dst)
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_plan_cells failed: {rc}")
+        cells["cell_server"] = self.cell_server
+        cells["cell_acc_idx"] = self.cell_acc_idx
+        cells["seg_start"] = self.seg_start
+        return cells
+
+    # ------------------------------------------------------------------
+    # Capacity-limited planning
+    # ------------------------------------------------------------------
+    def _plan_capacity(self, capacity, n_scen: int) -> np.ndarray:
+        """Validate plan()'s capacity and return it as int32 [S, n_types]."""
+        types = self.capacity_types
+        n_types = len(types)
+        if hasattr(capacity, "keys"):
+            unknown = sorted(set(capacity) - set(types))
+            if unknown:
+                raise ValueError(f"capacity names unknown accelerator types: {unknown}")
+            try:
+                row = np.array([capacity.get(t, 0) for t in types], dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"capacity is not numeric: {e}") from None
+            vals = np.repeat(row[None, :], n_scen, axis=0)
+        else:
+            try:
+                vals = np.asarray(capacity, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"capacity is not numeric: {e}") from None
+            if vals.shape != (n_scen, n_types):
+                raise ValueError(
+                    f"capacity must be a mapping or have shape [{n_scen}, {n_types}] "
+                    f"(columns {types}), got {vals.shape}"
+                )
+        if not np.isfinite(vals).all():
+            raise ValueError("capacity must be finite")
+        if (vals < 0).any() or (vals != np.floor(vals)).any():
+            raise ValueError("capacity must hold non-negative integers")
+        if (vals > np.iinfo(np.int32).max).any():
+            raise ValueError("capacity must fit int32")
+        return np.ascontiguousarray(vals, dtype=np.int32)
+
+    def _plan_limited(self, scen, capacity, saturation_policy, delayed, return_cells):
+        import os
+
+        from ..config import SaturationPolicy
+
+        n_scen, n_srv = scen.shape
+        cap = self._plan_capacity(capacity, n_scen)
+        policy = _POLICY_CODE[SaturationPolicy.parse(saturation_policy).value]
+        delayed = bool(delayed)
+        n_acc = len(self.acc_names)
+        cells = None
+        if self.n_cells == 0 or n_acc == 0:
+            w = _empty_winner(n_srv)
+            winners = WinnerRecord(**{
+                f: np.repeat(getattr(w, f)[None, :], n_scen, axis=0) for f in _WINNER_FIELDS
+            })
+            zeros = np.zeros((n_scen, n_srv), dtype=np.int32)
+            sol = (winners, None, zeros, zeros.copy(), cap.astype(np.int64))
+        elif self.backend == "gpu":
+            mode = os.environ.get("INFERNO_PLAN_GREEDY", "") or PLAN_GREEDY_DEFAULT
+            if mode not in ("host", "device"):
+                raise ValueError(f"INFERNO_PLAN_GREEDY must be host or device, got {mode!r}")
+            if (policy in (2, 3) and cap.size
+                    and int(cap.astype(np.int64).sum(axis=1).max()) > PLAN_GREEDY_RR_MAX_UNITS):
+                mode = "host"
+            if mode == "device":
+                sol = self._plan_limited_device(scen, cap, policy, delayed)
+                if return_cells:
+                    cells = self._plan_cells_gpu(n_scen)
+            else:
+                sol, cells = self._plan_limited_host(scen, cap, policy, delayed)
+                if not return_cells:
+                    cells = None
+        else:
+            sol = self._plan_limited_cpu(scen, cap, saturation_policy, delayed)
+        winners, totals, desired, n_cand, cap_left = sol
+        has = winners.acc_idx != -1
+        if totals is None:
+            totals = np.zeros((n_scen, n_acc), dtype=np.int64)
+            for s in range(n_scen):
+                on = winners.acc_idx[s] >= 0
+                np.add.at(totals[s], winners.acc_idx[s][on],
+                          winners.num_replicas[s][on].astype(np.int64))
+        cost_total = np.array(
+            [winners.cost[s][has[s]].astype(np.float64).sum() for s in range(n_scen)],
+            dtype=np.float64,
+        )
+        granted = winners.num_replicas
+        return PlanResult(
+            winners=winners,
+            replicas_by_acc=totals,
+            cost_total=cost_total,
+            infeasible_servers=(~has).sum(axis=1).astype(np.int64),
+            arrival=scen,
+            cells=cells,
+            desired_replicas=desired,
+            unallocated_servers=((n_cand > 0) & ~has).sum(axis=1).astype(np.int64),
+            partial_servers=((granted > 0) & (granted < desired)).sum(axis=1).astype(np.int64),
+            capacity_left=cap_left.astype(np.int64),
+            capacity_types=self.capacity_types,
+        )
+
+    def _sync_greedy_static(self) -> None:
+        """Upload the static greedy inputs into the native context (only when
+        they changed)."""
+        import ctypes
+
+        from ..ops.sweep import HipKernelError
+
+        st = self._gpu
+        _, cell_tidx, units, prio = self.greedy_static()
+        arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in (cell_tidx, units, prio)]
+        key = b"".join(a.tobytes() for a in arrs)
+        if st.get("greedy_static_key") == key:
+            return
+        rc = st["ctx_lib"].wva_ctx_set_greedy_static(
+            st["ctx"], *[a.ctypes.data_as(ctypes.c_void_p) for a in arrs]
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_set_greedy_static failed: {rc}")
+        st["greedy_static_key"] = key
+
+    def _plan_limited_device(self, scen, cap, policy: int, delayed: bool):
+        import ctypes
+
+        from ..ops.sweep import HipKernelError
+
+        n_scen, n_srv = scen.shape
+        n_acc = len(self.acc_names)
+        n_types = cap.shape[1]
+        if not hasattr(self, "_gpu"):
+            self._init_gpu_state()
+        st = self._gpu
+        arrs = self._refresh_dynamic(plan_arrival=scen)
+        self._ensure_ctx()
+        self._fill_pinned(arrs)
+        self._sync_buckets(arrs["batch_n"])
+        self._sync_greedy_static()
+        cell_scen = np.ascontiguousarray(scen[:, self.cell_server], dtype=np.float32)
+        p_f, p_i, p_t = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        p_x, p_c = ctypes.c_void_p(), ctypes.c_void_p()
+        rc = st["ctx_lib"].wva_ctx_plan_limited(
+            st["ctx"], ctypes.c_int(n_scen), ctypes.c_int(n_acc),
+            cell_scen.ctypes.data_as(ctypes.c_void_p),
+            ctypes.c_int(n_types), cap.ctypes.data_as(ctypes.c_void_p),
+            ctypes.c_int(1 if delayed else 0), ctypes.c_int(policy),
+            ctypes.byref(p_f), ctypes.byref(p_i), ctypes.byref(p_t),
+            ctypes.byref(p_x), ctypes.byref(p_c),
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_plan_limited failed: {rc}")
+
+        def view(ptr, ctype, shape):
+            n = int(np.prod(shape))
+            buf = (ctype * n).from_address(ptr.value)
+            return np.ctypeslib.as_array(buf).reshape(shape).copy()
+
+        of = view(p_f, ctypes.c_float, (n_scen, 6, n_srv))
+        oi = view(p_i, ctypes.c_int32, (n_scen, 4, n_srv))
+        ox = view(p_x, ctypes.c_int32, (n_scen, 2, n_srv))
+        totals = view(p_t, ctypes.c_uint64, (n_scen, n_acc)).astype(np.int64)
+        cap_left = view(p_c, ctypes.c_int32, (n_scen, n_types)).astype(np.int64)
+        winners = WinnerRecord(
+            acc_idx=oi[:, 0].copy(), num_replicas=oi[:, 1].copy(), batch=oi[:, 2].copy(),
+            cost=of[:, 0].copy(), value=of[:, 1].copy(), itl=of[:, 2].copy(),
+            ttft=of[:, 3].copy(), rho=of[:, 4].copy(), max_rate=of[:, 5].copy(),
+        )
+        self._plan_limited_cells = oi[:, 3].copy()  # winning cell index; tests read it
+        return winners, totals, ox[:, 0].copy(), ox[:, 1].copy(), cap_left
+
+    def _plan_limited_host(self, scen, cap, policy: int, delayed: bool):
+        """The host loop: one native greedy (ops/native/greedy.cpp) per
+        scenario over the downloaded per-cell outputs."""
+        from ..ops.sweep import run_greedy_native
+
+        n_scen, n_srv = scen.shape
+        _, _, cells = self._plan_gpu(scen, True)
+        _, cell_tidx, units, prio = self.greedy_static()
+        prio = np.ascontiguousarray(prio, dtype=np.int32)
+        win_cells = np.full((n_scen, n_srv), -1, dtype=np.int32)
+        granted = np.zeros((n_scen, n_srv), dtype=np.int32)
+        cap_left = cap.copy()
+        for s in range(n_scen):
+            order, seg, c_val, c_type, c_units, c_reps = greedy_candidates(
+                cells["feasible"][s], cells["zero_empty"][s], cells["value"][s],
+                cells["num_replicas"][s], self.cell_server, cell_tidx, units, n_srv,
+            )
+            win_cand, win_reps = run_greedy_native(
+                c_val, c_type, c_units, c_reps, seg, prio, cap_left[s], delayed, policy,
+                allow_build=False,
+            )
+            got = win_cand >= 0
+            win_cells[s, got] = order[win_cand[got]]
+            granted[s, got] = win_reps[got]
+        # winner records of all scenarios at once
+        has = win_cells >= 0
+        at = np.where(has, win_cells, 0)
+
+        def pick(key, empty):
+            return np.where(has, np.take_along_axis(cells[key], at, axis=1), empty)
+
+        desired = pick("num_replicas", 0).astype(np.int32)
+        cut = has & (desired > 0) & (granted != desired)
+        factor = np.ones((n_scen, n_srv), dtype=np.float64)
+        factor[cut] = granted[cut].astype(np.float64) / desired[cut].astype(np.float64)
+        rec = {}
+        for f in ("cost", "value"):
+            whole = pick(f, np.float32(0.0)).astype(np.float32)
+            scaled = (whole.astype(np.float64) * factor).astype(np.float32)
+            rec[f] = np.where(cut, scaled, whole)
+        for f in ("itl", "ttft", "rho", "max_rate"):
+            rec[f] = pick(f, np.float32(0.0)).astype(np.float32)
+        winners = WinnerRecord(
+            acc_idx=np.where(has, self.cell_acc_idx[at], -1).astype(np.int32),
+            num_replicas=granted, batch=pick("batch", 0).astype(np.int32), **rec,
+        )
+        real = cells["feasible"].astype(bool) & ~cells["zero_empty"].astype(bool)
+        run = np.concatenate(
+            [np.zeros((n_scen, 1), dtype=np.int32), np.cumsum(real, axis=1, dtype=np.int32)],
+            axis=1)
+        n_cand = run[:, self.seg_start[1:]] - run[:, self.seg_start[:-1]]
+        self._plan_limited_cells = win_cells
+        return (winners, None, desired, n_cand, cap_left.astype(np.int64)), cells
+
+    def _plan_limited_cpu(self, scen, cap, saturation_policy, delayed: bool):
+        """Golden path: per scenario the CPU sweep with the scenario's loads,
+        then solver.greedy.solve_greedy with the scenario's capacity. Loads,
+        allocations, candidate lists and system.capacity are restored
+        afterwards in any case."""
+        from ..config import SaturationPolicy
+        from ..solver.greedy import solve_greedy
+        from .engine import SweepEngine
+
+        system = self.system
+        n_scen, n_srv = scen.shape
+        types = self.capacity_types
+        _, in_tok, out_tok = self._base_load()
+        policy = SaturationPolicy.parse(saturation_policy)
+        members = set(self.server_names)
+        saved_load = [
+            None if srv.load is None
+            else (srv.load.arrivalRate, srv.load.avgInTokens, srv.load.avgOutTokens)
+            for srv in self._srv_objs
+        ]
+        saved_alloc = {
+            name: (srv.allocation, srv.all_allocations, srv.spec.desiredAlloc)
+            for name, srv in system.servers.items()
+        }
+        saved_capacity = system.capacity
+        winners = WinnerRecord(**{
+            f: np.repeat(getattr(_empty_winner(n_srv), f)[None, :], n_scen, axis=0)
+            for f in _WINNER_FIELDS
+        })
+        desired = np.zeros((n_scen, n_srv), dtype=np.int32)
+        n_cand = np.zeros((n_scen, n_srv), dtype=np.int32)
+        cap_left = cap.astype(np.int64)
+        engine = SweepEngine(backend="cpu")
+        try:
+            for s in range(n_scen):
+                for i, srv in enumerate(self._srv_objs):
+                    if srv.load is None:
+                        continue  # no load: zero-traffic whatever the scenario says
+                    srv.load.arrivalRate = float(scen[s, i])
+                    if self.load_override is not None:
+                        srv.load.avgInTokens = int(in_tok[i])
+                        srv.load.avgOutTokens = int(out_tok[i])
+                for name, srv in system.servers.items():
+                    if name not in members:
+                        srv.all_allocations = {}  # only this sweep's servers compete
+                engine.sweep(system, server_names=self.server_names)
+                want = {}
+                for i, srv in enumerate(self._srv_objs):
+                    for alloc in srv.all_allocations.values():
+                        want[id(alloc)] = alloc.num_replicas
+                        if alloc.accelerator != "":
+                            n_cand[s, i] += 1
+                system.capacity = {t: int(cap[s, j]) for j, t in enumerate(types)}
+                solve_greedy(system, delayed_best_effort=delayed, saturation_policy=policy)
+                for i, srv in enumerate(self._srv_objs):
+                    alloc = srv.allocation
+                    if alloc is None or alloc.accelerator == "":
+                        continue
+                    acc = system.accelerators[alloc.accelerator]
+                    model = system.models[srv.model_name]
+                    per = model.get_num_instances(acc.name) * acc.multiplicity
+                    cap_left[s, types.index(acc.type)] -= alloc.num_replicas * per
+                    desired[s, i] = want.get(id(alloc), alloc.num_replicas)
+                    winners.acc_idx[s, i] = self._acc_index[alloc.accelerator]
+                    winners.num_replicas[s, i] = alloc.num_replicas
+                    winners.batch[s, i] = alloc.batch_size
+                    winners.cost[s, i] = alloc.cost
+                    winners.value[s, i] = alloc.value
+                    winners.itl[s, i] = alloc.itl
+                    winners.ttft[s, i] = alloc.ttft
+                    winners.rho[s, i] = alloc.rho
+                    winners.max_rate[s, i] = alloc.max_arrv_rate_per_replica
+        finally:
+            for srv, old in zip(self._srv_objs, saved_load):
+                if old is not None:
+                    (srv.load.arrivalRate, srv.load.avgInTokens,
+                     srv.load.avgOutTokens) = old
+            for name, (alloc, all_allocs, want_alloc) in saved_alloc.items():
+                system.servers[name].allocation = alloc
+                system.servers[name].all_allocations = all_allocs
+                system.servers[name].spec.desiredAlloc = want_alloc
+            system.capacity = saved_capacity
+        return winners, None, desired, n_cand, cap_left
 
     def _plan_cpu(self, scen: np.ndarray) -> WinnerRecord:
         """Golden path: one _reconcile_cpu per scenario with the scenario's

@@ -1373,6 +1373,435 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_reduce(
 }
 
 // ---------------------------------------------------------------------------
+// K5 wva_plan_greedy: the capacity-limited ("limited mode") solution of every
+// scenario of a planning sweep, one wave per scenario. The reference for every
+// detail is ops/native/greedy.cpp; docs/design/kernels.md ("Capacity-limited
+// planning") explains the formulation. In short: every server has at most one
+// live entry, the host's sorted list is the total order (priority asc, delta
+// desc, value desc, stamp asc), "pop front" is a wave-wide argmin over the
+// live servers, and leftmost re-insertion among equal keys is a stamp of minus
+// the running pop counter (initial stamps are the server index, >= 0).
+// Server srv belongs to lane srv % 64: that lane sorts its candidates, keeps
+// the front entry among its servers in registers, and performs the pop when
+// the wave-wide reduction picks one of them. The best-effort policies run on
+// lane 0; the winner records are spread over the lanes.
+//
+// Per-scenario state. Hot (read or written by every pop): per server delta,
+// cnt, cur, stamp, live, priority, segment start, current value, granted cell
+// and replicas; per sorted candidate position its cell, type, value and
+// replicas * units. It lives in dynamic LDS when use_lds is set (the host
+// sets it when wva_greedy_lds_bytes() fits its budget) and otherwise in the
+// scenario's rows of the global workspace, in the same layout: wsd
+// [n_srv + n_cells] 8-byte words, wsi [15 * n_srv + 3 * n_cells] int32. Cold,
+// always in the tail of the wsi row: the fall-out list and the five ticket
+// fields. capacity [n_scen][n_types] is consumed in place (through an LDS
+// copy when n_types <= WVA_GREEDY_LDS_TYPES) and holds the capacity left on
+// exit.
+// px [n_scen][2][n_srv]: the granted cell's pre-cut replica count, and the
+// server's number of feasible candidates that are not zero-load.
+// ---------------------------------------------------------------------------
+#define WVA_GREEDY_LDS_TYPES 256
+#define WVA_GREEDY_MAXF32 3.4028234663852886e38
+
+struct WvaGreedyScen {
+  const float *val;          // scenario slice, [n_cells]
+  const uint8_t *zero_empty;
+  const int *reps;
+  const int *seg_start;
+  const int *cell_type;
+  const int *cell_units;
+  const int *order;
+  const int *cnt;
+  int *cap;
+  int *win_cell;
+  int *win_rep;
+};
+
+// (priority asc, delta desc, value desc, stamp asc); doubles compare as
+// doubles, so -0.0 == 0.0 as on the host
+__device__ __forceinline__ bool wva_greedy_before(int pa, double da, double va, int sa, int pb,
+                                                  double db, double vb, int sb) {
+  if (pa != pb) return pa < pb;
+  if (da != db) return da > db;
+  if (va != vb) return va > vb;
+  return sa < sb;
+}
+
+__device__ __forceinline__ int wva_greedy_type(const WvaGreedyScen &g, int cell) {
+  return g.zero_empty[cell] ? -1 : g.cell_type[cell];
+}
+
+// greedy.cpp allocate_maximally
+__device__ void wva_greedy_maximally(const WvaGreedyScen &g, const int *list, int n) {
+  for (int j = 0; j < n; ++j) {
+    const int srv = list[j];
+    const int beg = g.seg_start[srv];
+    const int len = g.cnt[srv];
+    for (int i = 0; i < len; ++i) {
+      const int cell = g.order[beg + i];
+      const int t = wva_greedy_type(g, cell);
+      if (t < 0) continue;
+      const int u = g.cell_units[cell];
+      if (u <= 0) continue;
+      int max_rep = g.cap[t] / u;
+      if (max_rep > g.reps[cell]) max_rep = g.reps[cell];
+      if (max_rep > 0) {
+        g.win_cell[srv] = cell;
+        g.win_rep[srv] = max_rep;
+        g.cap[t] -= max_rep * u;
+        break;
+      }
+    }
+  }
+}
+
+// greedy.cpp allocate_equally. Ticket state: 0 dead, 1 live, 2 live and
+// active. Every step on a live ticket either takes at least one capacity unit
+// or kills the ticket, so the live steps are bounded by the capacity units
+// left plus twice the list length; max_pass bounds the passes the same way.
+__device__ void wva_greedy_equally(const WvaGreedyScen &g, const int *list, int n, int *tk_state,
+                                   int *tk_type, int *tk_units, int *tk_granted, int *tk_cand,
+                                   int n_types) {
+  long long max_pass = (long long)n + 1;
+  for (int t = 0; t < n_types; ++t) max_pass += (long long)g.cap[t];
+  for (int j = 0; j < n; ++j) {
+    tk_state[j] = 1;
+    tk_granted[j] = 0;
+    tk_cand[j] = -1;
+  }
+  int live = n;
+  for (long long pass = 0; live > 0 && pass < max_pass; ++pass) {
+    for (int j = 0; j < n; ++j) {
+      int st = tk_state[j];
+      if (st == 0) continue;
+      if (st == 1) {
+        const int srv = list[j];
+        const int beg = g.seg_start[srv];
+        const int len = g.cnt[srv];
+        for (int i = 0; i < len; ++i) {
+          const int cell = g.order[beg + i];
+          const int t = wva_greedy_type(g, cell);
+          if (t < 0) continue;
+          const int u = g.cell_units[cell];
+          if (u > 0 && g.cap[t] >= u) {
+            st = 2;
+            tk_state[j] = 2;
+            tk_type[j] = t;
+            tk_units[j] = u;
+            tk_cand[j] = cell;
+            break;
+          }
+        }
+        if (st != 2) {
+          tk_state[j] = 0;
+          --live;
+          continue;
+        }
+      }
+      const int t = tk_type[j], u = tk_units[j];
+      const int avail_rep = g.cap[t] / u;
+      const int want = g.reps[tk_cand[j]];
+      if ((avail_rep < want ? avail_rep : want) > 0) {
+        tk_granted[j] += 1;
+        g.cap[t] -= u;
+      } else {
+        tk_state[j] = 0;
+        --live;
+      }
+    }
+  }
+  for (int j = 0; j < n; ++j) {
+    if (tk_granted[j] > 0) {
+      g.win_cell[list[j]] = tk_cand[j];
+      g.win_rep[list[j]] = tk_granted[j];
+    }
+  }
+}
+
+// greedy.cpp best_effort; policy: 0 None, 1 PriorityExhaustive,
+// 2 PriorityRoundRobin, 3 RoundRobin
+__device__ void wva_greedy_best_effort(const WvaGreedyScen &g, const int *list, int n, int policy,
+                                       const int *srv_prio, int *tk_state, int *tk_type,
+                                       int *tk_units, int *tk_granted, int *tk_cand, int n_types) {
+  if (policy == 1) {
+    wva_greedy_maximally(g, list, n);
+  } else if (policy == 2) {
+    int i = 0;
+    while (i < n) {
+      int j = i + 1;
+      const int prio = srv_prio[list[i]];
+      while (j < n && srv_prio[list[j]] == prio) ++j;
+      wva_greedy_equally(g, list + i, j - i, tk_state, tk_type, tk_units, tk_granted, tk_cand,
+                         n_types);
+      i = j;
+    }
+  } else if (policy == 3) {
+    wva_greedy_equally(g, list, n, tk_state, tk_type, tk_units, tk_granted, tk_cand, n_types);
+  }
+}
+
+// bytes of dynamic LDS the per-scenario state takes (0 = keep it in the
+// global workspace): 8-byte arrays first, then the 4-byte ones
+static size_t wva_greedy_lds_bytes(int n_srv, int n_cells) {
+  return ((size_t)n_srv + (size_t)n_cells) * 8 + ((size_t)9 * n_srv + (size_t)3 * n_cells) * 4;
+}
+
+// LDS = true: the hot state is the dynamic LDS block (the pointers below are
+// then LDS pointers at compile time); false: the global workspace rows
+template <bool LDS>
+__device__ __forceinline__ void wva_plan_greedy_body(
+    const float *value, const uint8_t *feasible, const uint8_t *zero_empty, const int *cell_acc,
+    const int *num_replicas, const int *batch, const float *cost, const float *itl,
+    const float *ttft, const float *rho, const float *max_rate, const int *seg_start,
+    const int *cell_type, const int *cell_units, const int *srv_prio, int n_srv, int n_cells,
+    int n_acc, int n_types, int delayed, int policy, int *capacity, int *wsi, double *wsd,
+    float *pf, int *pi, int *px, unsigned long long *totals, int *s_cap) {
+  extern __shared__ double wva_greedy_lds[];
+  const int sc = blockIdx.x;
+  const int lane = threadIdx.x;
+  const size_t base = (size_t)sc * (size_t)n_cells;
+  const float *val = value + base;
+  const uint8_t *feas = feasible + base;
+  int *gcap = capacity + (size_t)sc * (size_t)n_types;
+  float *gf = pf + (size_t)sc * 6 * (size_t)n_srv;
+  int *gi = pi + (size_t)sc * 4 * (size_t)n_srv;
+  int *gx = px + (size_t)sc * 2 * (size_t)n_srv;
+  // Hot state: the same layout in dynamic LDS (use_lds) or in the scenario's
+  // rows of the global workspace; the code below does not care which.
+  double *hd;
+  if constexpr (LDS) hd = wva_greedy_lds;
+  else hd = wsd + (size_t)sc * ((size_t)n_srv + (size_t)n_cells);
+  double *delta = hd;                                // [n_srv]
+  long long *scount = (long long *)(delta + n_srv);  // [n_cells] replicas * units, sorted order
+  int *hi;
+  if constexpr (LDS) hi = (int *)(scount + n_cells);
+  else hi = wsi + (size_t)sc * ((size_t)15 * n_srv + (size_t)3 * n_cells);
+  int *order = hi;                      // [n_cells] cell of sorted candidate position
+  int *stype = order + n_cells;         // [n_cells] its type, -1 = zero-load
+  float *sval = (float *)(stype + n_cells);  // [n_cells] its value
+  int *cnt = (int *)(sval + n_cells);   // per server: candidates
+  int *cur = cnt + n_srv;               //   current candidate
+  int *stamp = cur + n_srv;             //   tie-break stamp
+  int *live = stamp + n_srv;            //   entry still in the list
+  int *sprio = live + n_srv;            //   priority
+  int *sbeg = sprio + n_srv;            //   segment start
+  float *curval = (float *)(sbeg + n_srv);  // current candidate's value
+  int *win_cell = (int *)(curval + n_srv);  // granted cell, -1 = none
+  int *win_rep = win_cell + n_srv;      //   granted replicas, -1 = the cell's own count
+  // cold state, always global: fall-out list and tickets
+  int *fall = wsi + (size_t)sc * ((size_t)15 * n_srv + (size_t)3 * n_cells) +
+              (size_t)9 * n_srv + (size_t)3 * n_cells;
+  int *tk_state = fall + n_srv;
+  int *tk_type = tk_state + n_srv;
+  int *tk_units = tk_type + n_srv;
+  int *tk_granted = tk_units + n_srv;
+  int *tk_cand = tk_granted + n_srv;
+  // capacity counters: LDS when they fit, else the scenario's global row
+  const bool cap_lds = n_types <= WVA_GREEDY_LDS_TYPES;
+  int *cap = cap_lds ? s_cap : gcap;
+  if (cap_lds)
+    for (int t = lane; t < n_types; t += WVA_WAVE) s_cap[t] = gcap[t];
+
+  WvaGreedyScen g;
+  g.val = val;
+  g.zero_empty = zero_empty + base;
+  g.reps = num_replicas + base;
+  g.seg_start = seg_start;
+  g.cell_type = cell_type;
+  g.cell_units = cell_units;
+  g.order = order;
+  g.cnt = cnt;
+  g.cap = cap;
+  g.win_cell = win_cell;
+  g.win_rep = win_rep;
+
+  // 1. per-server candidates: feasible cells by (double)value ascending, ties
+  // in cell order (stable insertion sort; segments are short)
+  int bound = 0;
+  for (int srv = lane; srv < n_srv; srv += WVA_WAVE) {
+    const int beg = seg_start[srv], end = seg_start[srv + 1];
+    int n = 0, nz = 0;
+    for (int i = beg; i < end; ++i) {
+      if (!feas[i]) continue;
+      const float v = val[i];
+      int k = n;
+      while (k > 0 && (double)sval[beg + k - 1] > (double)v) {
+        order[beg + k] = order[beg + k - 1];
+        sval[beg + k] = sval[beg + k - 1];
+        --k;
+      }
+      order[beg + k] = i;
+      sval[beg + k] = v;
+      ++n;
+      if (!g.zero_empty[i]) ++nz;
+    }
+    for (int k = 0; k < n; ++k) {
+      const int cell = order[beg + k];
+      stype[beg + k] = wva_greedy_type(g, cell);
+      scount[beg + k] = (long long)g.reps[cell] * (long long)cell_units[cell];
+    }
+    cnt[srv] = n;
+    cur[srv] = 0;
+    stamp[srv] = srv;
+    live[srv] = n > 0 ? 1 : 0;
+    sprio[srv] = srv_prio[srv];
+    sbeg[srv] = beg;
+    curval[srv] = n > 0 ? sval[beg] : 0.0f;
+    delta[srv] = n > 1 ? (double)sval[beg + 1] - (double)sval[beg] : WVA_GREEDY_MAXF32;
+    win_cell[srv] = -1;
+    win_rep[srv] = 0;
+    gx[n_srv + srv] = nz;
+    bound += n + (n > 0 ? 1 : 0);
+  }
+#pragma unroll
+  for (int off = WVA_WAVE / 2; off > 0; off >>= 1) bound += __shfl_xor(bound, off, WVA_WAVE);
+  __syncthreads();
+
+  // 2. pop loop: at most one pop per feasible candidate, bounded by the
+  // candidate count plus the entry count whatever the data. Server srv is
+  // owned by lane srv % 64: only that lane changes its entry, and it keeps
+  // the front entry among the servers it owns in registers, so a pop costs
+  // one wave-wide reduction plus a rescan of the owner's servers.
+  int lb = -1, lbp = 0, lbs = 0;
+  double lbd = 0.0, lbv = 0.0;
+  auto rescan = [&]() {
+    lb = -1;
+#pragma unroll 4
+    for (int srv = lane; srv < n_srv; srv += WVA_WAVE) {
+      const int lv = live[srv], p = sprio[srv], s = stamp[srv];
+      const double d = delta[srv], v = (double)curval[srv];
+      if (lv && (lb < 0 || wva_greedy_before(p, d, v, s, lbp, lbd, lbv, lbs))) {
+        lb = srv; lbp = p; lbd = d; lbv = v; lbs = s;
+      }
+    }
+  };
+  rescan();
+  int n_fall = 0, pops = 0, group_prio = 0;
+  bool have_group = false;
+  for (int it = 0; it < bound; ++it) {
+    int b = lb, bp = lbp, bs = lbs;
+    double bd = lbd, bv = lbv;
+#pragma unroll
+    for (int off = WVA_WAVE / 2; off > 0; off >>= 1) {
+      const int ob = __shfl_xor(b, off, WVA_WAVE);
+      const int op = __shfl_xor(bp, off, WVA_WAVE);
+      const int os = __shfl_xor(bs, off, WVA_WAVE);
+      const double od = __shfl_xor(bd, off, WVA_WAVE);
+      const double ov = __shfl_xor(bv, off, WVA_WAVE);
+      if (ob >= 0 && (b < 0 || wva_greedy_before(op, od, ov, os, bp, bd, bv, bs))) {
+        b = ob; bp = op; bd = od; bv = ov; bs = os;
+      }
+    }
+    if (b < 0) break;  // uniform: every lane holds the same front entry
+    if (!delayed && have_group && bp != group_prio) {
+      // the previous priority group is done: its fall-out list goes through
+      // best-effort before the first pop of this group
+      if (lane == 0)
+        wva_greedy_best_effort(g, fall, n_fall, policy, srv_prio, tk_state, tk_type, tk_units,
+                               tk_granted, tk_cand, n_types);
+      n_fall = 0;
+      __syncthreads();
+    }
+    group_prio = bp;
+    have_group = true;
+    ++pops;
+    const int owner = b & (WVA_WAVE - 1);
+    int fell = 0;
+    if (lane == owner) {
+      const int len = cnt[b];
+      int c = cur[b];
+      const int pos = sbeg[b] + c;
+      const int t = stype[pos];
+      if (t < 0) {
+        live[b] = 0;  // zero-load empty candidate: the entry is dropped
+      } else {
+        const long long count = scount[pos];
+        if ((long long)cap[t] >= count) {
+          cap[t] -= (int)count;
+          win_cell[b] = order[pos];
+          win_rep[b] = -1;
+          live[b] = 0;
+        } else {
+          c += 1;
+          if (c == len) {
+            live[b] = 0;
+            fall[n_fall] = b;
+            fell = 1;
+          } else {
+            const float nv = sval[pos + 1];
+            cur[b] = c;
+            curval[b] = nv;
+            delta[b] = c + 1 < len ? (double)sval[pos + 2] - (double)nv : WVA_GREEDY_MAXF32;
+            stamp[b] = -pops;
+          }
+        }
+      }
+      rescan();
+    }
+    n_fall += __shfl(fell, owner, WVA_WAVE);
+    __syncthreads();  // the capacity counters and the fall-out list change hands
+  }
+  if (lane == 0 && n_fall > 0)
+    wva_greedy_best_effort(g, fall, n_fall, policy, srv_prio, tk_state, tk_type, tk_units,
+                           tk_granted, tk_cand, n_types);
+  __syncthreads();
+
+  // 3. winner records (wva_plan_reduce's layout; cost and value scaled by
+  // granted/desired in fp64 and rounded once), replica totals, capacity left
+  for (int srv = lane; srv < n_srv; srv += WVA_WAVE) {
+    const int w = win_cell[srv];
+    const bool has = w >= 0;
+    const size_t wc = base + (size_t)(has ? w : 0);
+    const int desired = has ? num_replicas[wc] : 0;
+    const int granted = has ? (win_rep[srv] < 0 ? desired : win_rep[srv]) : 0;
+    float c = has ? cost[wc] : 0.0f;
+    float v = has ? value[wc] : 0.0f;
+    if (has && desired > 0 && granted != desired) {
+      const double f = (double)granted / (double)desired;
+      c = (float)((double)c * f);
+      v = (float)((double)v * f);
+    }
+    const int acc = has ? cell_acc[w] : -1;
+    gf[0 * n_srv + srv] = c;
+    gf[1 * n_srv + srv] = v;
+    gf[2 * n_srv + srv] = has ? itl[wc] : 0.0f;
+    gf[3 * n_srv + srv] = has ? ttft[wc] : 0.0f;
+    gf[4 * n_srv + srv] = has ? rho[wc] : 0.0f;
+    gf[5 * n_srv + srv] = has ? max_rate[wc] : 0.0f;
+    gi[0 * n_srv + srv] = acc;
+    gi[1 * n_srv + srv] = granted;
+    gi[2 * n_srv + srv] = has ? batch[wc] : 0;
+    gi[3 * n_srv + srv] = w;
+    gx[srv] = desired;
+    if (acc >= 0 && acc < n_acc && granted > 0)
+      atomicAdd(totals + (size_t)sc * (size_t)n_acc + (size_t)acc, (unsigned long long)granted);
+  }
+  if (cap_lds)
+    for (int t = lane; t < n_types; t += WVA_WAVE) gcap[t] = s_cap[t];
+}
+
+extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_greedy(
+    const float *value, const uint8_t *feasible, const uint8_t *zero_empty, const int *cell_acc,
+    const int *num_replicas, const int *batch, const float *cost, const float *itl,
+    const float *ttft, const float *rho, const float *max_rate, const int *seg_start,
+    const int *cell_type, const int *cell_units, const int *srv_prio, int n_srv, int n_cells,
+    int n_scen, int n_acc, int n_types, int delayed, int policy, int use_lds, int *capacity,
+    int *wsi, double *wsd, float *pf, int *pi, int *px, unsigned long long *totals) {
+  __shared__ int s_cap[WVA_GREEDY_LDS_TYPES];
+  if ((int)blockIdx.x >= n_scen) return;  // whole block
+  if (use_lds)
+    wva_plan_greedy_body<true>(value, feasible, zero_empty, cell_acc, num_replicas, batch, cost,
+                               itl, ttft, rho, max_rate, seg_start, cell_type, cell_units,
+                               srv_prio, n_srv, n_cells, n_acc, n_types, delayed, policy,
+                               capacity, wsi, wsd, pf, pi, px, totals, s_cap);
+  else
+    wva_plan_greedy_body<false>(value, feasible, zero_empty, cell_acc, num_replicas, batch, cost,
+                                itl, ttft, rho, max_rate, seg_start, cell_type, cell_units,
+                                srv_prio, n_srv, n_cells, n_acc, n_types, delayed, policy,
+                                capacity, wsi, wsd, pf, pi, px, totals, s_cap);
+}
+
+// ---------------------------------------------------------------------------
 // Native reconcile context: the whole per-tick device pipeline behind ONE C
 // call (H2D copies, regime-bucketed sweep launches overlapped via events on
 // three streams, argmin, gather, D2H, sync) — no per-step host dispatch
@@ -1443,6 +1872,24 @@ struct WvaCtx {
   float *plan_pin_pf;
   int *plan_pin_pi;
   unsigned long long *plan_pin_tot;
+  // capacity-limited planning (wva_ctx_plan_limited): the static greedy
+  // inputs (wva_ctx_set_greedy_static) and the per-scenario workspace, both
+  // allocated on first use and freed in destroy
+  void *lim_static;     // device: cell_type, cell_units [n_cells], srv_prio [n_srv]
+  const int *lim_cell_type;
+  const int *lim_cell_units;
+  const int *lim_srv_prio;
+  int lim_cap;          // scenarios the workspace holds (0 = not allocated)
+  int lim_types_cap;    // accelerator types per capacity row it holds
+  void *lim_dev;        // one device allocation, carved up below
+  void *lim_pin;        // one pinned host allocation, carved up below
+  size_t lim_lds_budget;  // dynamic LDS the greedy may take (INFERNO_PLAN_GREEDY_LDS)
+  double *lim_wsd;      // device [S][n_srv + n_cells] 8-byte words
+  int *lim_wsi;         // device [S][15 * n_srv + 3 * n_cells]
+  int *lim_capacity;    // device [S][n_types]
+  int *lim_px;          // device [S][2][n_srv]
+  int *lim_pin_capacity;  // pinned mirrors of lim_capacity / lim_px
+  int *lim_pin_px;
 };
 
 // pointer-slot order for wva_ctx_create (host mirrors in ops/sweep.py):
@@ -1471,6 +1918,21 @@ extern "C" void *wva_ctx_create(int n_cells, int n_srv, void **p) {
   c->plan_s = 0;
   c->plan_dev = nullptr;
   c->plan_pin = nullptr;
+  c->lim_static = nullptr;
+  c->lim_cap = 0;
+  c->lim_types_cap = 0;
+  c->lim_dev = nullptr;
+  c->lim_pin = nullptr;
+  // Dynamic LDS wva_plan_greedy may take for its hot state, in bytes; fleets
+  // that need more keep it in the global workspace (same code, same result).
+  // INFERNO_PLAN_GREEDY_LDS overrides it (0 = always global), read here once.
+  c->lim_lds_budget = 120 * 1024;
+  if (const char *lds_env = getenv("INFERNO_PLAN_GREEDY_LDS")) {
+    char *end = nullptr;
+    const long v = strtol(lds_env, &end, 10);
+    if (end != lds_env && *end == '\0' && v >= 0 && v <= 120 * 1024)
+      c->lim_lds_budget = (size_t)v;
+  }
   char *di = (char *)p[0];
   char *df = (char *)p[1];
   size_t ci = (size_t)n_cells * sizeof(int);
@@ -1788,16 +2250,129 @@ static int wva_plan_reserve(WvaCtx *c, int n_scen, int n_acc) {
 // wva_ctx_plan or wva_ctx_destroy: pf [n_scen][6][n_srv] fp32 (cost, value,
 // itl, ttft, rho, max_rate), pi [n_scen][4][n_srv] i32 (acc code, replicas,
 // batch, winner cell), totals [n_scen][n_acc] u64.
-extern "C" int wva_ctx_plan(void *ctx, int n_scen, int n_acc, const float *scen_arrival,
-                            const void **out_pf, const void **out_pi,
-                            const void **out_totals) {
+//
+// lim == nullptr is the unlimited plan (wva_ctx_plan). With lim, step 3 is
+// wva_plan_greedy instead of wva_plan_reduce and the capacity rows go up and
+// come back (wva_ctx_plan_limited); everything else is the same pass.
+struct WvaLimArgs {
+  int n_types;
+  const int *capacity;  // host [n_scen][n_types]
+  int delayed;
+  int policy;
+};
+
+static void wva_lim_release(WvaCtx *c) {
+  if (c->lim_dev != nullptr) (void)hipFree(c->lim_dev);
+  if (c->lim_pin != nullptr) (void)hipHostFree(c->lim_pin);
+  c->lim_dev = nullptr;
+  c->lim_pin = nullptr;
+  c->lim_cap = 0;
+  c->lim_types_cap = 0;
+}
+
+// (re)allocate the greedy workspace for n_scen scenarios and n_types
+// accelerator types; on failure nothing is held and reconciles and unlimited
+// plans keep working
+static int wva_lim_reserve(WvaCtx *c, int n_scen, int n_types) {
+  if (n_scen <= c->lim_cap && n_types <= c->lim_types_cap) return 0;
+  const int cap = n_scen > c->lim_cap ? n_scen : c->lim_cap;
+  const int tcap = n_types > c->lim_types_cap ? n_types : c->lim_types_cap;
+  wva_lim_release(c);
+  const size_t b_wsd =
+      wva_align256((size_t)cap * ((size_t)c->n_srv + (size_t)c->n_cells) * sizeof(double));
+  const size_t b_wsi = wva_align256((size_t)cap *
+                                    ((size_t)15 * c->n_srv + (size_t)3 * c->n_cells) * sizeof(int));
+  const size_t b_cap = wva_align256((size_t)cap * tcap * sizeof(int));
+  const size_t b_px = wva_align256((size_t)cap * 2 * c->n_srv * sizeof(int));
+  const size_t dev_bytes = b_wsd + b_wsi + b_cap + b_px;
+  const size_t pin_bytes = b_cap + b_px;
+
+  int prev_dev = -1, dev = -1;
+  hipPointerAttribute_t attr;
+  if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
+  if (hipPointerGetAttributes(&attr, c->dev_i) == hipSuccess) dev = attr.device;
+  const bool switched = dev >= 0 && prev_dev >= 0 && dev != prev_dev &&
+                        hipSetDevice(dev) == hipSuccess;
+  void *d = nullptr, *h = nullptr;
+  bool ok = hipMalloc(&d, dev_bytes) == hipSuccess && d != nullptr;
+  ok = ok && hipHostMalloc(&h, pin_bytes, hipHostMallocDefault) == hipSuccess && h != nullptr;
+  if (switched) (void)hipSetDevice(prev_dev);
+  if (!ok) {
+    if (d != nullptr) (void)hipFree(d);
+    if (h != nullptr) (void)hipHostFree(h);
+    (void)hipGetLastError();
+    return -34;
+  }
+  c->lim_dev = d;
+  c->lim_pin = h;
+  c->lim_cap = cap;
+  c->lim_types_cap = tcap;
+  char *q = (char *)d;
+  c->lim_wsd = (double *)q;       q += b_wsd;
+  c->lim_wsi = (int *)q;          q += b_wsi;
+  c->lim_capacity = (int *)q;     q += b_cap;
+  c->lim_px = (int *)q;
+  q = (char *)h;
+  c->lim_pin_capacity = (int *)q; q += b_cap;
+  c->lim_pin_px = (int *)q;
+  return 0;
+}
+
+// Static inputs of wva_plan_greedy: host cell_type, cell_units [n_cells] and
+// srv_prio [n_srv]. Synchronous upload; the caller repeats it only when one
+// of the arrays changed.
+extern "C" int wva_ctx_set_greedy_static(void *ctx, const int *cell_type, const int *cell_units,
+                                         const int *srv_prio) {
   WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || cell_type == nullptr || cell_units == nullptr || srv_prio == nullptr)
+    return -31;
+  if (c->n_cells <= 0 || c->n_srv <= 0) return -33;
+  const size_t b_c = wva_align256((size_t)c->n_cells * sizeof(int));
+  const size_t b_s = wva_align256((size_t)c->n_srv * sizeof(int));
+  if (c->lim_static == nullptr) {
+    int prev_dev = -1, dev = -1;
+    hipPointerAttribute_t attr;
+    if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
+    if (hipPointerGetAttributes(&attr, c->dev_i) == hipSuccess) dev = attr.device;
+    const bool switched = dev >= 0 && prev_dev >= 0 && dev != prev_dev &&
+                          hipSetDevice(dev) == hipSuccess;
+    void *d = nullptr;
+    const bool ok = hipMalloc(&d, 2 * b_c + b_s) == hipSuccess && d != nullptr;
+    if (switched) (void)hipSetDevice(prev_dev);
+    if (!ok) {
+      (void)hipGetLastError();
+      return -34;
+    }
+    c->lim_static = d;
+    c->lim_cell_type = (const int *)d;
+    c->lim_cell_units = (const int *)((char *)d + b_c);
+    c->lim_srv_prio = (const int *)((char *)d + 2 * b_c);
+  }
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -1;
+  char *d = (char *)c->lim_static;
+  if (hipMemcpy(d, cell_type, (size_t)c->n_cells * sizeof(int), hipMemcpyHostToDevice) !=
+          hipSuccess ||
+      hipMemcpy(d + b_c, cell_units, (size_t)c->n_cells * sizeof(int), hipMemcpyHostToDevice) !=
+          hipSuccess ||
+      hipMemcpy(d + 2 * b_c, srv_prio, (size_t)c->n_srv * sizeof(int), hipMemcpyHostToDevice) !=
+          hipSuccess)
+    return -2;
+  return 0;
+}
+
+static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arrival,
+                        const WvaLimArgs *lim, const void **out_pf, const void **out_pi,
+                        const void **out_totals) {
   if (c == nullptr || scen_arrival == nullptr) return -31;
   if (n_scen < 1 || n_scen > WVA_PLAN_MAX_S || n_acc < 1) return -32;
   if (c->n_cells <= 0 || c->n_srv <= 0) return -33;
   c->plan_s = 0;
   int rc = wva_plan_reserve(c, n_scen, n_acc);
   if (rc != 0) return rc;
+  if (lim != nullptr) {
+    rc = wva_lim_reserve(c, n_scen, lim->n_types);
+    if (rc != 0) return rc;
+  }
   const size_t cells = (size_t)n_scen * (size_t)c->n_cells;
   hipError_t err;
 
@@ -1816,6 +2391,13 @@ extern "C" int wva_ctx_plan(void *ctx, int n_scen, int n_acc, const float *scen_
   err = hipMemsetAsync(c->plan_tot, 0, (size_t)n_scen * n_acc * sizeof(unsigned long long),
                        c->s0);
   if (err != hipSuccess) return (int)err;
+  const size_t n_capacity = lim != nullptr ? (size_t)n_scen * (size_t)lim->n_types : 0;
+  if (lim != nullptr) {
+    for (size_t i = 0; i < n_capacity; ++i) c->lim_pin_capacity[i] = lim->capacity[i];
+    err = hipMemcpyAsync(c->lim_capacity, c->lim_pin_capacity, n_capacity * sizeof(int),
+                         hipMemcpyHostToDevice, c->s0);
+    if (err != hipSuccess) return (int)err;
+  }
   if (hipEventRecord(c->e_up, c->s0) != hipSuccess) return -10;
 
   // 2. planning buckets: same streams, fork/join and order as the reconcile
@@ -1833,14 +2415,39 @@ extern "C" int wva_ctx_plan(void *ctx, int n_scen, int n_acc, const float *scen_
     if (hipStreamWaitEvent(c->s0, c->e_b[i - 1], 0) != hipSuccess) return -14;
 
   // 3. winners, records and totals for all (server, scenario) pairs
-  hipLaunchKernelGGL(wva_plan_reduce, dim3(c->n_srv, n_scen), dim3(WVA_WAVE), 0, c->s0,
-                     c->plan_out.value, c->plan_out.feasible, c->plan_out.zero_empty,
-                     c->cell_acc, c->plan_out.num_replicas, c->plan_out.batch, c->plan_out.cost,
-                     c->plan_out.itl, c->plan_out.ttft, c->plan_out.rho, c->plan_out.max_rate,
-                     c->seg_start, c->n_srv, c->n_cells, n_scen, n_acc, c->plan_pf, c->plan_pi,
-                     c->plan_tot);
+  if (lim == nullptr) {
+    hipLaunchKernelGGL(wva_plan_reduce, dim3(c->n_srv, n_scen), dim3(WVA_WAVE), 0, c->s0,
+                       c->plan_out.value, c->plan_out.feasible, c->plan_out.zero_empty,
+                       c->cell_acc, c->plan_out.num_replicas, c->plan_out.batch, c->plan_out.cost,
+                       c->plan_out.itl, c->plan_out.ttft, c->plan_out.rho, c->plan_out.max_rate,
+                       c->seg_start, c->n_srv, c->n_cells, n_scen, n_acc, c->plan_pf, c->plan_pi,
+                       c->plan_tot);
+  } else {
+    size_t lds = wva_greedy_lds_bytes(c->n_srv, c->n_cells);
+    if (lds > c->lim_lds_budget ||
+        wva_optin_lds(reinterpret_cast<const void *>(&wva_plan_greedy), lds) != 0) {
+      (void)hipGetLastError();
+      lds = 0;  // hot state in the global workspace
+    }
+    hipLaunchKernelGGL(wva_plan_greedy, dim3(n_scen), dim3(WVA_WAVE), lds, c->s0,
+                       c->plan_out.value, c->plan_out.feasible, c->plan_out.zero_empty,
+                       c->cell_acc, c->plan_out.num_replicas, c->plan_out.batch, c->plan_out.cost,
+                       c->plan_out.itl, c->plan_out.ttft, c->plan_out.rho, c->plan_out.max_rate,
+                       c->seg_start, c->lim_cell_type, c->lim_cell_units, c->lim_srv_prio,
+                       c->n_srv, c->n_cells, n_scen, n_acc, lim->n_types, lim->delayed,
+                       lim->policy, lds > 0 ? 1 : 0, c->lim_capacity, c->lim_wsi, c->lim_wsd, c->plan_pf,
+                       c->plan_pi, c->lim_px, c->plan_tot);
+  }
   err = hipGetLastError();
   if (err != hipSuccess) return (int)err;
+  if (lim != nullptr) {
+    err = hipMemcpyAsync(c->lim_pin_capacity, c->lim_capacity, n_capacity * sizeof(int),
+                         hipMemcpyDeviceToHost, c->s0);
+    if (err != hipSuccess) return (int)err;
+    err = hipMemcpyAsync(c->lim_pin_px, c->lim_px, (size_t)n_scen * 2 * c->n_srv * sizeof(int),
+                         hipMemcpyDeviceToHost, c->s0);
+    if (err != hipSuccess) return (int)err;
+  }
 
   // 4. downloads
   err = hipMemcpyAsync(c->plan_pin_pf, c->plan_pf, (size_t)n_scen * 6 * c->n_srv * sizeof(float),
@@ -1859,6 +2466,40 @@ extern "C" int wva_ctx_plan(void *ctx, int n_scen, int n_acc, const float *scen_
   if (out_pf) *out_pf = c->plan_pin_pf;
   if (out_pi) *out_pi = c->plan_pin_pi;
   if (out_totals) *out_totals = c->plan_pin_tot;
+  return 0;
+}
+
+extern "C" int wva_ctx_plan(void *ctx, int n_scen, int n_acc, const float *scen_arrival,
+                            const void **out_pf, const void **out_pi,
+                            const void **out_totals) {
+  return wva_plan_run((WvaCtx *)ctx, n_scen, n_acc, scen_arrival, nullptr, out_pf, out_pi,
+                      out_totals);
+}
+
+// One capacity-limited planning pass: wva_ctx_plan's uploads and buckets, then
+// one greedy solve per scenario on the device. capacity: host, [n_scen]
+// [n_types] int32 units per accelerator type. policy: 0 None,
+// 1 PriorityExhaustive, 2 PriorityRoundRobin, 3 RoundRobin. The static inputs
+// must have been set (wva_ctx_set_greedy_static). pf, pi and totals are as for
+// wva_ctx_plan, holding the limited solution (pi row 0 is the granted
+// accelerator or -1, row 1 the granted replicas). out_px: pinned i32 [n_scen]
+// [2][n_srv] (the granted cell's pre-cut replicas; the server's feasible
+// candidates that are not zero-load). out_capacity: pinned i32 [n_scen]
+// [n_types], the capacity left.
+extern "C" int wva_ctx_plan_limited(void *ctx, int n_scen, int n_acc, const float *scen_arrival,
+                                    int n_types, const int *capacity, int delayed, int policy,
+                                    const void **out_pf, const void **out_pi,
+                                    const void **out_totals, const void **out_px,
+                                    const void **out_capacity) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || capacity == nullptr) return -31;
+  if (n_types < 1 || policy < 0 || policy > 3) return -32;
+  if (c->lim_static == nullptr) return -35;
+  const WvaLimArgs lim = {n_types, capacity, delayed ? 1 : 0, policy};
+  const int rc = wva_plan_run(c, n_scen, n_acc, scen_arrival, &lim, out_pf, out_pi, out_totals);
+  if (rc != 0) return rc;
+  if (out_px) *out_px = c->lim_pin_px;
+  if (out_capacity) *out_capacity = c->lim_pin_capacity;
   return 0;
 }
 
@@ -1894,5 +2535,7 @@ extern "C" void wva_ctx_destroy(void *ctx) {
   }
   if (c->memo != nullptr) (void)hipFree(c->memo);
   wva_plan_release(c);
+  wva_lim_release(c);
+  if (c->lim_static != nullptr) (void)hipFree(c->lim_static);
   delete c;
 }

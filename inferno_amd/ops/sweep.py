@@ -183,6 +183,30 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
     ]
     lib.wva_ctx_plan_cells.restype = ctypes.c_int
     lib.wva_ctx_plan_cells.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+    # capacity-limited planning (FastSweep.plan(capacity=...))
+    lib.wva_ctx_set_greedy_static.restype = ctypes.c_int
+    lib.wva_ctx_set_greedy_static.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_void_p,  # host i32 [n_cells] accelerator-type index per cell
+        ctypes.c_void_p,  # host i32 [n_cells] units per replica
+        ctypes.c_void_p,  # host i32 [n_srv] priority
+    ]
+    lib.wva_ctx_plan_limited.restype = ctypes.c_int
+    lib.wva_ctx_plan_limited.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_int,  # n_scen
+        ctypes.c_int,  # n_acc
+        ctypes.c_void_p,  # host fp32 [n_scen][n_cells] arrival rates
+        ctypes.c_int,  # n_types
+        ctypes.c_void_p,  # host i32 [n_scen][n_types] capacity
+        ctypes.c_int,  # delayed best-effort
+        ctypes.c_int,  # saturation policy 0..3
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned fp32 [n_scen][6][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_scen][4][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][n_acc]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_scen][2][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_scen][n_types]
+    ]
     _lib = lib
     return lib
 

@@ -29,7 +29,7 @@ import numpy as np
 from ..config import AllocationData, OptimizerSpec, SaturationPolicy
 from ..core.system import AllocationByType, System
 from ..engine import SweepEngine
-from ..engine.fastpath import FastSweep, _empty_winner
+from ..engine.fastpath import FastSweep, _empty_winner, greedy_candidates
 
 # winner record encoding: [server_global_idx, acc_code, num_replicas, cost,
 #                          batch, itl, ttft, valid]
@@ -340,29 +340,7 @@ class ShardedSolver:
     def _greedy_static(self, system: System):
         """Static per-cell greedy inputs (units/replica, accelerator-type
         index) and per-server priorities, cached per fleet topology."""
-        fs = self._fast_sweep
-        cached = getattr(fs, "_greedy_static_cache", None)
-        if cached is not None:
-            return cached
-        type_names = sorted(
-            {acc.type for acc in system.accelerators.values()} | set(system.capacity)
-        )
-        type_index = {t: i for i, t in enumerate(type_names)}
-        acc_tidx = np.empty(len(fs.acc_names), dtype=np.int32)
-        for i, an in enumerate(fs.acc_names):
-            acc_tidx[i] = type_index[system.accelerators[an].type]
-        units = np.empty(fs.n_cells, dtype=np.int32)
-        for k in range(fs.n_cells):
-            srv = fs._srv_objs[fs.cell_server[k]]
-            acc_name = fs.acc_names[fs.cell_acc_idx[k]]
-            acc = system.accelerators[acc_name]
-            model = system.models[srv.model_name]
-            units[k] = model.get_num_instances(acc_name) * acc.multiplicity
-        prio = np.array([s.priority(system) for s in fs._srv_objs], dtype=np.int32)
-        cell_tidx = acc_tidx[fs.cell_acc_idx]
-        cached = (type_names, cell_tidx, units, prio)
-        fs._greedy_static_cache = cached
-        return cached
+        return self._fast_sweep.greedy_static()
 
     def _solve_limited_native(self, system: System, local_names, cells, spec,
                               acc_names):
@@ -380,25 +358,11 @@ class ShardedSolver:
         type_names, cell_tidx, units, prio = self._greedy_static(system)
         fs = self._fast_sweep
 
-        feas = cells["feasible"].astype(bool)
-        idx = np.nonzero(feas)[0]
-        value = cells["value"]
-        srv_of = cells["cell_server"]
-        # per-server candidates sorted by value; stable -> acc-name tie order
-        # (identical to sorted(all_allocations.values(), key=value))
-        order = idx[np.lexsort((value[idx].astype(np.float64), srv_of[idx]))]
         n_srv = len(local_names)
-        counts = np.bincount(srv_of[order], minlength=n_srv)
-        seg = np.zeros(n_srv + 1, dtype=np.int32)
-        np.cumsum(counts, out=seg[1:])
-
-        cand_value = np.ascontiguousarray(value[order], dtype=np.float32)
-        # zero-load "" allocations drop like the Python acc-lookup miss
-        cand_tidx = np.where(
-            cells["zero_empty"][order].astype(bool), -1, cell_tidx[order]
-        ).astype(np.int32)
-        cand_units = np.ascontiguousarray(units[order], dtype=np.int32)
-        cand_reps = np.ascontiguousarray(cells["num_replicas"][order], dtype=np.int32)
+        order, seg, cand_value, cand_tidx, cand_units, cand_reps = greedy_candidates(
+            cells["feasible"], cells["zero_empty"], cells["value"], cells["num_replicas"],
+            cells["cell_server"], cell_tidx, units, n_srv,
+        )
         capacity = np.array(
             [int(system.capacity.get(t, 0)) for t in type_names], dtype=np.int32
         )
