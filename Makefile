@@ -1,7 +1,7 @@
 PYTHON ?= python
 IMG ?= inferno-amd/controller:latest
 
-.PHONY: all build test test-gpu bench bench-cpu prof deploy-crd deploy undeploy docker-build lint
+.PHONY: all build test test-gpu bench bench-cpu prof deploy-crd deploy undeploy docker-build lint asan-stage
 
 all: build test
 
@@ -65,6 +65,16 @@ lint:
 ## AddressSanitizer pass over the native C++ greedy (host code)
 asan-greedy:
 	$(PYTHON) scripts/greedy_asan_check.py
+
+## AddressSanitizer + UBSan pass over the tick's host staging and by-type
+## aggregation (ops/native/stage.cpp) through its stand-alone driver
+CXX ?= g++
+asan-stage:
+	mkdir -p build
+	$(CXX) -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all \
+		inferno_amd/ops/native/stage.cpp inferno_amd/ops/native/stage_driver.cpp \
+		-o build/stage_driver
+	./build/stage_driver
 
 ## One-command local stack (apiserver stand-in + emulator + TLS prom + controller)
 stack:

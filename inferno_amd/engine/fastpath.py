@@ -6,10 +6,12 @@ FastSweep splits the snapshot into:
 
   * a STATIC cell structure built once per fleet topology (perf parms,
     SLO targets, cell->server segments, accelerator costs), and
-  * a vectorized DYNAMIC refresh per reconcile (arrival rates, token
-    averages, current-allocation penalty inputs) — pure numpy gathers.
+  * a DYNAMIC refresh per reconcile (arrival rates, token averages,
+    current-allocation penalty inputs): on the GPU path a native loop over
+    the cells (ops/native/stage.cpp) behind the tick's one C call, with the
+    vectorized numpy version (_refresh_dynamic) as its reference.
 
-Per reconcile it uploads the refreshed SoA, launches wva_sweep + wva_argmin,
+Per reconcile it uploads the refreshed SoA, launches wva_sweep + wva_winner,
 and materializes ONLY the per-server winner records (not all candidate
 cells). The slow path (SweepEngine) remains the oracle and serves greedy
 limited mode, which needs the full candidate lists.
@@ -238,17 +240,11 @@ class FastSweep:
                 out_tok[i] = load.avgOutTokens if load is not None else 0
         return arrival, in_tok, out_tok
 
-    def _refresh_dynamic(self, plan_arrival: Optional[np.ndarray] = None) -> dict:
-        """Gather per-server dynamic state into per-cell arrays (vectorized).
-
-        ``plan_arrival`` ([S, n_servers] fp32, scenario planning) replaces the
-        per-server arrival rate by its maximum over the scenarios: a cell then
-        counts as zero-load only where no scenario loads it, so every loaded
-        cell keeps the batch size a single reconcile of that scenario uses."""
+    def _base_cur(self):
+        """(cur_acc i32 [-3 none, -1 empty, >= 0 accelerator index],
+        cur_replicas i32, cur_cost f32) per server: the current-allocation
+        override when set, else the server objects."""
         n_srv = len(self.server_names)
-        arrival, in_tok, out_tok = self._base_load()
-        if plan_arrival is not None:
-            arrival = plan_arrival.max(axis=0).astype(np.float32)
         if self.cur_override is not None:
             cur_acc, cur_rep, cur_cost = self.cur_override
             cur_acc = np.asarray(cur_acc, dtype=np.int32)
@@ -266,6 +262,19 @@ class FastSweep:
                     cur_acc[i] = self._acc_index.get(cur.accelerator, -1)
                     cur_rep[i] = cur.num_replicas
                     cur_cost[i] = cur.cost
+        return cur_acc, cur_rep, cur_cost
+
+    def _refresh_dynamic(self, plan_arrival: Optional[np.ndarray] = None) -> dict:
+        """Gather per-server dynamic state into per-cell arrays (vectorized).
+
+        ``plan_arrival`` ([S, n_servers] fp32, scenario planning) replaces the
+        per-server arrival rate by its maximum over the scenarios: a cell then
+        counts as zero-load only where no scenario loads it, so every loaded
+        cell keeps the batch size a single reconcile of that scenario uses."""
+        arrival, in_tok, out_tok = self._base_load()
+        if plan_arrival is not None:
+            arrival = plan_arrival.max(axis=0).astype(np.float32)
+        cur_acc, cur_rep, cur_cost = self._base_cur()
 
         cs = self.cell_server
         c_out = out_tok[cs]
@@ -341,11 +350,13 @@ class FastSweep:
         return self._reconcile_cpu()
 
     # GPU persistent-state reconcile: static SoA uploaded once; per step the
-    # dynamic fields are packed into TWO pinned staging buffers (one int32,
-    # one fp32) -> two H2D copies; bucket ids cached on the batch_n bytes;
-    # outputs preallocated; winner records gathered ON-DEVICE and downloaded
-    # in a single D2H copy.
+    # native library expands the per-server state into ONE pinned dynamic
+    # block (the _DYN_INT rows, then _DYN_F32) -> one H2D copy; the bucket
+    # layout is kept until the staged batch_n differs from the one it was
+    # chosen for; outputs preallocated; winner records selected and gathered
+    # ON-DEVICE in one launch and downloaded in a single D2H copy.
     _DYN_INT = ("in_tok", "out_tok", "batch_n", "perf_max_batch", "cur_replicas", "flags")
+    _DYN_F32 = ("arrival_rate", "cur_cost")
     _STAT_F32 = ("alpha", "beta", "gamma", "delta", "t_itl", "t_ttft", "t_tps", "acc_cost")
 
     def _init_gpu_state(self) -> None:
@@ -362,11 +373,11 @@ class FastSweep:
         st["min_replicas"] = torch.from_numpy(
             np.ascontiguousarray(self._stat["min_replicas"], dtype=np.int32)
         ).to(dev)
-        st["pin_i"] = torch.empty((len(self._DYN_INT), n), dtype=torch.int32,
-                                  pin_memory=True)
-        st["pin_f"] = torch.empty((2, n), dtype=torch.float32, pin_memory=True)
-        st["dev_i"] = torch.empty((len(self._DYN_INT), n), dtype=torch.int32, device=dev)
-        st["dev_f"] = torch.empty((2, n), dtype=torch.float32, device=dev)
+        # the dynamic block: 4-byte words, int32 rows then fp32 rows
+        n_dyn = len(self._DYN_INT) + len(self._DYN_F32)
+        st["pin_dyn"] = torch.empty((n_dyn, n), dtype=torch.int32, pin_memory=True)
+        st["dev_dyn"] = torch.empty((n_dyn, n), dtype=torch.int32, device=dev)
+        st["pin_dyn_np"] = st["pin_dyn"].numpy()
         st["seg"] = torch.from_numpy(self.seg_start).to(dev)
         st["cell_acc"] = torch.from_numpy(self.cell_acc_idx).to(dev)
         # outputs
@@ -378,10 +389,13 @@ class FastSweep:
             st[k] = torch.zeros(n, dtype=torch.float32, device=dev)
         n_srv = len(self.server_names)
         st["winner"] = torch.full((n_srv,), -1, dtype=torch.int32, device=dev)
-        st["gather_f"] = torch.empty((6, n_srv), dtype=torch.float32, device=dev)
-        st["gather_i"] = torch.empty((4, n_srv), dtype=torch.int32, device=dev)
-        st["pin_out_f"] = torch.empty((6, n_srv), dtype=torch.float32, pin_memory=True)
-        st["pin_out_i"] = torch.empty((4, n_srv), dtype=torch.int32, pin_memory=True)
+        # winner records: six fp32 rows (cost, value, itl, ttft, rho, max_rate)
+        # then four int32 rows (acc code, num_replicas, batch, winner cell)
+        st["gather"] = torch.empty((10, n_srv), dtype=torch.int32, device=dev)
+        st["pin_out"] = torch.empty((10, n_srv), dtype=torch.int32, pin_memory=True)
+        st["pin_out_np"] = st["pin_out"].numpy()
+        st["tick_stale"] = False  # did the last tick find the bucket layout stale
+        st["stale_ticks"] = 0
         st["bucket_key"] = None
         st["buckets"] = []
         self._gpu = st
@@ -418,18 +432,17 @@ class FastSweep:
         if "ctx" in st:
             return
         lib = load_library(allow_build=False)
-        di, df = st["dev_i"], st["dev_f"]
+        # slot order: see WVA_CTX_SLOTS in ops/hip/wva_kernels.hip
         slots = [
-            di, df,
+            st["dev_dyn"],
             st["min_replicas"],
             st["alpha"], st["beta"], st["gamma"], st["delta"],
             st["t_itl"], st["t_ttft"], st["t_tps"], st["acc_cost"],
             st["feasible"], st["zero_empty"], st["num_replicas"], st["batch"],
             st["cost"], st["value"], st["itl"], st["ttft"], st["rho"],
             st["max_rate"],
-            st["seg"], st["winner"], st["cell_acc"], st["gather_f"],
-            st["gather_i"],
-            st["pin_i"], st["pin_f"], st["pin_out_f"], st["pin_out_i"],
+            st["seg"], st["winner"], st["cell_acc"], st["gather"],
+            st["pin_dyn"], st["pin_out"],
         ]
         arr = (ctypes.c_void_p * len(slots))(
             *[ctypes.c_void_p(t.data_ptr()) for t in slots]
@@ -443,6 +456,17 @@ class FastSweep:
             raise HipKernelError("wva_ctx_create failed")
         st["ctx"] = ctx
         st["ctx_lib"] = lib
+        # the static topology the native tick stages from (copied by the ctx)
+        topo = [
+            np.ascontiguousarray(a, dtype=np.int32)
+            for a in (self.cell_server, self.cell_acc_idx, self._stat["perf_max_batch_cfg"],
+                      self._stat["at_tokens"], self._stat["override"])
+        ]
+        rc = lib.wva_ctx_set_topology(ctx, *[a.ctypes.data for a in topo])
+        if rc != 0:
+            from ..ops.sweep import HipKernelError
+
+            raise HipKernelError(f"wva_ctx_set_topology failed: {rc}")
 
     def __del__(self):  # release the native context's streams/events
         st = getattr(self, "_gpu", None)
@@ -452,14 +476,15 @@ class FastSweep:
             except Exception:
                 pass
 
-    def _sync_buckets(self, batch_n: np.ndarray) -> None:
-        """Push the bucket layout + analyzer mode into the native context
-        (only when it changed)."""
+    def _sync_buckets(self, batch_n: np.ndarray, force: bool = False) -> None:
+        """Push the bucket layout + analyzer mode into the native context,
+        together with the batch_n it was chosen for (only when it changed,
+        or when the context itself reported its layout stale)."""
         import ctypes
 
         st = self._gpu
         buckets = self._buckets_for(batch_n)
-        if st.get("ctx_buckets_key") == st["bucket_key"]:
+        if not force and st.get("ctx_buckets_key") == st["bucket_key"]:
             return
         n = len(buckets)
         nts = (ctypes.c_int * n)(*[b[0] for b in buckets])
@@ -481,9 +506,11 @@ class FastSweep:
         )
         mode = 1 if getattr(self.system, "analyzer_mode", "mm1k") == "mg1" else 0
         cv2 = float(getattr(self.system, "analyzer_cv2", 1.0))
+        batch_n = np.ascontiguousarray(batch_n, dtype=np.int32)
         rc = st["ctx_lib"].wva_ctx_set_buckets(
             st["ctx"], ctypes.c_int(n), nts, ids, nbl, mxn,
             ctypes.c_int(mode), ctypes.c_float(cv2), g_invs, g_anchors,
+            batch_n.ctypes.data,
         )
         if rc != 0:
             from ..ops.sweep import HipKernelError
@@ -491,28 +518,59 @@ class FastSweep:
             raise HipKernelError(f"wva_ctx_set_buckets failed: {rc}")
         st["ctx_buckets_key"] = st["bucket_key"]
 
-    def _fill_pinned(self, arrs: dict) -> None:
-        import torch
+    def _tick(self, plan_arrival: Optional[np.ndarray] = None, launch: bool = True) -> None:
+        """One native tick (wva_ctx_tick): the library expands the six
+        per-server arrays into the pinned dynamic block — what
+        _refresh_dynamic() computes, byte for byte — and, with ``launch``,
+        runs the whole device pipeline and synchronises. When the staged
+        batch_n no longer fits the context's bucket layout the library
+        launches nothing and says so; the layout is then chosen here as
+        before and the already staged tick resumed (wva_reconcile).
 
-        st = self._gpu
-        pin_i, pin_f = st["pin_i"], st["pin_f"]
-        for j, k in enumerate(self._DYN_INT):
-            pin_i[j] = torch.from_numpy(np.ascontiguousarray(arrs[k], dtype=np.int32))
-        pin_f[0] = torch.from_numpy(
-            np.ascontiguousarray(arrs["arrival_rate"], dtype=np.float32)
-        )
-        pin_f[1] = torch.from_numpy(np.ascontiguousarray(arrs["cur_cost"], dtype=np.float32))
-
-    def _native_reconcile(self, arrs: dict) -> None:
-        from ..ops.sweep import HipKernelError
+        ``plan_arrival`` as in _refresh_dynamic; the planning passes stage
+        with ``launch=False`` and run their own pipeline afterwards."""
+        from ..ops.sweep import TICK_STALE, HipKernelError
 
         st = self._gpu
         self._ensure_ctx()
-        self._fill_pinned(arrs)
-        self._sync_buckets(arrs["batch_n"])
-        rc = st["ctx_lib"].wva_reconcile(st["ctx"])
+        arrival, in_tok, out_tok = self._base_load()
+        zero = None
+        if plan_arrival is not None:
+            arrival = plan_arrival.max(axis=0).astype(np.float32)
+            zero = arrival
+        cur_acc, cur_rep, cur_cost = self._base_cur()
+        n_srv = len(self.server_names)
+        f32, i32 = np.float32, np.int32
+        srv = (
+            np.ascontiguousarray(arrival, dtype=f32), np.ascontiguousarray(in_tok, dtype=i32),
+            np.ascontiguousarray(out_tok, dtype=i32), np.ascontiguousarray(cur_acc, dtype=i32),
+            np.ascontiguousarray(cur_rep, dtype=i32), np.ascontiguousarray(cur_cost, dtype=f32),
+        )
+        for a in srv:
+            if a.shape != (n_srv,):
+                raise ValueError(
+                    f"per-server override has shape {a.shape}, expected ({n_srv},)"
+                )
+        lib = st["ctx_lib"]
+        rc = lib.wva_ctx_tick(
+            st["ctx"], srv[0].ctypes.data, srv[1].ctypes.data, srv[2].ctypes.data,
+            srv[3].ctypes.data, srv[4].ctypes.data, srv[5].ctypes.data,
+            zero.ctypes.data if zero is not None else None, 1 if launch else 0,
+        )
+        st["tick_stale"] = rc == TICK_STALE
+        if rc == TICK_STALE:
+            st["stale_ticks"] += 1
+            batch_n = st["pin_dyn_np"][self._DYN_INT.index("batch_n")].copy()
+            self._sync_buckets(batch_n, force=True)
+            rc = lib.wva_reconcile(st["ctx"]) if launch else 0
         if rc != 0:
-            raise HipKernelError(f"wva_reconcile failed: {rc}")
+            raise HipKernelError(f"native reconcile tick failed: {rc}")
+
+    def _winner_block(self) -> tuple[np.ndarray, np.ndarray]:
+        """The last tick's winner records, copied out of the pinned block:
+        (fp32 [6, n_srv], int32 [4, n_srv])."""
+        blk = self._gpu["pin_out_np"].copy()
+        return blk[:6].view(np.float32), blk[6:]
 
     def memo_stats(self) -> Optional[tuple[int, int]]:
         """(hits, misses) of the native context's sizing memo since the
@@ -545,8 +603,7 @@ class FastSweep:
         if not hasattr(self, "_gpu"):
             self._init_gpu_state()
         st = self._gpu
-        arrs = self._refresh_dynamic()
-        self._native_reconcile(arrs)  # fully synced on return
+        self._tick()  # fully synced on return
         out = {
             k: st[k].cpu().numpy()
             for k in ("feasible", "zero_empty", "num_replicas", "batch", "cost",
@@ -563,21 +620,18 @@ class FastSweep:
             return _empty_winner(n_srv)
         if not hasattr(self, "_gpu"):
             self._init_gpu_state()
-        st = self._gpu
-        arrs = self._refresh_dynamic()
-        self._native_reconcile(arrs)
-        of = st["pin_out_f"].numpy()
-        oi = st["pin_out_i"].numpy()
+        self._tick()
+        of, oi = self._winner_block()  # one copy; the rows are views of it
         return WinnerRecord(
-            acc_idx=oi[0].copy(),
-            num_replicas=oi[1].copy(),
-            batch=oi[2].copy(),
-            cost=of[0].copy(),
-            value=of[1].copy(),
-            itl=of[2].copy(),
-            ttft=of[3].copy(),
-            rho=of[4].copy(),
-            max_rate=of[5].copy(),
+            acc_idx=oi[0],
+            num_replicas=oi[1],
+            batch=oi[2],
+            cost=of[0],
+            value=of[1],
+            itl=of[2],
+            ttft=of[3],
+            rho=of[4],
+            max_rate=of[5],
         )
 
     # ------------------------------------------------------------------
@@ -700,10 +754,7 @@ class FastSweep:
         if not hasattr(self, "_gpu"):
             self._init_gpu_state()
         st = self._gpu
-        arrs = self._refresh_dynamic(plan_arrival=scen)
-        self._ensure_ctx()
-        self._fill_pinned(arrs)
-        self._sync_buckets(arrs["batch_n"])
+        self._tick(plan_arrival=scen, launch=False)  # stage + bucket layout
         cell_scen = np.ascontiguousarray(scen[:, self.cell_server], dtype=np.float32)
         p_f, p_i, p_t = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         rc = st["ctx_lib"].wva_ctx_plan(
@@ -879,10 +930,7 @@ class FastSweep:
         if not hasattr(self, "_gpu"):
             self._init_gpu_state()
         st = self._gpu
-        arrs = self._refresh_dynamic(plan_arrival=scen)
-        self._ensure_ctx()
-        self._fill_pinned(arrs)
-        self._sync_buckets(arrs["batch_n"])
+        self._tick(plan_arrival=scen, launch=False)  # stage + bucket layout
         self._sync_greedy_static()
         cell_scen = np.ascontiguousarray(scen[:, self.cell_server], dtype=np.float32)
         p_f, p_i, p_t = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()

@@ -14,8 +14,14 @@ import sys
 OPS_DIR = os.path.dirname(os.path.abspath(__file__))
 HIP_SRC = os.path.join(OPS_DIR, "hip", "wva_kernels.hip")
 # host-only native sources linked into the same .so (C++ runtime pieces:
-# the sequential greedy tail of limited mode)
-NATIVE_SRCS = [os.path.join(OPS_DIR, "native", "greedy.cpp")]
+# the sequential greedy tail of limited mode; the reconcile tick's host
+# staging and by-type aggregation)
+NATIVE_SRCS = [
+    os.path.join(OPS_DIR, "native", "greedy.cpp"),
+    os.path.join(OPS_DIR, "native", "stage.cpp"),
+]
+# headers the sources above include (a newer one makes the library stale)
+NATIVE_HDRS = [os.path.join(OPS_DIR, "native", "wva_stage.h")]
 LIB_DIR = os.path.join(OPS_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libwva_hip.so")
 
@@ -28,7 +34,7 @@ def needs_build() -> bool:
         return True
     lib_mtime = os.path.getmtime(LIB_PATH)
     return any(
-        os.path.getmtime(src) > lib_mtime for src in [HIP_SRC, *NATIVE_SRCS]
+        os.path.getmtime(src) > lib_mtime for src in [HIP_SRC, *NATIVE_SRCS, *NATIVE_HDRS]
     )
 
 

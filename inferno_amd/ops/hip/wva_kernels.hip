@@ -51,8 +51,11 @@
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <type_traits>
+
+#include "../native/wva_stage.h"  // dynamic-block rows, tick code, host staging ABI
 
 #define WVA_WAVE 64
 // max LDS-resident batch size per cell (bounds the LDS chain geometry:
@@ -1320,16 +1323,17 @@ extern "C" __global__ void __launch_bounds__(256) wva_gather(
 // atomic (a cell may hold 2 147 483 000 replicas, and integer adds make the
 // sum independent of execution order).
 // ---------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_reduce(
+// Shared by wva_plan_reduce and wva_winner: one wave selects server srv's
+// winner on scenario slice sc (cell arrays offset by sc * n_cells) and lane 0
+// writes the record into gf[6][n_srv] / gi[4][n_srv]. Returns the winner cell
+// index on lane 0 (other lanes: unspecified); acc and reps are lane 0's
+// record fields.
+__device__ __forceinline__ int wva_winner_record(
     const float *value, const uint8_t *feasible, const uint8_t *zero_empty, const int *cell_acc,
     const int *num_replicas, const int *batch, const float *cost, const float *itl,
     const float *ttft, const float *rho, const float *max_rate, const int *seg_start, int n_srv,
-    int n_cells, int n_scen, int n_acc, float *pf, int *pi, unsigned long long *totals) {
-  const int srv = blockIdx.x;
-  const int sc = blockIdx.y;
-  if (srv >= n_srv || sc >= n_scen) return;
+    size_t base, int srv, float *gf, int *gi, int &acc, int &reps) {
   const int lane = threadIdx.x;
-  const size_t base = (size_t)sc * (size_t)n_cells;
   const int beg = seg_start[srv], end = seg_start[srv + 1];
   float best = INFINITY;
   int best_i = -1;
@@ -1350,14 +1354,14 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_reduce(
       best_i = oi;
     }
   }
-  if (lane != 0) return;
+  acc = -1;
+  reps = 0;
+  if (lane != 0) return -1;
   const int w = best_i;
   const bool has = w >= 0;
   const size_t wc = base + (size_t)(has ? w : 0);
-  float *gf = pf + (size_t)sc * 6 * (size_t)n_srv;
-  int *gi = pi + (size_t)sc * 4 * (size_t)n_srv;
-  const int acc = has ? (zero_empty[wc] ? -2 : cell_acc[w]) : -1;
-  const int reps = has ? num_replicas[wc] : 0;
+  acc = has ? (zero_empty[wc] ? -2 : cell_acc[w]) : -1;
+  reps = has ? num_replicas[wc] : 0;
   gf[0 * n_srv + srv] = has ? cost[wc] : 0.0f;
   gf[1 * n_srv + srv] = has ? value[wc] : 0.0f;
   gf[2 * n_srv + srv] = has ? itl[wc] : 0.0f;
@@ -1368,8 +1372,46 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_reduce(
   gi[1 * n_srv + srv] = reps;
   gi[2 * n_srv + srv] = has ? batch[wc] : 0;
   gi[3 * n_srv + srv] = w;
+  return w;
+}
+
+extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_reduce(
+    const float *value, const uint8_t *feasible, const uint8_t *zero_empty, const int *cell_acc,
+    const int *num_replicas, const int *batch, const float *cost, const float *itl,
+    const float *ttft, const float *rho, const float *max_rate, const int *seg_start, int n_srv,
+    int n_cells, int n_scen, int n_acc, float *pf, int *pi, unsigned long long *totals) {
+  const int srv = blockIdx.x;
+  const int sc = blockIdx.y;
+  if (srv >= n_srv || sc >= n_scen) return;
+  int acc, reps;
+  wva_winner_record(value, feasible, zero_empty, cell_acc, num_replicas, batch, cost, itl, ttft,
+                    rho, max_rate, seg_start, n_srv, (size_t)sc * (size_t)n_cells, srv,
+                    pf + (size_t)sc * 6 * (size_t)n_srv, pi + (size_t)sc * 4 * (size_t)n_srv, acc,
+                    reps);
+  if (threadIdx.x != 0) return;
   if (acc >= 0 && acc < n_acc && reps > 0)
     atomicAdd(totals + (size_t)sc * (size_t)n_acc + (size_t)acc, (unsigned long long)reps);
+}
+
+// ---------------------------------------------------------------------------
+// K4b wva_winner: the reconcile tick's winner step in one launch, one wave
+// per server: wva_argmin's selection followed by wva_gather's record, i.e.
+// wva_plan_reduce on a single scenario without the totals. rec is the
+// 10 x n_srv winner block (six fp32 rows, then four int32 rows); winner[srv]
+// gets the winning cell index as wva_argmin leaves it.
+// ---------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_winner(
+    const float *value, const uint8_t *feasible, const uint8_t *zero_empty, const int *cell_acc,
+    const int *num_replicas, const int *batch, const float *cost, const float *itl,
+    const float *ttft, const float *rho, const float *max_rate, const int *seg_start, int n_srv,
+    void *rec, int *winner) {
+  const int srv = blockIdx.x;
+  if (srv >= n_srv) return;
+  int acc, reps;
+  const int w = wva_winner_record(value, feasible, zero_empty, cell_acc, num_replicas, batch, cost,
+                                  itl, ttft, rho, max_rate, seg_start, n_srv, 0, srv,
+                                  (float *)rec, (int *)rec + (size_t)6 * (size_t)n_srv, acc, reps);
+  if (threadIdx.x == 0) winner[srv] = w;
 }
 
 // ---------------------------------------------------------------------------
@@ -1803,9 +1845,10 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_greedy(
 
 // ---------------------------------------------------------------------------
 // Native reconcile context: the whole per-tick device pipeline behind ONE C
-// call (H2D copies, regime-bucketed sweep launches overlapped via events on
-// three streams, argmin, gather, D2H, sync) — no per-step host dispatch
-// beyond wva_reconcile(ctx).
+// call (host staging of the per-server state, one H2D copy, regime-bucketed
+// sweep launches overlapped via events on side streams, the fused winner
+// kernel, one D2H copy, sync) — no per-step host dispatch beyond
+// wva_ctx_tick(ctx, ...); wva_reconcile(ctx) runs an already staged tick.
 // ---------------------------------------------------------------------------
 #define WVA_MAX_BUCKETS 5
 
@@ -1829,15 +1872,22 @@ struct WvaCtx {
   const int *seg_start;
   int *winner;
   const int *cell_acc;
-  float *gather_f;
-  int *gather_i;
-  // device dynamic blocks + host pinned sources
-  void *dev_i;        // 6 x n_cells int32
-  void *dev_f;        // 2 x n_cells f32
-  const void *pin_i;  // host pinned
-  const void *pin_f;
-  void *pin_out_f;    // host pinned, 6 x n_srv f32
-  void *pin_out_i;    // host pinned, 4 x n_srv i32
+  // dynamic block: WVA_DYN_ROWS x n_cells 4-byte words (six int32 rows, then
+  // arrival_rate and cur_cost), one device allocation and its pinned source;
+  // `in` points into the device one
+  void *dev_dyn;
+  void *pin_dyn;
+  // winner records: 10 x n_srv words (six fp32 rows, then four int32 rows),
+  // one device block and its pinned mirror
+  void *gather;
+  void *pin_out;
+  // host-side staging (wva_ctx_tick): the static per-cell topology and the
+  // batch_n row the current bucket layout was chosen for (one host
+  // allocation, carved up)
+  int *topo;  // nullptr until wva_ctx_set_topology
+  const int *topo_cell_server, *topo_cell_acc, *topo_cfg, *topo_at_tokens, *topo_override;
+  int *bucket_batch_n;
+  int bucket_batch_valid;  // 0 until set_buckets recorded a batch_n row
   WvaBucket buckets[WVA_MAX_BUCKETS];
   int n_buckets;
   hipStream_t s0;                           // primary stream
@@ -1845,7 +1895,7 @@ struct WvaCtx {
   hipEvent_t e_up;                          // upload-complete
   hipEvent_t e_b[WVA_MAX_BUCKETS - 1];      // side-bucket completion
   // hipGraph capture of the whole per-tick pipeline (H2D copies, bucket
-  // kernels on their streams, argmin+gather, D2H): replayed as ONE launch
+  // kernels on their streams, winner kernel, D2H): replayed as ONE launch
   // per reconcile. State: 0 = not captured, 1 = exec valid, -1 = capture
   // failed once -> stay on the eager path. Invalidated by set_buckets.
   hipGraphExec_t graph_exec;
@@ -1893,14 +1943,18 @@ struct WvaCtx {
 };
 
 // pointer-slot order for wva_ctx_create (host mirrors in ops/sweep.py):
-//  0 dev_i (6*n_cells i32)   1 dev_f (2*n_cells f32)
-//  2 min_replicas            3 alpha  4 beta  5 gamma  6 delta
-//  7 t_itl  8 t_ttft  9 t_tps  10 acc_cost
-//  11 feasible  12 zero_empty  13 num_replicas  14 batch  15 cost
-//  16 value  17 itl  18 ttft  19 rho  20 max_rate
-//  21 seg_start  22 winner  23 cell_acc  24 gather_f  25 gather_i
-//  26 pin_i  27 pin_f  28 pin_out_f  29 pin_out_i
-#define WVA_CTX_SLOTS 30
+//  0 dev_dyn (8*n_cells words: in_tok, out_tok, batch_n, perf_max_batch,
+//    cur_replicas, flags i32; arrival_rate, cur_cost f32)
+//  1 min_replicas            2 alpha  3 beta  4 gamma  5 delta
+//  6 t_itl  7 t_ttft  8 t_tps  9 acc_cost
+//  10 feasible  11 zero_empty  12 num_replicas  13 batch  14 cost
+//  15 value  16 itl  17 ttft  18 rho  19 max_rate
+//  20 seg_start  21 winner  22 cell_acc
+//  23 gather (10*n_srv words: cost, value, itl, ttft, rho, max_rate f32;
+//     acc code, num_replicas, batch, winner cell i32)
+//  24 pin_dyn (pinned source of 0)  25 pin_out (pinned mirror of 23)
+#define WVA_CTX_SLOTS 26
+#define WVA_REC_ROWS 10
 
 extern "C" void *wva_ctx_create(int n_cells, int n_srv, void **p) {
   WvaCtx *c = new WvaCtx();
@@ -1933,48 +1987,44 @@ extern "C" void *wva_ctx_create(int n_cells, int n_srv, void **p) {
     if (end != lds_env && *end == '\0' && v >= 0 && v <= 120 * 1024)
       c->lim_lds_budget = (size_t)v;
   }
-  char *di = (char *)p[0];
-  char *df = (char *)p[1];
-  size_t ci = (size_t)n_cells * sizeof(int);
-  size_t cf = (size_t)n_cells * sizeof(float);
-  c->in.in_tok = (const int *)(di + 0 * ci);
-  c->in.out_tok = (const int *)(di + 1 * ci);
-  c->in.batch_n = (const int *)(di + 2 * ci);
-  c->in.perf_max_batch = (const int *)(di + 3 * ci);
-  c->in.cur_replicas = (const int *)(di + 4 * ci);
-  c->in.flags = (const int *)(di + 5 * ci);
-  c->in.min_replicas = (const int *)p[2];
-  c->in.alpha = (const float *)p[3];
-  c->in.beta = (const float *)p[4];
-  c->in.gamma = (const float *)p[5];
-  c->in.delta = (const float *)p[6];
-  c->in.arrival_rate = (const float *)(df + 0 * cf);
-  c->in.cur_cost = (const float *)(df + 1 * cf);
-  c->in.t_itl = (const float *)p[7];
-  c->in.t_ttft = (const float *)p[8];
-  c->in.t_tps = (const float *)p[9];
-  c->in.acc_cost = (const float *)p[10];
-  c->out.feasible = (uint8_t *)p[11];
-  c->out.zero_empty = (uint8_t *)p[12];
-  c->out.num_replicas = (int *)p[13];
-  c->out.batch = (int *)p[14];
-  c->out.cost = (float *)p[15];
-  c->out.value = (float *)p[16];
-  c->out.itl = (float *)p[17];
-  c->out.ttft = (float *)p[18];
-  c->out.rho = (float *)p[19];
-  c->out.max_rate = (float *)p[20];
-  c->seg_start = (const int *)p[21];
-  c->winner = (int *)p[22];
-  c->cell_acc = (const int *)p[23];
-  c->gather_f = (float *)p[24];
-  c->gather_i = (int *)p[25];
-  c->dev_i = p[0];
-  c->dev_f = p[1];
-  c->pin_i = p[26];
-  c->pin_f = p[27];
-  c->pin_out_f = p[28];
-  c->pin_out_i = p[29];
+  c->topo = nullptr;
+  c->bucket_batch_valid = 0;
+  char *dd = (char *)p[0];
+  size_t cw = (size_t)n_cells * 4;  // one row of the dynamic block
+  c->in.in_tok = (const int *)(dd + 0 * cw);
+  c->in.out_tok = (const int *)(dd + 1 * cw);
+  c->in.batch_n = (const int *)(dd + 2 * cw);
+  c->in.perf_max_batch = (const int *)(dd + 3 * cw);
+  c->in.cur_replicas = (const int *)(dd + 4 * cw);
+  c->in.flags = (const int *)(dd + 5 * cw);
+  c->in.arrival_rate = (const float *)(dd + 6 * cw);
+  c->in.cur_cost = (const float *)(dd + 7 * cw);
+  c->in.min_replicas = (const int *)p[1];
+  c->in.alpha = (const float *)p[2];
+  c->in.beta = (const float *)p[3];
+  c->in.gamma = (const float *)p[4];
+  c->in.delta = (const float *)p[5];
+  c->in.t_itl = (const float *)p[6];
+  c->in.t_ttft = (const float *)p[7];
+  c->in.t_tps = (const float *)p[8];
+  c->in.acc_cost = (const float *)p[9];
+  c->out.feasible = (uint8_t *)p[10];
+  c->out.zero_empty = (uint8_t *)p[11];
+  c->out.num_replicas = (int *)p[12];
+  c->out.batch = (int *)p[13];
+  c->out.cost = (float *)p[14];
+  c->out.value = (float *)p[15];
+  c->out.itl = (float *)p[16];
+  c->out.ttft = (float *)p[17];
+  c->out.rho = (float *)p[18];
+  c->out.max_rate = (float *)p[19];
+  c->seg_start = (const int *)p[20];
+  c->winner = (int *)p[21];
+  c->cell_acc = (const int *)p[22];
+  c->gather = p[23];
+  c->dev_dyn = p[0];
+  c->pin_dyn = p[24];
+  c->pin_out = p[25];
   bool ok = hipStreamCreateWithFlags(&c->s0, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&c->e_up, hipEventDisableTiming) == hipSuccess;
   for (int i = 0; ok && i < WVA_MAX_BUCKETS - 1; ++i)
@@ -1990,7 +2040,7 @@ extern "C" void *wva_ctx_create(int n_cells, int n_srv, void **p) {
   const char *memo_env = getenv("INFERNO_SIZING_MEMO");
   const bool memo_on = !(memo_env != nullptr && memo_env[0] == '0' && memo_env[1] == '\0');
   if (memo_on && n_cells > 0) {
-    // allocate on the device that owns dev_i (the kernels' inputs)
+    // allocate on the device that owns dev_dyn (the kernels' inputs)
     int prev_dev = -1, dev = -1;
     hipPointerAttribute_t attr;
     if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
@@ -2027,12 +2077,52 @@ extern "C" int wva_ctx_memo_stats(void *ctx, unsigned *hits, unsigned *misses) {
   return 0;
 }
 
+// The static per-cell topology wva_ctx_tick stages from, five host int32
+// arrays of n_cells each (copied): the cell's server, its accelerator index,
+// the profile's maxBatchSize and atTokens, the server's batch override.
+extern "C" int wva_ctx_set_topology(void *ctx, const int *cell_server, const int *cell_acc_idx,
+                                    const int *perf_max_batch_cfg, const int *at_tokens,
+                                    const int *override_n) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr) return -1;
+  const size_t n = (size_t)c->n_cells;
+  if (n > 0 && (cell_server == nullptr || cell_acc_idx == nullptr ||
+                perf_max_batch_cfg == nullptr || at_tokens == nullptr || override_n == nullptr))
+    return -1;
+  for (size_t k = 0; k < n; ++k)
+    if (cell_server[k] < 0 || cell_server[k] >= c->n_srv) return -2;
+  if (c->topo == nullptr) {
+    c->topo = (int *)malloc((6 * n + 1) * sizeof(int));
+    if (c->topo == nullptr) return -3;
+  }
+  const int *src[5] = {cell_server, cell_acc_idx, perf_max_batch_cfg, at_tokens, override_n};
+  for (int r = 0; r < 5; ++r)
+    if (n > 0) memcpy(c->topo + r * n, src[r], n * sizeof(int));
+  c->topo_cell_server = c->topo + 0 * n;
+  c->topo_cell_acc = c->topo + 1 * n;
+  c->topo_cfg = c->topo + 2 * n;
+  c->topo_at_tokens = c->topo + 3 * n;
+  c->topo_override = c->topo + 4 * n;
+  c->bucket_batch_n = c->topo + 5 * n;
+  c->bucket_batch_valid = 0;
+  return 0;
+}
+
+// batch_n (may be null): the host batch_n row [n_cells] the layout was chosen
+// for. It is recorded; wva_ctx_tick reports a stale layout when a tick's
+// batch_n differs from it (or when none was recorded).
 extern "C" int wva_ctx_set_buckets(void *ctx, int n_buckets, const int *nts,
                                    const void **cell_ids, const int *n_blocks,
                                    const int *max_ns, int analyzer_mode, float cv2,
-                                   const void **g_invs, const void **g_anchors) {
+                                   const void **g_invs, const void **g_anchors,
+                                   const int *batch_n) {
   WvaCtx *c = (WvaCtx *)ctx;
   if (n_buckets < 0 || n_buckets > WVA_MAX_BUCKETS) return -1;
+  c->bucket_batch_valid = 0;
+  if (batch_n != nullptr && c->topo != nullptr) {
+    if (c->n_cells > 0) memcpy(c->bucket_batch_n, batch_n, (size_t)c->n_cells * sizeof(int));
+    c->bucket_batch_valid = 1;
+  }
   c->n_buckets = n_buckets;
   for (int i = 0; i < n_buckets; ++i) {
     c->buckets[i].nt = nts[i];
@@ -2060,11 +2150,8 @@ static int wva_launch_bucket_on(WvaCtx *c, const WvaBucket &b, hipStream_t s) {
 // eager execution and for stream capture into a hipGraph)
 static int wva_enqueue_pipeline(WvaCtx *c) {
   hipError_t err;
-  // 1. dynamic H2D (pinned -> device)
-  err = hipMemcpyAsync(c->dev_i, c->pin_i, (size_t)6 * c->n_cells * sizeof(int),
-                       hipMemcpyHostToDevice, c->s0);
-  if (err != hipSuccess) return (int)err;
-  err = hipMemcpyAsync(c->dev_f, c->pin_f, (size_t)2 * c->n_cells * sizeof(float),
+  // 1. dynamic H2D (pinned -> device), the whole block in one copy
+  err = hipMemcpyAsync(c->dev_dyn, c->pin_dyn, (size_t)WVA_DYN_ROWS * c->n_cells * 4,
                        hipMemcpyHostToDevice, c->s0);
   if (err != hipSuccess) return (int)err;
   if (hipEventRecord(c->e_up, c->s0) != hipSuccess) return -10;
@@ -2081,24 +2168,46 @@ static int wva_enqueue_pipeline(WvaCtx *c) {
   for (int i = 1; i < c->n_buckets; ++i)
     if (hipStreamWaitEvent(c->s0, c->e_b[i - 1], 0) != hipSuccess) return -14;
 
-  // 3. argmin + gather on s0
-  hipLaunchKernelGGL(wva_argmin, dim3(c->n_srv), dim3(WVA_WAVE), 0, c->s0, c->out.value,
-                     c->out.feasible, c->seg_start, c->n_srv, c->winner);
-  hipLaunchKernelGGL(wva_gather, dim3((c->n_srv + 255) / 256), dim3(256), 0, c->s0, c->winner,
-                     c->out.zero_empty, c->cell_acc, c->out.num_replicas, c->out.batch,
-                     c->out.cost, c->out.value, c->out.itl, c->out.ttft, c->out.rho,
-                     c->out.max_rate, c->n_srv, c->gather_f, c->gather_i);
+  // 3. winner selection + winner records on s0, one launch
+  hipLaunchKernelGGL(wva_winner, dim3(c->n_srv), dim3(WVA_WAVE), 0, c->s0, c->out.value,
+                     c->out.feasible, c->out.zero_empty, c->cell_acc, c->out.num_replicas,
+                     c->out.batch, c->out.cost, c->out.itl, c->out.ttft, c->out.rho,
+                     c->out.max_rate, c->seg_start, c->n_srv, c->gather, c->winner);
   err = hipGetLastError();
   if (err != hipSuccess) return (int)err;
 
-  // 4. D2H of the winner records
-  err = hipMemcpyAsync(c->pin_out_f, c->gather_f, (size_t)6 * c->n_srv * sizeof(float),
-                       hipMemcpyDeviceToHost, c->s0);
-  if (err != hipSuccess) return (int)err;
-  err = hipMemcpyAsync(c->pin_out_i, c->gather_i, (size_t)4 * c->n_srv * sizeof(int),
+  // 4. D2H of the winner records, one copy
+  err = hipMemcpyAsync(c->pin_out, c->gather, (size_t)WVA_REC_ROWS * c->n_srv * 4,
                        hipMemcpyDeviceToHost, c->s0);
   if (err != hipSuccess) return (int)err;
   return 0;
+}
+
+// One reconcile tick behind one call: stage the six per-server arrays
+// ([n_srv] each; cur_acc -3 none, -1 empty, >= 0 accelerator index) into the
+// pinned dynamic block, then
+//   launch != 0: if the tick's batch_n equals the row the bucket layout was
+//     set for, run the pipeline and synchronise (returns 0, or a negative /
+//     HIP error code); otherwise launch nothing and return WVA_TICK_STALE.
+//     The caller then reads batch_n from the pinned block, calls
+//     wva_ctx_set_buckets and wva_reconcile, which runs the staged tick.
+//   launch == 0: stage only (the planning passes); returns 0 or
+//     WVA_TICK_STALE by the same comparison.
+// zero_arrival (may be null) replaces arrival in the zero-load decision.
+extern "C" int wva_reconcile(void *ctx);
+extern "C" int wva_ctx_tick(void *ctx, const float *arrival, const int *in_tok, const int *out_tok,
+                            const int *cur_acc, const int *cur_rep, const float *cur_cost,
+                            const float *zero_arrival, int launch) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || c->topo == nullptr) return -41;
+  int changed = 1;
+  const int rc = wva_stage_dynamic(
+      c->n_srv, c->n_cells, arrival, in_tok, out_tok, cur_acc, cur_rep, cur_cost, zero_arrival,
+      c->topo_cell_server, c->topo_cell_acc, c->topo_cfg, c->topo_at_tokens, c->topo_override,
+      c->pin_dyn, c->bucket_batch_valid ? c->bucket_batch_n : nullptr, &changed);
+  if (rc != 0) return -42;
+  if (changed) return WVA_TICK_STALE;
+  return launch ? wva_reconcile(ctx) : 0;
 }
 
 extern "C" int wva_reconcile(void *ctx) {
@@ -2200,7 +2309,7 @@ static int wva_plan_reserve(WvaCtx *c, int n_scen, int n_acc) {
   int prev_dev = -1, dev = -1;
   hipPointerAttribute_t attr;
   if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
-  if (hipPointerGetAttributes(&attr, c->dev_i) == hipSuccess) dev = attr.device;
+  if (hipPointerGetAttributes(&attr, c->dev_dyn) == hipSuccess) dev = attr.device;
   const bool switched = dev >= 0 && prev_dev >= 0 && dev != prev_dev &&
                         hipSetDevice(dev) == hipSuccess;
   void *d = nullptr, *h = nullptr;
@@ -2290,7 +2399,7 @@ static int wva_lim_reserve(WvaCtx *c, int n_scen, int n_types) {
   int prev_dev = -1, dev = -1;
   hipPointerAttribute_t attr;
   if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
-  if (hipPointerGetAttributes(&attr, c->dev_i) == hipSuccess) dev = attr.device;
+  if (hipPointerGetAttributes(&attr, c->dev_dyn) == hipSuccess) dev = attr.device;
   const bool switched = dev >= 0 && prev_dev >= 0 && dev != prev_dev &&
                         hipSetDevice(dev) == hipSuccess;
   void *d = nullptr, *h = nullptr;
@@ -2333,7 +2442,7 @@ extern "C" int wva_ctx_set_greedy_static(void *ctx, const int *cell_type, const 
     int prev_dev = -1, dev = -1;
     hipPointerAttribute_t attr;
     if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
-    if (hipPointerGetAttributes(&attr, c->dev_i) == hipSuccess) dev = attr.device;
+    if (hipPointerGetAttributes(&attr, c->dev_dyn) == hipSuccess) dev = attr.device;
     const bool switched = dev >= 0 && prev_dev >= 0 && dev != prev_dev &&
                           hipSetDevice(dev) == hipSuccess;
     void *d = nullptr;
@@ -2382,10 +2491,7 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   err = hipMemcpyAsync(c->plan_scen, c->plan_pin_scen, cells * sizeof(float),
                        hipMemcpyHostToDevice, c->s0);
   if (err != hipSuccess) return (int)err;
-  err = hipMemcpyAsync(c->dev_i, c->pin_i, (size_t)6 * c->n_cells * sizeof(int),
-                       hipMemcpyHostToDevice, c->s0);
-  if (err != hipSuccess) return (int)err;
-  err = hipMemcpyAsync(c->dev_f, c->pin_f, (size_t)2 * c->n_cells * sizeof(float),
+  err = hipMemcpyAsync(c->dev_dyn, c->pin_dyn, (size_t)WVA_DYN_ROWS * c->n_cells * 4,
                        hipMemcpyHostToDevice, c->s0);
   if (err != hipSuccess) return (int)err;
   err = hipMemsetAsync(c->plan_tot, 0, (size_t)n_scen * n_acc * sizeof(unsigned long long),
@@ -2537,5 +2643,6 @@ extern "C" void wva_ctx_destroy(void *ctx) {
   wva_plan_release(c);
   wva_lim_release(c);
   if (c->lim_static != nullptr) (void)hipFree(c->lim_static);
+  free(c->topo);
   delete c;
 }

@@ -158,9 +158,23 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
         ctypes.c_float,
         ctypes.POINTER(ctypes.c_void_p),  # per-bucket g_inv slabs (huge-N)
         ctypes.POINTER(ctypes.c_void_p),  # per-bucket g_anchor slabs
+        ctypes.c_void_p,  # host i32 [n_cells] batch_n the layout was chosen for
     ]
     lib.wva_reconcile.restype = ctypes.c_int
     lib.wva_reconcile.argtypes = [ctypes.c_void_p]
+    # the reconcile tick's native prologue (engine/fastpath.py)
+    lib.wva_ctx_set_topology.restype = ctypes.c_int
+    lib.wva_ctx_set_topology.argtypes = [ctypes.c_void_p] * 6
+    lib.wva_ctx_tick.restype = ctypes.c_int
+    lib.wva_ctx_tick.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_int]
+    # host-only staging and aggregation (ops/native/stage.cpp)
+    lib.wva_stage_dynamic.restype = ctypes.c_int
+    lib.wva_stage_dynamic.argtypes = (
+        [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 14
+        + [ctypes.POINTER(ctypes.c_int)]
+    )
+    lib.wva_aggregate_by_type.restype = ctypes.c_int
+    lib.wva_aggregate_by_type.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 9
     lib.wva_greedy_solve.restype = ctypes.c_int
     lib.wva_ctx_destroy.restype = None
     lib.wva_ctx_destroy.argtypes = [ctypes.c_void_p]
@@ -376,6 +390,90 @@ def run_greedy_native(cand_value, cand_acc_type, cand_units, cand_replicas,
     if rc != 0:
         raise HipKernelError(f"wva_greedy_solve failed: {rc}")
     return out_cand, out_reps
+
+
+# mirrors of ops/native/wva_stage.h: the tick code of wva_ctx_tick for "the
+# bucket layout does not fit the staged batch_n, nothing was launched"
+# (WVA_TICK_STALE) and the rows of the dynamic block (WVA_DYN_ROWS)
+TICK_STALE = 1 << 20
+DYN_ROWS = 8
+
+
+def run_stage_dynamic(arrival, in_tok, out_tok, cur_acc, cur_rep, cur_cost, cell_server,
+                      cell_acc_idx, perf_max_batch_cfg, at_tokens, override,
+                      zero_arrival=None, prev_batch_n=None, allow_build: bool = True):
+    """Host-only native staging (ops/native/stage.cpp; no GPU needed): the
+    six per-server arrays and the static per-cell topology -> the dynamic
+    block, an int32 array [8, n_cells] whose rows are in_tok, out_tok,
+    batch_n, perf_max_batch, cur_replicas, flags and the bit patterns of the
+    fp32 rows arrival_rate, cur_cost (``block[6:].view(np.float32)``).
+    ``zero_arrival`` replaces ``arrival`` in the zero-load decision.
+
+    Returns (block, changed): changed says whether batch_n differs from
+    ``prev_batch_n`` (always True when that is None)."""
+    import numpy as np
+
+    lib = load_library(allow_build=allow_build)
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
+    srv = [f32(arrival), i32(in_tok), i32(out_tok), i32(cur_acc), i32(cur_rep), f32(cur_cost)]
+    topo = [i32(cell_server), i32(cell_acc_idx), i32(perf_max_batch_cfg), i32(at_tokens),
+            i32(override)]
+    n_srv, n_cells = len(srv[0]), len(topo[0])
+    if any(len(a) != n_srv for a in srv) or any(len(a) != n_cells for a in topo):
+        raise ValueError("per-server / per-cell arrays differ in length")
+    zero = f32(zero_arrival) if zero_arrival is not None else None
+    prev = i32(prev_batch_n) if prev_batch_n is not None else None
+    if (zero is not None and len(zero) != n_srv) or (prev is not None and len(prev) != n_cells):
+        raise ValueError("zero_arrival / prev_batch_n have the wrong length")
+    block = np.empty((DYN_ROWS, n_cells), dtype=np.int32)
+    changed = ctypes.c_int(0)
+
+    def p(a):
+        return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+
+    rc = lib.wva_stage_dynamic(
+        n_srv, n_cells, *[p(a) for a in srv], p(zero), *[p(a) for a in topo], p(block),
+        p(prev), ctypes.byref(changed),
+    )
+    if rc != 0:
+        raise HipKernelError(f"wva_stage_dynamic failed: {rc}")
+    return block, bool(changed.value)
+
+
+def run_aggregate_by_type(acc_idx, num_replicas, cost, valid, inst, mult, type_idx,
+                          n_types: int, allow_build: bool = True):
+    """Host-only native by-type aggregation (ops/native/stage.cpp): unit
+    counts (int64 [n_types]) and fp64 cost sums of the winners with ``valid``
+    set and ``acc_idx >= 0``. Servers are added in ascending order, one fp64
+    add each — the order np.add.at uses — so the sums carry the same bits as
+    the numpy path of ShardedSolver._aggregate_by_type. The unit product
+    replicas * inst * mult is formed in int64 where numpy forms it in int32
+    and widens: the two differ only where that one silently overflowed."""
+    import numpy as np
+
+    lib = load_library(allow_build=allow_build)
+    acc_idx = np.ascontiguousarray(acc_idx, dtype=np.int32)
+    num_replicas = np.ascontiguousarray(num_replicas, dtype=np.int32)
+    cost = np.ascontiguousarray(cost, dtype=np.float32)
+    valid = np.ascontiguousarray(valid, dtype=np.bool_)
+    inst = np.ascontiguousarray(inst, dtype=np.int32)
+    mult = np.ascontiguousarray(mult, dtype=np.int32)
+    type_idx = np.ascontiguousarray(type_idx, dtype=np.int32)
+    n_srv, n_acc = len(acc_idx), len(mult)
+    if inst.shape != (n_srv, n_acc) or len(type_idx) != n_acc or not (
+            len(num_replicas) == len(cost) == len(valid) == n_srv):
+        raise ValueError("aggregation inputs differ in shape")
+    tcount = np.zeros(n_types, dtype=np.int64)
+    tcost = np.zeros(n_types, dtype=np.float64)
+    rc = lib.wva_aggregate_by_type(
+        n_srv, n_acc, n_types, acc_idx.ctypes.data, num_replicas.ctypes.data,
+        cost.ctypes.data, valid.ctypes.data, inst.ctypes.data, mult.ctypes.data,
+        type_idx.ctypes.data, tcount.ctypes.data, tcost.ctypes.data,
+    )
+    if rc != 0:
+        raise HipKernelError(f"wva_aggregate_by_type failed: {rc}")
+    return tcount, tcost
 
 
 def library_loaded() -> bool:

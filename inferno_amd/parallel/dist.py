@@ -112,6 +112,12 @@ class ShardedSolver:
         self._fast_key = None
         self._agg_key = None
         self._agg = None  # cached aggregation structures
+        # (agg, lib or None when the library is not loaded, count/cost outputs,
+        # pointers); decided once per aggregation structure, not per solve
+        self._agg_native = None
+        # True forces the encode -> all_gather-shaped record -> scatter path
+        # at world size 1 too (tests, A/B measurement of the shortcut)
+        self.force_generic_gather = False
 
     def invalidate(self) -> None:
         """Drop cached structures (fleet topology changed)."""
@@ -119,6 +125,7 @@ class ShardedSolver:
         self._fast_key = None
         self._agg_key = None
         self._agg = None
+        self._agg_native = None
 
     @property
     def fast_sweep(self) -> Optional[FastSweep]:
@@ -134,9 +141,6 @@ class ShardedSolver:
 
     # ------------------------------------------------------------------
     def solve(self, system: System, spec: OptimizerSpec) -> ShardResult:
-        import torch
-        import torch.distributed as dist
-
         initialized, rank, world = self._dist_info()
         all_names = sorted(system.servers)
         acc_names = sorted(system.accelerators)
@@ -146,6 +150,43 @@ class ShardedSolver:
             rec, stats = self._solve_fast(system, local_names)
         else:
             rec, stats = self._solve_slow(system, local_names, spec, acc_names)
+
+        if not (initialized and world > 1) and not self.force_generic_gather:
+            # world 1: the local shard is the fleet, in global order already,
+            # so the winner record is the global solution. The generic path
+            # below passes the int fields through fp32 records; the two differ
+            # only for |value| > 2^24, where that round trip was lossy.
+            winners = GlobalWinners(
+                names=all_names,
+                acc_names=acc_names,
+                acc_idx=np.asarray(rec.acc_idx, dtype=np.int32),
+                num_replicas=np.asarray(rec.num_replicas, dtype=np.int32),
+                batch=np.asarray(rec.batch, dtype=np.int32),
+                cost=np.asarray(rec.cost, dtype=np.float32),
+                itl=np.asarray(rec.itl, dtype=np.float32),
+                ttft=np.asarray(rec.ttft, dtype=np.float32),
+                valid=np.ones(len(all_names), dtype=bool),
+            )
+        else:
+            winners = self._gather_winners(rec, all_names, acc_names, local_names,
+                                           initialized, rank, world)
+
+        by_type = self._aggregate_by_type(system, all_names, acc_names, winners)
+        system.allocation_by_type = by_type
+        return ShardResult(
+            winners=winners,
+            allocation_by_type=by_type,
+            local_stats=stats,
+            _system=system,
+        )
+
+    def _gather_winners(self, rec, all_names, acc_names, local_names, initialized, rank,
+                        world) -> GlobalWinners:
+        """The generic path: encode the local winners as fixed-size fp32
+        records, all-gather them across ranks and scatter the rows back into
+        global order."""
+        import torch
+        import torch.distributed as dist
 
         # encode local winners into a fixed-size record tensor
         max_shard = (len(all_names) + world - 1) // world
@@ -195,15 +236,7 @@ class ShardedSolver:
         winners.itl[g] = rows[:, 5]
         winners.ttft[g] = rows[:, 6]
         winners.valid[g] = True
-
-        by_type = self._aggregate_by_type(system, all_names, acc_names, winners)
-        system.allocation_by_type = by_type
-        return ShardResult(
-            winners=winners,
-            allocation_by_type=by_type,
-            local_stats=stats,
-            _system=system,
-        )
+        return winners
 
     # ------------------------------------------------------------------
     def _aggregate_by_type(self, system, all_names, acc_names, winners):
@@ -228,18 +261,50 @@ class ShardedSolver:
             self._agg_key = key
         inst, mult, types, uniq_types, type_idx = self._agg
 
-        sel = winners.valid & (winners.acc_idx >= 0)
-        idx = np.nonzero(sel)[0]
         by_type: dict[str, AllocationByType] = {}
-        if len(idx):
-            codes = winners.acc_idx[idx]
-            counts = (
-                winners.num_replicas[idx] * inst[idx, codes] * mult[codes]
-            ).astype(np.int64)
-            tcount = np.zeros(len(uniq_types), dtype=np.int64)
-            tcost = np.zeros(len(uniq_types), dtype=np.float64)
-            np.add.at(tcount, type_idx[codes], counts)
-            np.add.at(tcost, type_idx[codes], winners.cost[idx].astype(np.float64))
+        tcount = tcost = None
+        from ..ops import sweep as _ops
+
+        nat = self._agg_native
+        if nat is None or nat[0] is not self._agg:
+            if _ops.library_loaded():
+                tcount = np.zeros(len(uniq_types), dtype=np.int64)
+                tcost = np.zeros(len(uniq_types), dtype=np.float64)
+                nat = (
+                    self._agg, _ops.load_library(allow_build=False), tcount, tcost,
+                    (inst.ctypes.data, mult.ctypes.data, type_idx.ctypes.data,
+                     tcount.ctypes.data, tcost.ctypes.data),
+                )
+            else:
+                nat = (self._agg, None, None, None, None)
+            self._agg_native = nat
+        if nat[1] is not None:
+            # native loop (ops/native/stage.cpp): same order of fp64 adds.
+            # See run_aggregate_by_type for the one difference (int64 units).
+            _, lib, tcount, tcost, ptrs = nat
+            w_acc = np.ascontiguousarray(winners.acc_idx, dtype=np.int32)
+            w_rep = np.ascontiguousarray(winners.num_replicas, dtype=np.int32)
+            w_cost = np.ascontiguousarray(winners.cost, dtype=np.float32)
+            w_valid = np.ascontiguousarray(winners.valid, dtype=np.bool_)
+            rc = lib.wva_aggregate_by_type(
+                len(all_names), len(acc_names), len(uniq_types), w_acc.ctypes.data,
+                w_rep.ctypes.data, w_cost.ctypes.data, w_valid.ctypes.data, *ptrs,
+            )
+            if rc != 0:
+                raise _ops.HipKernelError(f"wva_aggregate_by_type failed: {rc}")
+        else:
+            sel = winners.valid & (winners.acc_idx >= 0)
+            idx = np.nonzero(sel)[0]
+            if len(idx):
+                codes = winners.acc_idx[idx]
+                counts = (
+                    winners.num_replicas[idx] * inst[idx, codes] * mult[codes]
+                ).astype(np.int64)
+                tcount = np.zeros(len(uniq_types), dtype=np.int64)
+                tcost = np.zeros(len(uniq_types), dtype=np.float64)
+                np.add.at(tcount, type_idx[codes], counts)
+                np.add.at(tcost, type_idx[codes], winners.cost[idx].astype(np.float64))
+        if tcount is not None:
             for k, t in enumerate(uniq_types):
                 if tcount[k] == 0 and tcost[k] == 0.0:
                     continue

@@ -24,15 +24,15 @@ rows = []
 for step in range(38):
     t0 = time.perf_counter()
     fs.load_override = (pre[step].astype(np.float32), in_t, out_t)
-    arrs = fs._refresh_dynamic()
+    fs._tick(launch=False)  # host staging (+ bucket layout when it went stale)
     t1 = time.perf_counter()
-    fs._native_reconcile(arrs)
+    fs._tick()  # stages again (microseconds) and runs the device pipeline
     torch.cuda.synchronize()
     t2 = time.perf_counter()
-    of = fs._gpu["pin_out_f"].numpy(); oi = fs._gpu["pin_out_i"].numpy()
-    w = (oi[0].copy(), of[0].copy())
+    of, oi = fs._winner_block()
+    w = (oi[0], of[0])
     t3 = time.perf_counter()
     nz = int((pre[step] > 0).sum())
     rows.append((step, (t1-t0)*1e3, (t2-t1)*1e3, (t3-t2)*1e3, nz))
 for r in rows:
-    print(f"step {r[0]:2d} refresh {r[1]:7.2f} ms  gpu {r[2]:7.2f} ms  out {r[3]:5.2f} ms  nonzero {r[4]}")
+    print(f"step {r[0]:2d} stage {r[1]:7.2f} ms  gpu {r[2]:7.2f} ms  out {r[3]:5.2f} ms  nonzero {r[4]}")
