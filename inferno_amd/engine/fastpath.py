@@ -15,16 +15,25 @@ Per reconcile it uploads the refreshed SoA, launches wva_sweep + wva_winner,
 and materializes ONLY the per-server winner records (not all candidate
 cells). The slow path (SweepEngine) remains the oracle and serves greedy
 limited mode, which needs the full candidate lists.
+
+FastSweep is the fleet model, the public API with its input validation, and
+the CPU golden paths; the device buffers, the native context and the ctypes
+calls belong to NativeCtx (engine/native_ctx.py), held as ``_gpu``.
 """
 from __future__ import annotations
 
+import contextlib
+import os
 from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
 
+from ..config import SaturationPolicy
 from ..core import create_allocation
 from ..core.system import System
+from ..ops.sweep import PLAN_MAX_S, run_greedy_native
+from .native_ctx import NativeCtx
 from .snapshot import FLAG_CUR_EMPTY, FLAG_CUR_SAME, FLAG_HAS_CUR
 
 _INT_KEYS = ("in_tok", "out_tok", "batch_n", "min_replicas", "perf_max_batch",
@@ -349,175 +358,12 @@ class FastSweep:
             return self._reconcile_gpu()
         return self._reconcile_cpu()
 
-    # GPU persistent-state reconcile: static SoA uploaded once; per step the
-    # native library expands the per-server state into ONE pinned dynamic
-    # block (the _DYN_INT rows, then _DYN_F32) -> one H2D copy; the bucket
-    # layout is kept until the staged batch_n differs from the one it was
-    # chosen for; outputs preallocated; winner records selected and gathered
-    # ON-DEVICE in one launch and downloaded in a single D2H copy.
-    _DYN_INT = ("in_tok", "out_tok", "batch_n", "perf_max_batch", "cur_replicas", "flags")
-    _DYN_F32 = ("arrival_rate", "cur_cost")
-    _STAT_F32 = ("alpha", "beta", "gamma", "delta", "t_itl", "t_ttft", "t_tps", "acc_cost")
-
-    def _init_gpu_state(self) -> None:
-        import torch
-
-        from ..ops.sweep import load_library
-
-        load_library(allow_build=False)
-        dev = self.device
-        n = self.n_cells
-        st: dict = {}
-        for k in self._STAT_F32:
-            st[k] = torch.from_numpy(np.ascontiguousarray(self._stat[k])).to(dev)
-        st["min_replicas"] = torch.from_numpy(
-            np.ascontiguousarray(self._stat["min_replicas"], dtype=np.int32)
-        ).to(dev)
-        # the dynamic block: 4-byte words, int32 rows then fp32 rows
-        n_dyn = len(self._DYN_INT) + len(self._DYN_F32)
-        st["pin_dyn"] = torch.empty((n_dyn, n), dtype=torch.int32, pin_memory=True)
-        st["dev_dyn"] = torch.empty((n_dyn, n), dtype=torch.int32, device=dev)
-        st["pin_dyn_np"] = st["pin_dyn"].numpy()
-        st["seg"] = torch.from_numpy(self.seg_start).to(dev)
-        st["cell_acc"] = torch.from_numpy(self.cell_acc_idx).to(dev)
-        # outputs
-        st["feasible"] = torch.zeros(n, dtype=torch.uint8, device=dev)
-        st["zero_empty"] = torch.zeros(n, dtype=torch.uint8, device=dev)
-        st["num_replicas"] = torch.zeros(n, dtype=torch.int32, device=dev)
-        st["batch"] = torch.zeros(n, dtype=torch.int32, device=dev)
-        for k in ("cost", "value", "itl", "ttft", "rho", "max_rate"):
-            st[k] = torch.zeros(n, dtype=torch.float32, device=dev)
-        n_srv = len(self.server_names)
-        st["winner"] = torch.full((n_srv,), -1, dtype=torch.int32, device=dev)
-        # winner records: six fp32 rows (cost, value, itl, ttft, rho, max_rate)
-        # then four int32 rows (acc code, num_replicas, batch, winner cell)
-        st["gather"] = torch.empty((10, n_srv), dtype=torch.int32, device=dev)
-        st["pin_out"] = torch.empty((10, n_srv), dtype=torch.int32, pin_memory=True)
-        st["pin_out_np"] = st["pin_out"].numpy()
-        st["tick_stale"] = False  # did the last tick find the bucket layout stale
-        st["stale_ticks"] = 0
-        st["bucket_key"] = None
-        st["buckets"] = []
-        self._gpu = st
-
-    def _buckets_for(self, batch_n: np.ndarray):
-        import torch
-
-        from ..ops.sweep import alloc_gmem_slabs, choose_buckets
-
-        st = self._gpu
-        key = batch_n.tobytes()
-        if st["bucket_key"] == key:
-            return st["buckets"]
-        buckets = []
-        for nt, ids, bmax, count, gmem in choose_buckets(batch_n):
-            ids_t = torch.from_numpy(ids).to(self.device) if ids is not None else None
-            slabs = (
-                alloc_gmem_slabs(count, bmax, nt, self.device) if gmem else (None, None)
-            )
-            buckets.append((nt, ids_t, bmax, count, slabs))
-        st["bucket_key"] = key
-        st["buckets"] = buckets
-        return buckets
-
-    def _ensure_ctx(self) -> None:
-        """Create the native reconcile context (opaque C struct owning the
-        HIP streams/events and all registered device/pinned pointers) —
-        the whole per-tick pipeline then runs behind ONE C call."""
-        import ctypes
-
-        from ..ops.sweep import load_library
-
-        st = self._gpu
-        if "ctx" in st:
-            return
-        lib = load_library(allow_build=False)
-        # slot order: see WVA_CTX_SLOTS in ops/hip/wva_kernels.hip
-        slots = [
-            st["dev_dyn"],
-            st["min_replicas"],
-            st["alpha"], st["beta"], st["gamma"], st["delta"],
-            st["t_itl"], st["t_ttft"], st["t_tps"], st["acc_cost"],
-            st["feasible"], st["zero_empty"], st["num_replicas"], st["batch"],
-            st["cost"], st["value"], st["itl"], st["ttft"], st["rho"],
-            st["max_rate"],
-            st["seg"], st["winner"], st["cell_acc"], st["gather"],
-            st["pin_dyn"], st["pin_out"],
-        ]
-        arr = (ctypes.c_void_p * len(slots))(
-            *[ctypes.c_void_p(t.data_ptr()) for t in slots]
-        )
-        ctx = lib.wva_ctx_create(
-            ctypes.c_int(self.n_cells), ctypes.c_int(len(self.server_names)), arr
-        )
-        if not ctx:
-            from ..ops.sweep import HipKernelError
-
-            raise HipKernelError("wva_ctx_create failed")
-        st["ctx"] = ctx
-        st["ctx_lib"] = lib
-        # the static topology the native tick stages from (copied by the ctx)
-        topo = [
-            np.ascontiguousarray(a, dtype=np.int32)
-            for a in (self.cell_server, self.cell_acc_idx, self._stat["perf_max_batch_cfg"],
-                      self._stat["at_tokens"], self._stat["override"])
-        ]
-        rc = lib.wva_ctx_set_topology(ctx, *[a.ctypes.data for a in topo])
-        if rc != 0:
-            from ..ops.sweep import HipKernelError
-
-            raise HipKernelError(f"wva_ctx_set_topology failed: {rc}")
-
-    def __del__(self):  # release the native context's streams/events
-        st = getattr(self, "_gpu", None)
-        if st and "ctx" in st:
-            try:
-                st["ctx_lib"].wva_ctx_destroy(st.pop("ctx"))
-            except Exception:
-                pass
-
-    def _sync_buckets(self, batch_n: np.ndarray, force: bool = False) -> None:
-        """Push the bucket layout + analyzer mode into the native context,
-        together with the batch_n it was chosen for (only when it changed,
-        or when the context itself reported its layout stale)."""
-        import ctypes
-
-        st = self._gpu
-        buckets = self._buckets_for(batch_n)
-        if not force and st.get("ctx_buckets_key") == st["bucket_key"]:
-            return
-        n = len(buckets)
-        nts = (ctypes.c_int * n)(*[b[0] for b in buckets])
-        ids = (ctypes.c_void_p * n)(
-            *[ctypes.c_void_p(b[1].data_ptr()) if b[1] is not None else None
-              for b in buckets]
-        )
-        nbl = (ctypes.c_int * n)(
-            *[int(b[1].numel()) if b[1] is not None else self.n_cells for b in buckets]
-        )
-        mxn = (ctypes.c_int * n)(*[b[2] for b in buckets])
-        g_invs = (ctypes.c_void_p * n)(
-            *[ctypes.c_void_p(b[4][0].data_ptr()) if b[4][0] is not None else None
-              for b in buckets]
-        )
-        g_anchors = (ctypes.c_void_p * n)(
-            *[ctypes.c_void_p(b[4][1].data_ptr()) if b[4][1] is not None else None
-              for b in buckets]
-        )
-        mode = 1 if getattr(self.system, "analyzer_mode", "mm1k") == "mg1" else 0
-        cv2 = float(getattr(self.system, "analyzer_cv2", 1.0))
-        batch_n = np.ascontiguousarray(batch_n, dtype=np.int32)
-        rc = st["ctx_lib"].wva_ctx_set_buckets(
-            st["ctx"], ctypes.c_int(n), nts, ids, nbl, mxn,
-            ctypes.c_int(mode), ctypes.c_float(cv2), g_invs, g_anchors,
-            batch_n.ctypes.data,
-        )
-        if rc != 0:
-            from ..ops.sweep import HipKernelError
-
-            raise HipKernelError(f"wva_ctx_set_buckets failed: {rc}")
-        st["ctx_buckets_key"] = st["bucket_key"]
-
+    # GPU persistent-state reconcile (NativeCtx): static SoA uploaded once; per
+    # step the native library expands the per-server state into ONE pinned
+    # dynamic block -> one H2D copy; the bucket layout is kept until the staged
+    # batch_n differs from the one it was chosen for; outputs preallocated;
+    # winner records selected and gathered ON-DEVICE in one launch and
+    # downloaded in a single D2H copy.
     def _tick(self, plan_arrival: Optional[np.ndarray] = None, launch: bool = True) -> None:
         """One native tick (wva_ctx_tick): the library expands the six
         per-server arrays into the pinned dynamic block — what
@@ -528,11 +374,12 @@ class FastSweep:
         before and the already staged tick resumed (wva_reconcile).
 
         ``plan_arrival`` as in _refresh_dynamic; the planning passes stage
-        with ``launch=False`` and run their own pipeline afterwards."""
-        from ..ops.sweep import TICK_STALE, HipKernelError
-
-        st = self._gpu
-        self._ensure_ctx()
+        with ``launch=False`` and run their own pipeline afterwards. The
+        device state is set up on the first call."""
+        g = getattr(self, "_gpu", None)
+        if g is None:
+            g = self._gpu = NativeCtx(len(self.server_names), self._stat, self.cell_server,
+                                      self.cell_acc_idx, self.seg_start, self.device)
         arrival, in_tok, out_tok = self._base_load()
         zero = None
         if plan_arrival is not None:
@@ -551,47 +398,30 @@ class FastSweep:
                 raise ValueError(
                     f"per-server override has shape {a.shape}, expected ({n_srv},)"
                 )
-        lib = st["ctx_lib"]
-        rc = lib.wva_ctx_tick(
-            st["ctx"], srv[0].ctypes.data, srv[1].ctypes.data, srv[2].ctypes.data,
-            srv[3].ctypes.data, srv[4].ctypes.data, srv[5].ctypes.data,
-            zero.ctypes.data if zero is not None else None, 1 if launch else 0,
-        )
-        st["tick_stale"] = rc == TICK_STALE
-        if rc == TICK_STALE:
-            st["stale_ticks"] += 1
-            batch_n = st["pin_dyn_np"][self._DYN_INT.index("batch_n")].copy()
-            self._sync_buckets(batch_n, force=True)
-            rc = lib.wva_reconcile(st["ctx"]) if launch else 0
-        if rc != 0:
-            raise HipKernelError(f"native reconcile tick failed: {rc}")
+        if g.tick(srv, zero, launch):  # layout stale: staged, nothing launched
+            mode = 1 if getattr(self.system, "analyzer_mode", "mm1k") == "mg1" else 0
+            cv2 = float(getattr(self.system, "analyzer_cv2", 1.0))
+            g.sync_buckets(g.staged_batch_n(), mode, cv2)
+            if launch:
+                g.resume()
 
     def _winner_block(self) -> tuple[np.ndarray, np.ndarray]:
         """The last tick's winner records, copied out of the pinned block:
         (fp32 [6, n_srv], int32 [4, n_srv])."""
-        blk = self._gpu["pin_out_np"].copy()
-        return blk[:6].view(np.float32), blk[6:]
+        return self._gpu.winner_block()
 
     def memo_stats(self) -> Optional[tuple[int, int]]:
         """(hits, misses) of the native context's sizing memo since the
         context was created, or None when there is no context yet or the
         memo is off (INFERNO_SIZING_MEMO=0). Synchronous; diagnostics only."""
-        import ctypes
+        g = getattr(self, "_gpu", None)
+        return g.memo_stats() if g is not None else None
 
-        st = getattr(self, "_gpu", None)
-        if not st or "ctx" not in st:
-            return None
-        hits, misses = ctypes.c_uint(0), ctypes.c_uint(0)
-        rc = st["ctx_lib"].wva_ctx_memo_stats(
-            st["ctx"], ctypes.byref(hits), ctypes.byref(misses)
-        )
-        if rc < 0:
-            from ..ops.sweep import HipKernelError
-
-            raise HipKernelError(f"wva_ctx_memo_stats failed: {rc}")
-        if rc != 0:
-            return None
-        return int(hits.value), int(misses.value)
+    def _with_cell_meta(self, cells: dict) -> dict:
+        cells["cell_server"] = self.cell_server
+        cells["cell_acc_idx"] = self.cell_acc_idx
+        cells["seg_start"] = self.seg_start
+        return cells
 
     def reconcile_cells(self) -> Optional[dict]:
         """Run the sweep and return PER-CELL output arrays (numpy) plus the
@@ -600,39 +430,14 @@ class FastSweep:
         None on CPU (the slow engine path covers it)."""
         if self.backend != "gpu" or self.n_cells == 0:
             return None
-        if not hasattr(self, "_gpu"):
-            self._init_gpu_state()
-        st = self._gpu
         self._tick()  # fully synced on return
-        out = {
-            k: st[k].cpu().numpy()
-            for k in ("feasible", "zero_empty", "num_replicas", "batch", "cost",
-                      "value", "itl", "ttft", "rho", "max_rate")
-        }
-        out["cell_server"] = self.cell_server
-        out["cell_acc_idx"] = self.cell_acc_idx
-        out["seg_start"] = self.seg_start
-        return out
+        return self._with_cell_meta(self._gpu.cells())
 
     def _reconcile_gpu(self) -> WinnerRecord:
-        n_srv = len(self.server_names)
         if self.n_cells == 0:
-            return _empty_winner(n_srv)
-        if not hasattr(self, "_gpu"):
-            self._init_gpu_state()
+            return _empty_winner(len(self.server_names))
         self._tick()
-        of, oi = self._winner_block()  # one copy; the rows are views of it
-        return WinnerRecord(
-            acc_idx=oi[0],
-            num_replicas=oi[1],
-            batch=oi[2],
-            cost=of[0],
-            value=of[1],
-            itl=of[2],
-            ttft=of[3],
-            rho=of[4],
-            max_rate=of[5],
-        )
+        return _winner_record(*self._gpu.winner_block())  # one copy; the rows are views of it
 
     # ------------------------------------------------------------------
     # What-if load planning
@@ -675,18 +480,23 @@ class FastSweep:
             winners, totals, cells = self._plan_gpu(scen, return_cells)
         else:
             winners, totals, cells = self._plan_cpu(scen), None, None
-        n_acc = len(self.acc_names)
+        return self._plan_result(scen, winners, totals, cells)
+
+    def _plan_result(self, scen, winners: WinnerRecord, totals, cells, **limited) -> PlanResult:
+        """The PlanResult of a solved plan; ``totals`` None = count the
+        winners' replicas here. ``limited``: the limited-mode fields."""
+        n_scen = scen.shape[0]
         has = winners.acc_idx != -1
         if totals is None:
-            totals = np.zeros((scen.shape[0], n_acc), dtype=np.int64)
-            for s in range(scen.shape[0]):
+            totals = np.zeros((n_scen, len(self.acc_names)), dtype=np.int64)
+            for s in range(n_scen):
                 on = winners.acc_idx[s] >= 0
                 np.add.at(totals[s], winners.acc_idx[s][on],
                           winners.num_replicas[s][on].astype(np.int64))
         # fp64 sum of the fp32 costs in server order (the device keeps no
         # fp32 running total: its order of additions would not be fixed)
         cost_total = np.array(
-            [winners.cost[s][has[s]].astype(np.float64).sum() for s in range(scen.shape[0])],
+            [winners.cost[s][has[s]].astype(np.float64).sum() for s in range(n_scen)],
             dtype=np.float64,
         )
         return PlanResult(
@@ -696,12 +506,11 @@ class FastSweep:
             infeasible_servers=(~has).sum(axis=1).astype(np.int64),
             arrival=scen,
             cells=cells,
+            **limited,
         )
 
     def _plan_scenarios(self, scales, arrival) -> np.ndarray:
         """Validate plan()'s input and return the [S, n_servers] fp32 rates."""
-        from ..ops.sweep import PLAN_MAX_S
-
         if (scales is None) == (arrival is None):
             raise ValueError("plan() takes exactly one of scales and arrival")
         n_srv = len(self.server_names)
@@ -739,69 +548,19 @@ class FastSweep:
         return scen
 
     def _plan_gpu(self, scen: np.ndarray, return_cells: bool):
-        import ctypes
-
-        from ..ops.sweep import HipKernelError
-
         n_scen, n_srv = scen.shape
         n_acc = len(self.acc_names)
         if self.n_cells == 0 or n_acc == 0:
-            w = _empty_winner(n_srv)
-            winners = WinnerRecord(**{
-                f: np.repeat(getattr(w, f)[None, :], n_scen, axis=0) for f in _WINNER_FIELDS
-            })
-            return winners, np.zeros((n_scen, n_acc), dtype=np.int64), None
-        if not hasattr(self, "_gpu"):
-            self._init_gpu_state()
-        st = self._gpu
+            return _empty_winners(n_scen, n_srv), np.zeros((n_scen, n_acc), dtype=np.int64), None
         self._tick(plan_arrival=scen, launch=False)  # stage + bucket layout
         cell_scen = np.ascontiguousarray(scen[:, self.cell_server], dtype=np.float32)
-        p_f, p_i, p_t = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-        rc = st["ctx_lib"].wva_ctx_plan(
-            st["ctx"], ctypes.c_int(n_scen), ctypes.c_int(n_acc),
-            cell_scen.ctypes.data_as(ctypes.c_void_p),
-            ctypes.byref(p_f), ctypes.byref(p_i), ctypes.byref(p_t),
-        )
-        if rc != 0:
-            raise HipKernelError(f"wva_ctx_plan failed: {rc}")
-
-        def view(ptr, ctype, shape):
-            n = int(np.prod(shape))
-            buf = (ctype * n).from_address(ptr.value)
-            return np.ctypeslib.as_array(buf).reshape(shape).copy()
-
-        of = view(p_f, ctypes.c_float, (n_scen, 6, n_srv))
-        oi = view(p_i, ctypes.c_int32, (n_scen, 4, n_srv))
-        totals = view(p_t, ctypes.c_uint64, (n_scen, n_acc)).astype(np.int64)
-        winners = WinnerRecord(
-            acc_idx=oi[:, 0].copy(), num_replicas=oi[:, 1].copy(), batch=oi[:, 2].copy(),
-            cost=of[:, 0].copy(), value=of[:, 1].copy(), itl=of[:, 2].copy(),
-            ttft=of[:, 3].copy(), rho=of[:, 4].copy(), max_rate=of[:, 5].copy(),
-        )
+        of, oi, totals = self._gpu.plan(cell_scen, n_acc)
         cells = self._plan_cells_gpu(n_scen) if return_cells else None
-        return winners, totals, cells
+        return _winner_record(of, oi), totals, cells
 
     def _plan_cells_gpu(self, n_scen: int) -> dict:
         """Per-cell outputs of the planning pass that just ran."""
-        import ctypes
-
-        from ..ops.sweep import HipKernelError
-
-        st = self._gpu
-        keys = ("feasible", "zero_empty", "num_replicas", "batch", "cost", "value",
-                "itl", "ttft", "rho", "max_rate")
-        dtypes = (np.uint8, np.uint8, np.int32, np.int32) + (np.float32,) * 6
-        cells = {k: np.empty((n_scen, self.n_cells), dtype=d) for k, d in zip(keys, dtypes)}
-        dst = (ctypes.c_void_p * len(keys))(
-            *[cells[k].ctypes.data_as(ctypes.c_void_p) for k in keys]
-        )
-        rc = st["ctx_lib"].wva_ctx_plan_cells(st["ctx"], dst)
-        if rc != 0:
-            raise HipKernelError(f"wva_ctx_plan_cells failed: {rc}")
-        cells["cell_server"] = self.cell_server
-        cells["cell_acc_idx"] = self.cell_acc_idx
-        cells["seg_start"] = self.seg_start
-        return cells
+        return self._with_cell_meta(self._gpu.plan_cells(n_scen))
 
     # ------------------------------------------------------------------
     # Capacity-limited planning
@@ -838,23 +597,14 @@ class FastSweep:
         return np.ascontiguousarray(vals, dtype=np.int32)
 
     def _plan_limited(self, scen, capacity, saturation_policy, delayed, return_cells):
-        import os
-
-        from ..config import SaturationPolicy
-
         n_scen, n_srv = scen.shape
         cap = self._plan_capacity(capacity, n_scen)
         policy = _POLICY_CODE[SaturationPolicy.parse(saturation_policy).value]
         delayed = bool(delayed)
-        n_acc = len(self.acc_names)
         cells = None
-        if self.n_cells == 0 or n_acc == 0:
-            w = _empty_winner(n_srv)
-            winners = WinnerRecord(**{
-                f: np.repeat(getattr(w, f)[None, :], n_scen, axis=0) for f in _WINNER_FIELDS
-            })
+        if self.n_cells == 0 or not self.acc_names:
             zeros = np.zeros((n_scen, n_srv), dtype=np.int32)
-            sol = (winners, None, zeros, zeros.copy(), cap.astype(np.int64))
+            sol = (_empty_winners(n_scen, n_srv), None, zeros, zeros.copy(), cap.astype(np.int64))
         elif self.backend == "gpu":
             mode = os.environ.get("INFERNO_PLAN_GREEDY", "") or PLAN_GREEDY_DEFAULT
             if mode not in ("host", "device"):
@@ -874,24 +624,9 @@ class FastSweep:
             sol = self._plan_limited_cpu(scen, cap, saturation_policy, delayed)
         winners, totals, desired, n_cand, cap_left = sol
         has = winners.acc_idx != -1
-        if totals is None:
-            totals = np.zeros((n_scen, n_acc), dtype=np.int64)
-            for s in range(n_scen):
-                on = winners.acc_idx[s] >= 0
-                np.add.at(totals[s], winners.acc_idx[s][on],
-                          winners.num_replicas[s][on].astype(np.int64))
-        cost_total = np.array(
-            [winners.cost[s][has[s]].astype(np.float64).sum() for s in range(n_scen)],
-            dtype=np.float64,
-        )
         granted = winners.num_replicas
-        return PlanResult(
-            winners=winners,
-            replicas_by_acc=totals,
-            cost_total=cost_total,
-            infeasible_servers=(~has).sum(axis=1).astype(np.int64),
-            arrival=scen,
-            cells=cells,
+        return self._plan_result(
+            scen, winners, totals, cells,
             desired_replicas=desired,
             unallocated_servers=((n_cand > 0) & ~has).sum(axis=1).astype(np.int64),
             partial_servers=((granted > 0) & (granted < desired)).sum(axis=1).astype(np.int64),
@@ -899,76 +634,19 @@ class FastSweep:
             capacity_types=self.capacity_types,
         )
 
-    def _sync_greedy_static(self) -> None:
-        """Upload the static greedy inputs into the native context (only when
-        they changed)."""
-        import ctypes
-
-        from ..ops.sweep import HipKernelError
-
-        st = self._gpu
-        _, cell_tidx, units, prio = self.greedy_static()
-        arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in (cell_tidx, units, prio)]
-        key = b"".join(a.tobytes() for a in arrs)
-        if st.get("greedy_static_key") == key:
-            return
-        rc = st["ctx_lib"].wva_ctx_set_greedy_static(
-            st["ctx"], *[a.ctypes.data_as(ctypes.c_void_p) for a in arrs]
-        )
-        if rc != 0:
-            raise HipKernelError(f"wva_ctx_set_greedy_static failed: {rc}")
-        st["greedy_static_key"] = key
-
     def _plan_limited_device(self, scen, cap, policy: int, delayed: bool):
-        import ctypes
-
-        from ..ops.sweep import HipKernelError
-
-        n_scen, n_srv = scen.shape
-        n_acc = len(self.acc_names)
-        n_types = cap.shape[1]
-        if not hasattr(self, "_gpu"):
-            self._init_gpu_state()
-        st = self._gpu
         self._tick(plan_arrival=scen, launch=False)  # stage + bucket layout
-        self._sync_greedy_static()
+        g = self._gpu
+        g.sync_greedy_static(*self.greedy_static()[1:])
         cell_scen = np.ascontiguousarray(scen[:, self.cell_server], dtype=np.float32)
-        p_f, p_i, p_t = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-        p_x, p_c = ctypes.c_void_p(), ctypes.c_void_p()
-        rc = st["ctx_lib"].wva_ctx_plan_limited(
-            st["ctx"], ctypes.c_int(n_scen), ctypes.c_int(n_acc),
-            cell_scen.ctypes.data_as(ctypes.c_void_p),
-            ctypes.c_int(n_types), cap.ctypes.data_as(ctypes.c_void_p),
-            ctypes.c_int(1 if delayed else 0), ctypes.c_int(policy),
-            ctypes.byref(p_f), ctypes.byref(p_i), ctypes.byref(p_t),
-            ctypes.byref(p_x), ctypes.byref(p_c),
-        )
-        if rc != 0:
-            raise HipKernelError(f"wva_ctx_plan_limited failed: {rc}")
-
-        def view(ptr, ctype, shape):
-            n = int(np.prod(shape))
-            buf = (ctype * n).from_address(ptr.value)
-            return np.ctypeslib.as_array(buf).reshape(shape).copy()
-
-        of = view(p_f, ctypes.c_float, (n_scen, 6, n_srv))
-        oi = view(p_i, ctypes.c_int32, (n_scen, 4, n_srv))
-        ox = view(p_x, ctypes.c_int32, (n_scen, 2, n_srv))
-        totals = view(p_t, ctypes.c_uint64, (n_scen, n_acc)).astype(np.int64)
-        cap_left = view(p_c, ctypes.c_int32, (n_scen, n_types)).astype(np.int64)
-        winners = WinnerRecord(
-            acc_idx=oi[:, 0].copy(), num_replicas=oi[:, 1].copy(), batch=oi[:, 2].copy(),
-            cost=of[:, 0].copy(), value=of[:, 1].copy(), itl=of[:, 2].copy(),
-            ttft=of[:, 3].copy(), rho=of[:, 4].copy(), max_rate=of[:, 5].copy(),
-        )
+        of, oi, totals, ox, cap_left = g.plan(cell_scen, len(self.acc_names),
+                                              (cap, delayed, policy))
         self._plan_limited_cells = oi[:, 3].copy()  # winning cell index; tests read it
-        return winners, totals, ox[:, 0].copy(), ox[:, 1].copy(), cap_left
+        return _winner_record(of, oi), totals, ox[:, 0].copy(), ox[:, 1].copy(), cap_left
 
     def _plan_limited_host(self, scen, cap, policy: int, delayed: bool):
         """The host loop: one native greedy (ops/native/greedy.cpp) per
         scenario over the downloaded per-cell outputs."""
-        from ..ops.sweep import run_greedy_native
-
         n_scen, n_srv = scen.shape
         _, _, cells = self._plan_gpu(scen, True)
         _, cell_tidx, units, prio = self.greedy_static()
@@ -1018,83 +696,86 @@ class FastSweep:
         self._plan_limited_cells = win_cells
         return (winners, None, desired, n_cand, cap_left.astype(np.int64)), cells
 
+    @contextlib.contextmanager
+    def _scenario_loads(self):
+        """For the CPU golden paths: yields set_loads(row), which puts one
+        scenario's arrival rates (and the load override's token averages, when
+        set) on the server objects; their loads are restored afterwards in any
+        case."""
+        _, in_tok, out_tok = self._base_load()
+        saved = [
+            None if srv.load is None
+            else (srv.load.arrivalRate, srv.load.avgInTokens, srv.load.avgOutTokens)
+            for srv in self._srv_objs
+        ]
+
+        def set_loads(row):
+            for i, srv in enumerate(self._srv_objs):
+                if srv.load is None:
+                    continue  # no load: zero-traffic whatever the scenario says
+                srv.load.arrivalRate = float(row[i])
+                if self.load_override is not None:
+                    srv.load.avgInTokens = int(in_tok[i])
+                    srv.load.avgOutTokens = int(out_tok[i])
+
+        try:
+            yield set_loads
+        finally:
+            for srv, old in zip(self._srv_objs, saved):
+                if old is not None:
+                    (srv.load.arrivalRate, srv.load.avgInTokens,
+                     srv.load.avgOutTokens) = old
+
     def _plan_limited_cpu(self, scen, cap, saturation_policy, delayed: bool):
         """Golden path: per scenario the CPU sweep with the scenario's loads,
         then solver.greedy.solve_greedy with the scenario's capacity. Loads,
         allocations, candidate lists and system.capacity are restored
         afterwards in any case."""
-        from ..config import SaturationPolicy
         from ..solver.greedy import solve_greedy
         from .engine import SweepEngine
 
         system = self.system
         n_scen, n_srv = scen.shape
         types = self.capacity_types
-        _, in_tok, out_tok = self._base_load()
         policy = SaturationPolicy.parse(saturation_policy)
         members = set(self.server_names)
-        saved_load = [
-            None if srv.load is None
-            else (srv.load.arrivalRate, srv.load.avgInTokens, srv.load.avgOutTokens)
-            for srv in self._srv_objs
-        ]
         saved_alloc = {
             name: (srv.allocation, srv.all_allocations, srv.spec.desiredAlloc)
             for name, srv in system.servers.items()
         }
         saved_capacity = system.capacity
-        winners = WinnerRecord(**{
-            f: np.repeat(getattr(_empty_winner(n_srv), f)[None, :], n_scen, axis=0)
-            for f in _WINNER_FIELDS
-        })
+        winners = _empty_winners(n_scen, n_srv)
         desired = np.zeros((n_scen, n_srv), dtype=np.int32)
         n_cand = np.zeros((n_scen, n_srv), dtype=np.int32)
         cap_left = cap.astype(np.int64)
         engine = SweepEngine(backend="cpu")
         try:
-            for s in range(n_scen):
-                for i, srv in enumerate(self._srv_objs):
-                    if srv.load is None:
-                        continue  # no load: zero-traffic whatever the scenario says
-                    srv.load.arrivalRate = float(scen[s, i])
-                    if self.load_override is not None:
-                        srv.load.avgInTokens = int(in_tok[i])
-                        srv.load.avgOutTokens = int(out_tok[i])
-                for name, srv in system.servers.items():
-                    if name not in members:
-                        srv.all_allocations = {}  # only this sweep's servers compete
-                engine.sweep(system, server_names=self.server_names)
-                want = {}
-                for i, srv in enumerate(self._srv_objs):
-                    for alloc in srv.all_allocations.values():
-                        want[id(alloc)] = alloc.num_replicas
-                        if alloc.accelerator != "":
-                            n_cand[s, i] += 1
-                system.capacity = {t: int(cap[s, j]) for j, t in enumerate(types)}
-                solve_greedy(system, delayed_best_effort=delayed, saturation_policy=policy)
-                for i, srv in enumerate(self._srv_objs):
-                    alloc = srv.allocation
-                    if alloc is None or alloc.accelerator == "":
-                        continue
-                    acc = system.accelerators[alloc.accelerator]
-                    model = system.models[srv.model_name]
-                    per = model.get_num_instances(acc.name) * acc.multiplicity
-                    cap_left[s, types.index(acc.type)] -= alloc.num_replicas * per
-                    desired[s, i] = want.get(id(alloc), alloc.num_replicas)
-                    winners.acc_idx[s, i] = self._acc_index[alloc.accelerator]
-                    winners.num_replicas[s, i] = alloc.num_replicas
-                    winners.batch[s, i] = alloc.batch_size
-                    winners.cost[s, i] = alloc.cost
-                    winners.value[s, i] = alloc.value
-                    winners.itl[s, i] = alloc.itl
-                    winners.ttft[s, i] = alloc.ttft
-                    winners.rho[s, i] = alloc.rho
-                    winners.max_rate[s, i] = alloc.max_arrv_rate_per_replica
+            with self._scenario_loads() as set_loads:
+                for s in range(n_scen):
+                    set_loads(scen[s])
+                    for name, srv in system.servers.items():
+                        if name not in members:
+                            srv.all_allocations = {}  # only this sweep's servers compete
+                    engine.sweep(system, server_names=self.server_names)
+                    want = {}
+                    for i, srv in enumerate(self._srv_objs):
+                        for alloc in srv.all_allocations.values():
+                            want[id(alloc)] = alloc.num_replicas
+                            if alloc.accelerator != "":
+                                n_cand[s, i] += 1
+                    system.capacity = {t: int(cap[s, j]) for j, t in enumerate(types)}
+                    solve_greedy(system, delayed_best_effort=delayed, saturation_policy=policy)
+                    for i, srv in enumerate(self._srv_objs):
+                        alloc = srv.allocation
+                        if alloc is None or alloc.accelerator == "":
+                            continue
+                        acc = system.accelerators[alloc.accelerator]
+                        model = system.models[srv.model_name]
+                        per = model.get_num_instances(acc.name) * acc.multiplicity
+                        cap_left[s, types.index(acc.type)] -= alloc.num_replicas * per
+                        desired[s, i] = want.get(id(alloc), alloc.num_replicas)
+                        _set_winner(winners, (s, i), alloc, self._acc_index[alloc.accelerator])
         finally:
-            for srv, old in zip(self._srv_objs, saved_load):
-                if old is not None:
-                    (srv.load.arrivalRate, srv.load.avgInTokens,
-                     srv.load.avgOutTokens) = old
             for name, (alloc, all_allocs, want_alloc) in saved_alloc.items():
                 system.servers[name].allocation = alloc
                 system.servers[name].all_allocations = all_allocs
@@ -1106,29 +787,11 @@ class FastSweep:
         """Golden path: one _reconcile_cpu per scenario with the scenario's
         arrival rate (and the load override's token averages, when set) put
         on the server objects, which are restored afterwards in any case."""
-        n_scen, n_srv = scen.shape
-        _, in_tok, out_tok = self._base_load()
-        saved = [
-            None if srv.load is None
-            else (srv.load.arrivalRate, srv.load.avgInTokens, srv.load.avgOutTokens)
-            for srv in self._srv_objs
-        ]
         rows = []
-        try:
-            for s in range(n_scen):
-                for i, srv in enumerate(self._srv_objs):
-                    if srv.load is None:
-                        continue  # no load: zero-traffic whatever the scenario says
-                    srv.load.arrivalRate = float(scen[s, i])
-                    if self.load_override is not None:
-                        srv.load.avgInTokens = int(in_tok[i])
-                        srv.load.avgOutTokens = int(out_tok[i])
+        with self._scenario_loads() as set_loads:
+            for row in scen:
+                set_loads(row)
                 rows.append(self._reconcile_cpu())
-        finally:
-            for srv, old in zip(self._srv_objs, saved):
-                if old is not None:
-                    (srv.load.arrivalRate, srv.load.avgInTokens,
-                     srv.load.avgOutTokens) = old
         return WinnerRecord(**{
             f: np.stack([getattr(r, f) for r in rows]) for f in _WINNER_FIELDS
         })
@@ -1150,17 +813,8 @@ class FastSweep:
                     best = alloc
             if best is None:
                 continue
-            rec.acc_idx[seg] = (
-                -2 if best.accelerator == "" else self._acc_index[best.accelerator]
-            )
-            rec.num_replicas[seg] = best.num_replicas
-            rec.batch[seg] = best.batch_size
-            rec.cost[seg] = best.cost
-            rec.value[seg] = best.value
-            rec.itl[seg] = best.itl
-            rec.ttft[seg] = best.ttft
-            rec.rho[seg] = best.rho
-            rec.max_rate[seg] = best.max_arrv_rate_per_replica
+            _set_winner(rec, seg, best,
+                        -2 if best.accelerator == "" else self._acc_index[best.accelerator])
         return rec
 
 
@@ -1175,4 +829,41 @@ def _empty_winner(n: int) -> WinnerRecord:
         ttft=np.zeros(n, dtype=np.float32),
         rho=np.zeros(n, dtype=np.float32),
         max_rate=np.zeros(n, dtype=np.float32),
+    )
+
+
+def _set_winner(rec: WinnerRecord, at, alloc, acc_idx: int) -> None:
+    """Put Allocation ``alloc`` into ``rec`` at index ``at`` (the CPU paths)."""
+    rec.acc_idx[at] = acc_idx
+    rec.num_replicas[at] = alloc.num_replicas
+    rec.batch[at] = alloc.batch_size
+    rec.cost[at] = alloc.cost
+    rec.value[at] = alloc.value
+    rec.itl[at] = alloc.itl
+    rec.ttft[at] = alloc.ttft
+    rec.rho[at] = alloc.rho
+    rec.max_rate[at] = alloc.max_arrv_rate_per_replica
+
+
+def _empty_winners(n_scen: int, n_srv: int) -> WinnerRecord:
+    """_empty_winner for every scenario of a plan: arrays [n_scen, n_srv]."""
+    w = _empty_winner(n_srv)
+    return WinnerRecord(**{
+        f: np.repeat(getattr(w, f)[None, :], n_scen, axis=0) for f in _WINNER_FIELDS
+    })
+
+
+def _winner_record(of: np.ndarray, oi: np.ndarray) -> WinnerRecord:
+    """The native winner blocks as a WinnerRecord: ``of`` holds the fp32 rows
+    (cost, value, itl, ttft, rho, max_rate), ``oi`` the int32 rows (acc code,
+    replicas, batch, winner cell). Either the [rows, n_srv] pair of a
+    reconcile, whose rows become the fields as they are (views, no copy), or
+    the [S, rows, n_srv] pair of a plan, which is first copied rows-major so
+    that every field is a contiguous [S, n_srv] array."""
+    if of.ndim == 3:
+        of = np.ascontiguousarray(of.transpose(1, 0, 2))
+        oi = np.ascontiguousarray(oi.transpose(1, 0, 2))
+    return WinnerRecord(
+        acc_idx=oi[0], num_replicas=oi[1], batch=oi[2],
+        cost=of[0], value=of[1], itl=of[2], ttft=of[3], rho=of[4], max_rate=of[5],
     )

@@ -1,0 +1,283 @@
+"""NativeCtx — owner of one native reconcile context and of every buffer the
+context was handed (ops/hip/wva_ctx.inc).
+
+FastSweep (engine/fastpath.py) holds one as ``_gpu``. It owns the torch device
+and pinned buffers, the opaque ctx handle, the bucket cache and what was last
+pushed into the context; its methods are the ctypes calls, nothing else. The
+context keeps raw pointers into the tensors, so they live here, next to the
+handle, and the handle is destroyed first (close()).
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import numpy as np
+
+from ..ops.sweep import (
+    DYN_ROWS,
+    REC_ROWS,
+    TICK_STALE,
+    HipKernelError,
+    alloc_gmem_slabs,
+    choose_buckets,
+    load_library,
+)
+
+# The dynamic block (4-byte words, int32 rows then fp32 rows) in row order.
+DYN_INT = ("in_tok", "out_tok", "batch_n", "perf_max_batch", "cur_replicas", "flags")
+DYN_F32 = ("arrival_rate", "cur_cost")
+_BATCH_N_ROW = DYN_INT.index("batch_n")
+_STAT_F32 = ("alpha", "beta", "gamma", "delta", "t_itl", "t_ttft", "t_tps", "acc_cost")
+# per-cell outputs in WvaCellsOut order, with the dtypes of wva_ctx_plan_cells
+CELL_KEYS = ("feasible", "zero_empty", "num_replicas", "batch", "cost", "value", "itl", "ttft",
+             "rho", "max_rate")
+_CELL_DTYPES = (np.uint8, np.uint8, np.int32, np.int32) + (np.float32,) * 6
+# wva_ctx_create's pointer slots, in order, as attribute names of NativeCtx
+# (WVA_CTX_SLOTS of them; the order is the C side's and must not change)
+CTX_SLOT_NAMES = (
+    "dev_dyn", "min_replicas", "alpha", "beta", "gamma", "delta", "t_itl", "t_ttft", "t_tps",
+    "acc_cost", "feasible", "zero_empty", "num_replicas", "batch", "cost", "value", "itl", "ttft",
+    "rho", "max_rate", "seg", "winner", "cell_acc", "gather", "pin_dyn", "pin_out",
+)
+
+
+def _copy_out(ptr: ctypes.c_void_p, ctype, shape) -> np.ndarray:
+    """A numpy copy of one of the context's pinned result buffers."""
+    buf = (ctype * int(np.prod(shape))).from_address(ptr.value)
+    return np.ctypeslib.as_array(buf).reshape(shape).copy()
+
+
+class NativeCtx:
+    def __init__(self, n_srv: int, stat: dict, cell_server, cell_acc_idx, seg_start,
+                 device: str):
+        """Upload the static SoA (``stat``: FastSweep._stat) and allocate the
+        dynamic block, the per-cell outputs and the winner-record block with
+        their pinned mirrors, then create the context on them."""
+        import torch
+
+        self._lib = load_library(allow_build=False)
+        self.device = device
+        self.n_srv = n_srv
+        self.n_cells = n = len(cell_server)
+        self.ctx = None
+        # static topology the native tick stages from (copied by the context)
+        self._topo = [
+            np.ascontiguousarray(a, dtype=np.int32)
+            for a in (cell_server, cell_acc_idx, stat["perf_max_batch_cfg"], stat["at_tokens"],
+                      stat["override"])
+        ]
+        for k in _STAT_F32:
+            setattr(self, k, torch.from_numpy(np.ascontiguousarray(stat[k])).to(device))
+        self.min_replicas = torch.from_numpy(
+            np.ascontiguousarray(stat["min_replicas"], dtype=np.int32)
+        ).to(device)
+        self.pin_dyn = torch.empty((DYN_ROWS, n), dtype=torch.int32, pin_memory=True)
+        self.dev_dyn = torch.empty((DYN_ROWS, n), dtype=torch.int32, device=device)
+        self.pin_dyn_np = self.pin_dyn.numpy()
+        self.seg = torch.from_numpy(seg_start).to(device)
+        self.cell_acc = torch.from_numpy(self._topo[1]).to(device)
+        # outputs
+        for k, dt in zip(CELL_KEYS, (torch.uint8, torch.uint8, torch.int32, torch.int32)
+                         + (torch.float32,) * 6):
+            setattr(self, k, torch.zeros(n, dtype=dt, device=device))
+        self.winner = torch.full((n_srv,), -1, dtype=torch.int32, device=device)
+        # winner records: six fp32 rows (cost, value, itl, ttft, rho, max_rate)
+        # then four int32 rows (acc code, num_replicas, batch, winner cell)
+        self.gather = torch.empty((REC_ROWS, n_srv), dtype=torch.int32, device=device)
+        self.pin_out = torch.empty((REC_ROWS, n_srv), dtype=torch.int32, pin_memory=True)
+        self.pin_out_np = self.pin_out.numpy()
+        self.tick_stale = False  # did the last tick find the bucket layout stale
+        self.stale_ticks = 0
+        self.bucket_key = None  # batch_n bytes `buckets` was chosen for
+        self.buckets: list = []
+        self.greedy_static_key = None  # static greedy inputs last pushed
+        self._create_ctx()
+
+    def _create_ctx(self) -> None:
+        """Create the native reconcile context (opaque C struct owning the
+        HIP streams/events and all registered device/pinned pointers) —
+        the whole per-tick pipeline then runs behind ONE C call."""
+        lib = self._lib
+        n_slots = lib.wva_abi(b"WVA_CTX_SLOTS")
+        if len(CTX_SLOT_NAMES) != n_slots:
+            raise HipKernelError(
+                f"WVA_CTX_SLOTS is {n_slots} in the library but engine/native_ctx.py "
+                f"fills {len(CTX_SLOT_NAMES)} slots"
+            )
+        arr = (ctypes.c_void_p * n_slots)(
+            *[ctypes.c_void_p(getattr(self, name).data_ptr()) for name in CTX_SLOT_NAMES]
+        )
+        ctx = lib.wva_ctx_create(ctypes.c_int(self.n_cells), ctypes.c_int(self.n_srv), arr)
+        if not ctx:
+            raise HipKernelError("wva_ctx_create failed")
+        self.ctx = ctx
+        rc = lib.wva_ctx_set_topology(ctx, *[a.ctypes.data for a in self._topo])
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_set_topology failed: {rc}")
+
+    def close(self) -> None:
+        """Destroy the context (its streams, events and own allocations). The
+        tensors it points into are still alive here."""
+        ctx, self.ctx = self.ctx, None
+        if ctx is not None:
+            self._lib.wva_ctx_destroy(ctx)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------
+    def buckets_for(self, batch_n: np.ndarray):
+        import torch
+
+        key = batch_n.tobytes()
+        if self.bucket_key == key:
+            return self.buckets
+        buckets = []
+        for nt, ids, bmax, count, gmem in choose_buckets(batch_n):
+            ids_t = torch.from_numpy(ids).to(self.device) if ids is not None else None
+            slabs = (
+                alloc_gmem_slabs(count, bmax, nt, self.device) if gmem else (None, None)
+            )
+            buckets.append((nt, ids_t, bmax, count, slabs))
+        self.bucket_key = key
+        self.buckets = buckets
+        return buckets
+
+    def sync_buckets(self, batch_n: np.ndarray, analyzer_mode: int, cv2: float) -> None:
+        """Push the bucket layout + analyzer mode into the native context,
+        together with the batch_n it was chosen for (called when the context
+        reported its layout stale)."""
+        buckets = self.buckets_for(batch_n)
+
+        def ptrs(tensors):
+            return (ctypes.c_void_p * len(tensors))(
+                *[ctypes.c_void_p(t.data_ptr()) if t is not None else None for t in tensors]
+            )
+
+        n = len(buckets)
+        nts = (ctypes.c_int * n)(*[b[0] for b in buckets])
+        nbl = (ctypes.c_int * n)(
+            *[int(b[1].numel()) if b[1] is not None else self.n_cells for b in buckets]
+        )
+        mxn = (ctypes.c_int * n)(*[b[2] for b in buckets])
+        batch_n = np.ascontiguousarray(batch_n, dtype=np.int32)
+        rc = self._lib.wva_ctx_set_buckets(
+            self.ctx, ctypes.c_int(n), nts, ptrs([b[1] for b in buckets]), nbl, mxn,
+            ctypes.c_int(analyzer_mode), ctypes.c_float(cv2),
+            ptrs([b[4][0] for b in buckets]), ptrs([b[4][1] for b in buckets]),
+            batch_n.ctypes.data,
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_set_buckets failed: {rc}")
+
+    def sync_greedy_static(self, cell_tidx, units, prio) -> None:
+        """Upload the static greedy inputs into the native context (only when
+        they changed)."""
+        arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in (cell_tidx, units, prio)]
+        key = b"".join(a.tobytes() for a in arrs)
+        if self.greedy_static_key == key:
+            return
+        rc = self._lib.wva_ctx_set_greedy_static(
+            self.ctx, *[a.ctypes.data_as(ctypes.c_void_p) for a in arrs]
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_set_greedy_static failed: {rc}")
+        self.greedy_static_key = key
+
+    # ------------------------------------------------------------------
+    def tick(self, srv, zero: Optional[np.ndarray], launch: bool) -> bool:
+        """wva_ctx_tick on the six contiguous per-server arrays ``srv``
+        (arrival, in_tok, out_tok, cur_acc, cur_rep, cur_cost). Returns
+        whether the context found its bucket layout stale — it then staged
+        the tick but launched nothing; sync_buckets(staged_batch_n(), ...)
+        and resume() finish it."""
+        rc = self._lib.wva_ctx_tick(
+            self.ctx, srv[0].ctypes.data, srv[1].ctypes.data, srv[2].ctypes.data,
+            srv[3].ctypes.data, srv[4].ctypes.data, srv[5].ctypes.data,
+            zero.ctypes.data if zero is not None else None, 1 if launch else 0,
+        )
+        self.tick_stale = rc == TICK_STALE
+        if rc == TICK_STALE:
+            self.stale_ticks += 1
+            return True
+        if rc != 0:
+            raise HipKernelError(f"native reconcile tick failed: {rc}")
+        return False
+
+    def staged_batch_n(self) -> np.ndarray:
+        return self.pin_dyn_np[_BATCH_N_ROW].copy()
+
+    def resume(self) -> None:
+        """Run the already staged tick (wva_reconcile) and synchronise."""
+        rc = self._lib.wva_reconcile(self.ctx)
+        if rc != 0:
+            raise HipKernelError(f"native reconcile tick failed: {rc}")
+
+    def winner_block(self) -> tuple[np.ndarray, np.ndarray]:
+        """The last tick's winner records, copied out of the pinned block:
+        (fp32 [6, n_srv], int32 [4, n_srv])."""
+        blk = self.pin_out_np.copy()
+        return blk[:6].view(np.float32), blk[6:]
+
+    def cells(self) -> dict:
+        """The last tick's per-cell outputs, downloaded."""
+        return {k: getattr(self, k).cpu().numpy() for k in CELL_KEYS}
+
+    def memo_stats(self) -> Optional[tuple[int, int]]:
+        """(hits, misses) of the sizing memo, None when the memo is off."""
+        hits, misses = ctypes.c_uint(0), ctypes.c_uint(0)
+        rc = self._lib.wva_ctx_memo_stats(self.ctx, ctypes.byref(hits), ctypes.byref(misses))
+        if rc < 0:
+            raise HipKernelError(f"wva_ctx_memo_stats failed: {rc}")
+        if rc != 0:
+            return None
+        return int(hits.value), int(misses.value)
+
+    # ------------------------------------------------------------------
+    def plan(self, cell_scen: np.ndarray, n_acc: int, limited=None):
+        """wva_ctx_plan on [S, n_cells] fp32 arrivals (the tick is staged and
+        the buckets are set): (fp32 [S, 6, n_srv], int32 [S, 4, n_srv], int64
+        totals [S, n_acc]). ``limited`` = (int32 capacity [S, n_types],
+        delayed, policy code) makes it wva_ctx_plan_limited (after
+        sync_greedy_static) and appends int32 [S, 2, n_srv] (pre-cut replicas,
+        candidate counts) and the int64 capacity left [S, n_types]."""
+        n_scen = cell_scen.shape[0]
+        out = [ctypes.c_void_p() for _ in range(3 if limited is None else 5)]
+        refs = [ctypes.byref(p) for p in out]
+        if limited is None:
+            call = "wva_ctx_plan"
+            rc = self._lib.wva_ctx_plan(self.ctx, n_scen, n_acc, cell_scen.ctypes.data, *refs)
+        else:
+            call = "wva_ctx_plan_limited"
+            cap, delayed, policy = limited
+            rc = self._lib.wva_ctx_plan_limited(
+                self.ctx, n_scen, n_acc, cell_scen.ctypes.data, cap.shape[1], cap.ctypes.data,
+                1 if delayed else 0, policy, *refs,
+            )
+        if rc != 0:
+            raise HipKernelError(f"{call} failed: {rc}")
+        res = (
+            _copy_out(out[0], ctypes.c_float, (n_scen, 6, self.n_srv)),
+            _copy_out(out[1], ctypes.c_int32, (n_scen, 4, self.n_srv)),
+            _copy_out(out[2], ctypes.c_uint64, (n_scen, n_acc)).astype(np.int64),
+        )
+        if limited is not None:
+            res += (_copy_out(out[3], ctypes.c_int32, (n_scen, 2, self.n_srv)),
+                    _copy_out(out[4], ctypes.c_int32, cap.shape).astype(np.int64))
+        return res
+
+    def plan_cells(self, n_scen: int) -> dict:
+        """Per-cell outputs [S, n_cells] of the planning pass that just ran."""
+        cells = {k: np.empty((n_scen, self.n_cells), dtype=d)
+                 for k, d in zip(CELL_KEYS, _CELL_DTYPES)}
+        dst = (ctypes.c_void_p * len(CELL_KEYS))(
+            *[cells[k].ctypes.data_as(ctypes.c_void_p) for k in CELL_KEYS]
+        )
+        rc = self._lib.wva_ctx_plan_cells(self.ctx, dst)
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_plan_cells failed: {rc}")
+        return cells

@@ -20,8 +20,13 @@ NATIVE_SRCS = [
     os.path.join(OPS_DIR, "native", "greedy.cpp"),
     os.path.join(OPS_DIR, "native", "stage.cpp"),
 ]
-# headers the sources above include (a newer one makes the library stale)
-NATIVE_HDRS = [os.path.join(OPS_DIR, "native", "wva_stage.h")]
+# files the sources above include (a newer one makes the library stale): the
+# context runtime is part of HIP_SRC's translation unit
+NATIVE_HDRS = [
+    os.path.join(OPS_DIR, "hip", "wva_ctx.inc"),
+    os.path.join(OPS_DIR, "native", "wva_stage.h"),
+    os.path.join(OPS_DIR, "native", "wva_arena.h"),
+]
 LIB_DIR = os.path.join(OPS_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libwva_hip.so")
 

@@ -1,0 +1,807 @@
+// wva_ctx.inc — host side of the native reconcile context, included at the end
+// of wva_kernels.hip (one translation unit: the kernels are launched from
+// here). The whole per-tick device pipeline behind ONE C call (host staging of
+// the per-server state, one H2D copy, regime-bucketed sweep launches
+// overlapped via events on side streams, the fused winner kernel, one D2H
+// copy, sync): wva_ctx_tick(ctx, ...); wva_reconcile(ctx) runs an already
+// staged tick; the planning passes share the context's arrays and buckets.
+#include "../native/wva_arena.h"  // 256-aligned arena layout (host only)
+
+#define WVA_MAX_BUCKETS 5
+#define WVA_PLAN_MAX_S 256  // scenarios per planning pass
+
+struct WvaBucket {
+  int nt;
+  const int *cell_ids;  // nullptr = identity
+  int n_blocks;
+  int max_n;
+  float *g_inv;      // non-null: global-memory geometry slab (huge-N spill)
+  double *g_anchor;
+};
+
+// Created with `new WvaCtx()`: every member without an initialiser below
+// starts as zero / nullptr.
+struct WvaCtx {
+  int n_cells;
+  int n_srv;
+  int analyzer_mode;
+  float cv2 = 1.0f;
+  // device SoA
+  WvaCellsIn in;
+  WvaCellsOut out;
+  const int *seg_start;
+  int *winner;
+  const int *cell_acc;
+  // dynamic block: WVA_DYN_ROWS x n_cells 4-byte words (six int32 rows, then
+  // arrival_rate and cur_cost), one device allocation and its pinned source;
+  // `in` points into the device one
+  void *dev_dyn;
+  void *pin_dyn;
+  // winner records: WVA_REC_ROWS x n_srv words (six fp32 rows, then four
+  // int32 rows), one device block and its pinned mirror
+  void *gather;
+  void *pin_out;
+  // host-side staging (wva_ctx_tick): the static per-cell topology and the
+  // batch_n row the current bucket layout was chosen for (one host
+  // allocation, carved up)
+  int *topo;  // nullptr until wva_ctx_set_topology
+  const int *topo_cell_server, *topo_cell_acc, *topo_cfg, *topo_at_tokens, *topo_override;
+  int *bucket_batch_n;
+  int bucket_batch_valid;  // 0 until set_buckets recorded a batch_n row
+  WvaBucket buckets[WVA_MAX_BUCKETS];
+  int n_buckets;
+  hipStream_t s0;                           // primary stream
+  hipStream_t side[WVA_MAX_BUCKETS - 1];    // overlap streams for buckets 1..
+  hipEvent_t e_up;                          // upload-complete
+  hipEvent_t e_b[WVA_MAX_BUCKETS - 1];      // side-bucket completion
+  // hipGraph capture of the whole per-tick pipeline (H2D copies, bucket
+  // kernels on their streams, winner kernel, D2H): replayed as ONE launch
+  // per reconcile. State: 0 = not captured, 1 = exec valid, -1 = capture
+  // failed once -> stay on the eager path. Invalidated by set_buckets.
+  hipGraphExec_t graph_exec;
+  int graph_state;
+  // sizing memo (one device allocation: n_cells records, then the hit and
+  // miss counters). nullptr = memo off (INFERNO_SIZING_MEMO=0 or the
+  // allocation failed). Stable for the life of the ctx, so a captured graph
+  // stays valid.
+  WvaMemoRec *memo;
+  unsigned *memo_cnt;
+  // scenario planning (wva_ctx_plan): buffers allocated on first use, grown
+  // to the largest scenario count / accelerator count seen, freed in destroy
+  int plan_cap;      // scenarios the buffers hold (0 = not allocated)
+  int plan_acc_cap;  // accelerators per totals row the buffers hold
+  int plan_s;        // scenario count of the last successful plan (0 = none)
+  void *plan_dev;    // one device allocation, carved up below
+  void *plan_pin;    // one pinned host allocation, carved up below
+  float *plan_scen;  // device [S][n_cells]
+  WvaCellsOut plan_out;  // device, each [S][n_cells]
+  float *plan_pf;    // device [S][6][n_srv]
+  int *plan_pi;      // device [S][4][n_srv]
+  unsigned long long *plan_tot;  // device [S][n_acc]
+  float *plan_pin_scen;  // pinned mirrors of plan_scen / pf / pi / tot
+  float *plan_pin_pf;
+  int *plan_pin_pi;
+  unsigned long long *plan_pin_tot;
+  // capacity-limited planning (wva_ctx_plan_limited): the static greedy
+  // inputs (wva_ctx_set_greedy_static) and the per-scenario workspace, both
+  // allocated on first use and freed in destroy
+  void *lim_static;     // device: cell_type, cell_units [n_cells], srv_prio [n_srv]
+  const int *lim_cell_type;
+  const int *lim_cell_units;
+  const int *lim_srv_prio;
+  int lim_cap;          // scenarios the workspace holds (0 = not allocated)
+  int lim_types_cap;    // accelerator types per capacity row it holds
+  void *lim_dev;        // one device allocation, carved up below
+  void *lim_pin;        // one pinned host allocation, carved up below
+  // Dynamic LDS wva_plan_greedy may take for its hot state, in bytes; fleets
+  // that need more keep it in the global workspace (same code, same result).
+  // INFERNO_PLAN_GREEDY_LDS overrides it (0 = always global), read once at
+  // create.
+  size_t lim_lds_budget = 120 * 1024;
+  double *lim_wsd;      // device [S][n_srv + n_cells] 8-byte words
+  int *lim_wsi;         // device [S][15 * n_srv + 3 * n_cells]
+  int *lim_capacity;    // device [S][n_types]
+  int *lim_px;          // device [S][2][n_srv]
+  int *lim_pin_capacity;  // pinned mirrors of lim_capacity / lim_px
+  int *lim_pin_px;
+};
+
+// pointer-slot order for wva_ctx_create (engine/native_ctx.py builds the
+// array from CTX_SLOT_NAMES and checks its length against WVA_CTX_SLOTS):
+//  0 dev_dyn (8*n_cells words: in_tok, out_tok, batch_n, perf_max_batch,
+//    cur_replicas, flags i32; arrival_rate, cur_cost f32)
+//  1 min_replicas            2 alpha  3 beta  4 gamma  5 delta
+//  6 t_itl  7 t_ttft  8 t_tps  9 acc_cost
+//  10 feasible  11 zero_empty  12 num_replicas  13 batch  14 cost
+//  15 value  16 itl  17 ttft  18 rho  19 max_rate
+//  20 seg_start  21 winner  22 cell_acc
+//  23 gather (10*n_srv words: cost, value, itl, ttft, rho, max_rate f32;
+//     acc code, num_replicas, batch, winner cell i32)
+//  24 pin_dyn (pinned source of 0)  25 pin_out (pinned mirror of 23)
+#define WVA_CTX_SLOTS 26
+#define WVA_REC_ROWS 10
+
+// The constants both sides of the C ABI rely on, by name; -1 for an unknown
+// name. ops/sweep.py load_library() checks its mirrors against these once.
+extern "C" int wva_abi(const char *name) {
+#define WVA_ABI(x) {#x, x}
+  static const struct {
+    const char *name;
+    int value;
+  } table[] = {WVA_ABI(WVA_MAX_N),      WVA_ABI(WVA_XL_MAX_N),  WVA_ABI(WVA_HUGE_MAX_N),
+               WVA_ABI(WVA_PLAN_MAX_S), WVA_ABI(WVA_N_SMALL),   WVA_ABI(WVA_N_MED),
+               WVA_ABI(WVA_TICK_STALE), WVA_ABI(WVA_DYN_ROWS),  WVA_ABI(WVA_REC_ROWS),
+               WVA_ABI(WVA_CTX_SLOTS),  WVA_ABI(WVA_MAX_BUCKETS)};
+#undef WVA_ABI
+  if (name == nullptr) return -1;
+  for (const auto &e : table)
+    if (strcmp(name, e.name) == 0) return e.value;
+  return -1;
+}
+
+// Makes the device that owns dev_ptr current for its scope (allocations must
+// land next to the kernels' inputs). Switches only when both device ids are
+// known and differ; restores only if it switched.
+struct WvaDeviceGuard {
+  int prev = -1;
+  bool switched = false;
+  explicit WvaDeviceGuard(const void *dev_ptr) {
+    int dev = -1;
+    hipPointerAttribute_t attr;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (hipPointerGetAttributes(&attr, dev_ptr) == hipSuccess) dev = attr.device;
+    switched = dev >= 0 && prev >= 0 && dev != prev && hipSetDevice(dev) == hipSuccess;
+  }
+  ~WvaDeviceGuard() {
+    if (switched) (void)hipSetDevice(prev);
+  }
+  WvaDeviceGuard(const WvaDeviceGuard &) = delete;
+  WvaDeviceGuard &operator=(const WvaDeviceGuard &) = delete;
+};
+
+extern "C" void *wva_ctx_create(int n_cells, int n_srv, void **p) {
+  WvaCtx *c = new WvaCtx();
+  c->n_cells = n_cells;
+  c->n_srv = n_srv;
+  if (const char *lds_env = getenv("INFERNO_PLAN_GREEDY_LDS")) {
+    char *end = nullptr;
+    const long v = strtol(lds_env, &end, 10);
+    if (end != lds_env && *end == '\0' && v >= 0 && v <= 120 * 1024)
+      c->lim_lds_budget = (size_t)v;
+  }
+  char *dd = (char *)p[0];
+  size_t cw = (size_t)n_cells * 4;  // one row of the dynamic block
+  c->in.in_tok = (const int *)(dd + 0 * cw);
+  c->in.out_tok = (const int *)(dd + 1 * cw);
+  c->in.batch_n = (const int *)(dd + 2 * cw);
+  c->in.perf_max_batch = (const int *)(dd + 3 * cw);
+  c->in.cur_replicas = (const int *)(dd + 4 * cw);
+  c->in.flags = (const int *)(dd + 5 * cw);
+  c->in.arrival_rate = (const float *)(dd + 6 * cw);
+  c->in.cur_cost = (const float *)(dd + 7 * cw);
+  c->in.min_replicas = (const int *)p[1];
+  c->in.alpha = (const float *)p[2];
+  c->in.beta = (const float *)p[3];
+  c->in.gamma = (const float *)p[4];
+  c->in.delta = (const float *)p[5];
+  c->in.t_itl = (const float *)p[6];
+  c->in.t_ttft = (const float *)p[7];
+  c->in.t_tps = (const float *)p[8];
+  c->in.acc_cost = (const float *)p[9];
+  c->out.feasible = (uint8_t *)p[10];
+  c->out.zero_empty = (uint8_t *)p[11];
+  c->out.num_replicas = (int *)p[12];
+  c->out.batch = (int *)p[13];
+  c->out.cost = (float *)p[14];
+  c->out.value = (float *)p[15];
+  c->out.itl = (float *)p[16];
+  c->out.ttft = (float *)p[17];
+  c->out.rho = (float *)p[18];
+  c->out.max_rate = (float *)p[19];
+  c->seg_start = (const int *)p[20];
+  c->winner = (int *)p[21];
+  c->cell_acc = (const int *)p[22];
+  c->gather = p[23];
+  c->dev_dyn = p[0];
+  c->pin_dyn = p[24];
+  c->pin_out = p[25];
+  bool ok = hipStreamCreateWithFlags(&c->s0, hipStreamNonBlocking) == hipSuccess &&
+            hipEventCreateWithFlags(&c->e_up, hipEventDisableTiming) == hipSuccess;
+  for (int i = 0; ok && i < WVA_MAX_BUCKETS - 1; ++i)
+    ok = hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking) == hipSuccess &&
+         hipEventCreateWithFlags(&c->e_b[i], hipEventDisableTiming) == hipSuccess;
+  if (!ok) {
+    delete c;
+    return nullptr;
+  }
+  // sizing memo: INFERNO_SIZING_MEMO=0 is the kill switch (A/B measurement,
+  // tests) — read per call, never cached. Any failure here leaves the memo
+  // off; the context itself is still good.
+  const char *memo_env = getenv("INFERNO_SIZING_MEMO");
+  const bool memo_on = !(memo_env != nullptr && memo_env[0] == '0' && memo_env[1] == '\0');
+  if (memo_on && n_cells > 0) {
+    WvaDeviceGuard on_dev(c->dev_dyn);
+    const size_t bytes = (size_t)n_cells * sizeof(WvaMemoRec) + 2 * sizeof(unsigned);
+    void *m = nullptr;
+    if (hipMalloc(&m, bytes) == hipSuccess && m != nullptr) {
+      if (hipMemsetAsync(m, 0, bytes, c->s0) == hipSuccess) {
+        c->memo = (WvaMemoRec *)m;
+        c->memo_cnt = (unsigned *)((char *)m + (size_t)n_cells * sizeof(WvaMemoRec));
+      } else {
+        (void)hipFree(m);
+      }
+    }
+    if (c->memo == nullptr) (void)hipGetLastError();  // clear the non-fatal error
+  }
+  return c;
+}
+
+// hit/miss counters of the sizing memo since the context was created
+// (unsigned, wrapping). Synchronous small D2H — diagnostics only, never on
+// the hot path. Returns 1 when the memo is off, <0 on a runtime error.
+extern "C" int wva_ctx_memo_stats(void *ctx, unsigned *hits, unsigned *misses) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || c->memo == nullptr) return 1;
+  unsigned h[2] = {0u, 0u};
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -1;
+  if (hipMemcpy(h, c->memo_cnt, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -2;
+  if (hits) *hits = h[0];
+  if (misses) *misses = h[1];
+  return 0;
+}
+
+// The static per-cell topology wva_ctx_tick stages from, five host int32
+// arrays of n_cells each (copied): the cell's server, its accelerator index,
+// the profile's maxBatchSize and atTokens, the server's batch override.
+extern "C" int wva_ctx_set_topology(void *ctx, const int *cell_server, const int *cell_acc_idx,
+                                    const int *perf_max_batch_cfg, const int *at_tokens,
+                                    const int *override_n) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr) return -1;
+  const size_t n = (size_t)c->n_cells;
+  if (n > 0 && (cell_server == nullptr || cell_acc_idx == nullptr ||
+                perf_max_batch_cfg == nullptr || at_tokens == nullptr || override_n == nullptr))
+    return -1;
+  for (size_t k = 0; k < n; ++k)
+    if (cell_server[k] < 0 || cell_server[k] >= c->n_srv) return -2;
+  if (c->topo == nullptr) {
+    c->topo = (int *)malloc((6 * n + 1) * sizeof(int));
+    if (c->topo == nullptr) return -3;
+  }
+  const int *src[5] = {cell_server, cell_acc_idx, perf_max_batch_cfg, at_tokens, override_n};
+  for (int r = 0; r < 5; ++r)
+    if (n > 0) memcpy(c->topo + r * n, src[r], n * sizeof(int));
+  c->topo_cell_server = c->topo + 0 * n;
+  c->topo_cell_acc = c->topo + 1 * n;
+  c->topo_cfg = c->topo + 2 * n;
+  c->topo_at_tokens = c->topo + 3 * n;
+  c->topo_override = c->topo + 4 * n;
+  c->bucket_batch_n = c->topo + 5 * n;
+  c->bucket_batch_valid = 0;
+  return 0;
+}
+
+// batch_n (may be null): the host batch_n row [n_cells] the layout was chosen
+// for. It is recorded; wva_ctx_tick reports a stale layout when a tick's
+// batch_n differs from it (or when none was recorded).
+extern "C" int wva_ctx_set_buckets(void *ctx, int n_buckets, const int *nts,
+                                   const void **cell_ids, const int *n_blocks,
+                                   const int *max_ns, int analyzer_mode, float cv2,
+                                   const void **g_invs, const void **g_anchors,
+                                   const int *batch_n) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (n_buckets < 0 || n_buckets > WVA_MAX_BUCKETS) return -1;
+  c->bucket_batch_valid = 0;
+  if (batch_n != nullptr && c->topo != nullptr) {
+    if (c->n_cells > 0) memcpy(c->bucket_batch_n, batch_n, (size_t)c->n_cells * sizeof(int));
+    c->bucket_batch_valid = 1;
+  }
+  c->n_buckets = n_buckets;
+  for (int i = 0; i < n_buckets; ++i) {
+    c->buckets[i].nt = nts[i];
+    c->buckets[i].cell_ids = (const int *)cell_ids[i];
+    c->buckets[i].n_blocks = n_blocks[i];
+    c->buckets[i].max_n = max_ns[i];
+    c->buckets[i].g_inv = g_invs ? (float *)g_invs[i] : nullptr;
+    c->buckets[i].g_anchor = g_anchors ? (double *)g_anchors[i] : nullptr;
+  }
+  c->analyzer_mode = analyzer_mode;
+  c->cv2 = cv2;
+  // bucket layout / analyzer change: drop the captured pipeline (unless
+  // capture already proved unsupported, which is sticky)
+  if (c->graph_state == 1) (void)hipGraphExecDestroy(c->graph_exec);
+  if (c->graph_state != -1) c->graph_state = 0;
+  return 0;
+}
+
+// The bucket sweeps of one pass, after the uploads queued on s0: record the
+// upload event, launch bucket 0 on s0 and the others on the side streams
+// behind that event, then join them back onto s0. `out` receives the per-cell
+// results; `plan` (may be null) selects the planning kernels. Enqueues only —
+// no synchronising call, since the reconcile pipeline runs under stream
+// capture.
+static int wva_run_buckets(WvaCtx *c, const WvaCellsOut &out, const WvaPlanArgs *plan) {
+  if (hipEventRecord(c->e_up, c->s0) != hipSuccess) return -10;
+  for (int i = 0; i < c->n_buckets; ++i) {
+    hipStream_t s = (i == 0) ? c->s0 : c->side[i - 1];
+    if (i > 0 && hipStreamWaitEvent(s, c->e_up, 0) != hipSuccess) return -11;
+    const WvaBucket &b = c->buckets[i];
+    const int rc =
+        wva_sweep_dispatch(b.n_blocks, b.max_n, b.nt, b.cell_ids, c->analyzer_mode, c->cv2, s,
+                           c->in, out, b.g_inv, b.g_anchor, c->memo, c->memo_cnt, plan);
+    if (rc != 0) return rc;
+    if (i > 0 && hipEventRecord(c->e_b[i - 1], s) != hipSuccess) return -12;
+  }
+  for (int i = 1; i < c->n_buckets; ++i)
+    if (hipStreamWaitEvent(c->s0, c->e_b[i - 1], 0) != hipSuccess) return -14;
+  return 0;
+}
+
+// enqueue the whole per-tick pipeline on the ctx's streams (used both for
+// eager execution and for stream capture into a hipGraph)
+static int wva_enqueue_pipeline(WvaCtx *c) {
+  hipError_t err;
+  // 1. dynamic H2D (pinned -> device), the whole block in one copy
+  err = hipMemcpyAsync(c->dev_dyn, c->pin_dyn, (size_t)WVA_DYN_ROWS * c->n_cells * 4,
+                       hipMemcpyHostToDevice, c->s0);
+  if (err != hipSuccess) return (int)err;
+
+  // 2. bucket launches, overlapped on the side streams
+  const int rc = wva_run_buckets(c, c->out, nullptr);
+  if (rc != 0) return rc;
+
+  // 3. winner selection + winner records on s0, one launch
+  hipLaunchKernelGGL(wva_winner, dim3(c->n_srv), dim3(WVA_WAVE), 0, c->s0, c->out.value,
+                     c->out.feasible, c->out.zero_empty, c->cell_acc, c->out.num_replicas,
+                     c->out.batch, c->out.cost, c->out.itl, c->out.ttft, c->out.rho,
+                     c->out.max_rate, c->seg_start, c->n_srv, c->gather, c->winner);
+  err = hipGetLastError();
+  if (err != hipSuccess) return (int)err;
+
+  // 4. D2H of the winner records, one copy
+  err = hipMemcpyAsync(c->pin_out, c->gather, (size_t)WVA_REC_ROWS * c->n_srv * 4,
+                       hipMemcpyDeviceToHost, c->s0);
+  if (err != hipSuccess) return (int)err;
+  return 0;
+}
+
+// One reconcile tick behind one call: stage the six per-server arrays
+// ([n_srv] each; cur_acc -3 none, -1 empty, >= 0 accelerator index) into the
+// pinned dynamic block, then
+//   launch != 0: if the tick's batch_n equals the row the bucket layout was
+//     set for, run the pipeline and synchronise (returns 0, or a negative /
+//     HIP error code); otherwise launch nothing and return WVA_TICK_STALE.
+//     The caller then reads batch_n from the pinned block, calls
+//     wva_ctx_set_buckets and wva_reconcile, which runs the staged tick.
+//   launch == 0: stage only (the planning passes); returns 0 or
+//     WVA_TICK_STALE by the same comparison.
+// zero_arrival (may be null) replaces arrival in the zero-load decision.
+extern "C" int wva_reconcile(void *ctx);
+extern "C" int wva_ctx_tick(void *ctx, const float *arrival, const int *in_tok, const int *out_tok,
+                            const int *cur_acc, const int *cur_rep, const float *cur_cost,
+                            const float *zero_arrival, int launch) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || c->topo == nullptr) return -41;
+  int changed = 1;
+  const int rc = wva_stage_dynamic(
+      c->n_srv, c->n_cells, arrival, in_tok, out_tok, cur_acc, cur_rep, cur_cost, zero_arrival,
+      c->topo_cell_server, c->topo_cell_acc, c->topo_cfg, c->topo_at_tokens, c->topo_override,
+      c->pin_dyn, c->bucket_batch_valid ? c->bucket_batch_n : nullptr, &changed);
+  if (rc != 0) return -42;
+  if (changed) return WVA_TICK_STALE;
+  return launch ? wva_reconcile(ctx) : 0;
+}
+
+extern "C" int wva_reconcile(void *ctx) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  // replay the captured pipeline when available: every buffer pointer and
+  // kernel argument is ctx-stable between ticks, so the graph stays valid
+  // until the bucket layout changes (set_buckets invalidates)
+  if (c->graph_state == 1) {
+    if (hipGraphLaunch(c->graph_exec, c->s0) != hipSuccess) {
+      (void)hipGraphExecDestroy(c->graph_exec);
+      c->graph_state = -1;  // fall back to eager permanently
+    } else {
+      return (int)hipStreamSynchronize(c->s0);
+    }
+  }
+  if (c->graph_state == 0) {
+    // OPT-IN (INFERNO_HIPGRAPH=1): measured SLOWER than eager on MI355X for
+    // this pipeline (0.55 vs 0.45 ms/step, same-box x3) — graph replay does
+    // not preserve the 4-HW-queue bucket overlap the eager path gets. Kept
+    // as an option for launch-bound configurations (many tiny buckets).
+    static int enabled = -1;
+    if (enabled < 0) enabled = getenv("INFERNO_HIPGRAPH") != nullptr ? 1 : 0;
+    if (!enabled) c->graph_state = -1;
+  }
+  if (c->graph_state == 0) {
+    // capture once: the side-stream forks/joins via events become graph
+    // dependencies (capture mode relaxed — no other thread uses these
+    // streams)
+    hipGraph_t graph = nullptr;
+    bool ok = hipStreamBeginCapture(c->s0, hipStreamCaptureModeRelaxed) == hipSuccess;
+    int rc = ok ? wva_enqueue_pipeline(c) : -20;
+    if (ok) {
+      if (hipStreamEndCapture(c->s0, &graph) != hipSuccess) ok = false;
+    }
+    if (ok && rc == 0 && graph != nullptr &&
+        hipGraphInstantiate(&c->graph_exec, graph, nullptr, nullptr, 0) == hipSuccess) {
+      c->graph_state = 1;
+      (void)hipGraphDestroy(graph);
+      if (hipGraphLaunch(c->graph_exec, c->s0) == hipSuccess)
+        return (int)hipStreamSynchronize(c->s0);
+      (void)hipGraphExecDestroy(c->graph_exec);
+      c->graph_state = -1;
+    } else {
+      if (graph != nullptr) (void)hipGraphDestroy(graph);
+      c->graph_state = -1;  // capture unsupported here: stay eager
+      // a failed capture may have left the stream in capture state; make
+      // sure it is usable again
+      hipStreamCaptureStatus st;
+      if (hipStreamIsCapturing(c->s0, &st) == hipSuccess &&
+          st != hipStreamCaptureStatusNone) {
+        hipGraph_t dead = nullptr;
+        (void)hipStreamEndCapture(c->s0, &dead);
+        if (dead != nullptr) (void)hipGraphDestroy(dead);
+      }
+    }
+  }
+  int rc = wva_enqueue_pipeline(c);
+  if (rc != 0) return rc;
+  return (int)hipStreamSynchronize(c->s0);
+}
+
+// ---------------------------------------------------------------------------
+// Scenario planning: S arrival-rate scenarios of the whole fleet in one pass.
+// Shares the context's static arrays, dynamic int arrays, buckets and sizing
+// memo with wva_reconcile; owns only the scenario arrivals, the [S][n_cells]
+// outputs and the reduce outputs. The hipGraph path is not involved.
+// ---------------------------------------------------------------------------
+
+static void wva_arena_free(void *&dev, void *&pin) {
+  if (dev != nullptr) (void)hipFree(dev);
+  if (pin != nullptr) (void)hipHostFree(pin);
+  dev = pin = nullptr;
+}
+
+// One device block of dev_bytes (on the device that owns dev_dyn; zero-filled
+// on s0 when `zero`) and one pinned host block of pin_bytes. On failure
+// nothing is held and the pending HIP error is cleared, so the context stays
+// usable for whatever does not need the arena.
+static bool wva_arena_alloc(WvaCtx *c, size_t dev_bytes, size_t pin_bytes, bool zero, void **dev,
+                            void **pin) {
+  void *d = nullptr, *h = nullptr;
+  bool ok;
+  {
+    WvaDeviceGuard on_dev(c->dev_dyn);
+    ok = hipMalloc(&d, dev_bytes) == hipSuccess && d != nullptr;
+    ok = ok && hipHostMalloc(&h, pin_bytes, hipHostMallocDefault) == hipSuccess && h != nullptr;
+    ok = ok && (!zero || hipMemsetAsync(d, 0, dev_bytes, c->s0) == hipSuccess);
+  }
+  if (!ok) {
+    wva_arena_free(d, h);
+    (void)hipGetLastError();
+    return false;
+  }
+  *dev = d;
+  *pin = h;
+  return true;
+}
+
+static void wva_plan_release(WvaCtx *c) {
+  wva_arena_free(c->plan_dev, c->plan_pin);
+  c->plan_cap = c->plan_acc_cap = c->plan_s = 0;
+}
+
+// (re)allocate the planning buffers for n_scen scenarios and n_acc
+// accelerators; on failure nothing is held and the context is otherwise intact
+static int wva_plan_reserve(WvaCtx *c, int n_scen, int n_acc) {
+  if (n_scen <= c->plan_cap && n_acc <= c->plan_acc_cap) return 0;
+  const int cap = n_scen > c->plan_cap ? n_scen : c->plan_cap;
+  const int acap = n_acc > c->plan_acc_cap ? n_acc : c->plan_acc_cap;
+  wva_plan_release(c);
+  const size_t cells = (size_t)cap * (size_t)c->n_cells;
+  const size_t b_w = cells * 4;  // one 4-byte per-cell array
+  const size_t b_pf = (size_t)cap * 6 * c->n_srv * sizeof(float);
+  const size_t b_pi = (size_t)cap * 4 * c->n_srv * sizeof(int);
+  const size_t b_tot = (size_t)cap * acap * sizeof(unsigned long long);
+  // device: scenario arrivals, the eight 4-byte and two 1-byte per-cell
+  // outputs, pf, pi, totals; pinned: arrivals, pf, pi, totals
+  enum { D_SCEN, D_REPS, D_BATCH, D_COST, D_VALUE, D_ITL, D_TTFT, D_RHO, D_RATE, D_FEAS, D_ZERO,
+         D_PF, D_PI, D_TOT, D_N };
+  enum { H_SCEN, H_PF, H_PI, H_TOT, H_N };
+  const size_t d_size[D_N] = {b_w, b_w, b_w, b_w, b_w, b_w, b_w, b_w, b_w, cells, cells,
+                              b_pf, b_pi, b_tot};
+  const size_t h_size[H_N] = {b_w, b_pf, b_pi, b_tot};
+  size_t d_off[D_N], h_off[H_N];
+  const size_t dev_bytes = wva_arena_layout(d_size, D_N, d_off);
+  const size_t pin_bytes = wva_arena_layout(h_size, H_N, h_off);
+  // infeasible cells write only their two flags; start from zeros so the
+  // other fields of such cells are defined
+  if (!wva_arena_alloc(c, dev_bytes, pin_bytes, true, &c->plan_dev, &c->plan_pin)) return -30;
+  c->plan_cap = cap;
+  c->plan_acc_cap = acap;
+  char *d = (char *)c->plan_dev, *h = (char *)c->plan_pin;
+  c->plan_scen = (float *)(d + d_off[D_SCEN]);
+  c->plan_out.num_replicas = (int *)(d + d_off[D_REPS]);
+  c->plan_out.batch = (int *)(d + d_off[D_BATCH]);
+  c->plan_out.cost = (float *)(d + d_off[D_COST]);
+  c->plan_out.value = (float *)(d + d_off[D_VALUE]);
+  c->plan_out.itl = (float *)(d + d_off[D_ITL]);
+  c->plan_out.ttft = (float *)(d + d_off[D_TTFT]);
+  c->plan_out.rho = (float *)(d + d_off[D_RHO]);
+  c->plan_out.max_rate = (float *)(d + d_off[D_RATE]);
+  c->plan_out.feasible = (uint8_t *)(d + d_off[D_FEAS]);
+  c->plan_out.zero_empty = (uint8_t *)(d + d_off[D_ZERO]);
+  c->plan_pf = (float *)(d + d_off[D_PF]);
+  c->plan_pi = (int *)(d + d_off[D_PI]);
+  c->plan_tot = (unsigned long long *)(d + d_off[D_TOT]);
+  c->plan_pin_scen = (float *)(h + h_off[H_SCEN]);
+  c->plan_pin_pf = (float *)(h + h_off[H_PF]);
+  c->plan_pin_pi = (int *)(h + h_off[H_PI]);
+  c->plan_pin_tot = (unsigned long long *)(h + h_off[H_TOT]);
+  return 0;
+}
+
+static void wva_lim_release(WvaCtx *c) {
+  wva_arena_free(c->lim_dev, c->lim_pin);
+  c->lim_cap = c->lim_types_cap = 0;
+}
+
+// (re)allocate the greedy workspace for n_scen scenarios and n_types
+// accelerator types; on failure nothing is held and reconciles and unlimited
+// plans keep working
+static int wva_lim_reserve(WvaCtx *c, int n_scen, int n_types) {
+  if (n_scen <= c->lim_cap && n_types <= c->lim_types_cap) return 0;
+  const int cap = n_scen > c->lim_cap ? n_scen : c->lim_cap;
+  const int tcap = n_types > c->lim_types_cap ? n_types : c->lim_types_cap;
+  wva_lim_release(c);
+  const size_t b_cap = (size_t)cap * tcap * sizeof(int);
+  const size_t b_px = (size_t)cap * 2 * c->n_srv * sizeof(int);
+  // device: wsd, wsi, capacity, px; pinned: capacity, px
+  enum { D_WSD, D_WSI, D_CAP, D_PX, D_N };
+  enum { H_CAP, H_PX, H_N };
+  const size_t d_size[D_N] = {
+      (size_t)cap * ((size_t)c->n_srv + (size_t)c->n_cells) * sizeof(double),
+      (size_t)cap * ((size_t)15 * c->n_srv + (size_t)3 * c->n_cells) * sizeof(int), b_cap, b_px};
+  const size_t h_size[H_N] = {b_cap, b_px};
+  size_t d_off[D_N], h_off[H_N];
+  const size_t dev_bytes = wva_arena_layout(d_size, D_N, d_off);
+  const size_t pin_bytes = wva_arena_layout(h_size, H_N, h_off);
+  if (!wva_arena_alloc(c, dev_bytes, pin_bytes, false, &c->lim_dev, &c->lim_pin)) return -34;
+  c->lim_cap = cap;
+  c->lim_types_cap = tcap;
+  char *d = (char *)c->lim_dev, *h = (char *)c->lim_pin;
+  c->lim_wsd = (double *)(d + d_off[D_WSD]);
+  c->lim_wsi = (int *)(d + d_off[D_WSI]);
+  c->lim_capacity = (int *)(d + d_off[D_CAP]);
+  c->lim_px = (int *)(d + d_off[D_PX]);
+  c->lim_pin_capacity = (int *)(h + h_off[H_CAP]);
+  c->lim_pin_px = (int *)(h + h_off[H_PX]);
+  return 0;
+}
+
+// Static inputs of wva_plan_greedy: host cell_type, cell_units [n_cells] and
+// srv_prio [n_srv]. Synchronous upload; the caller repeats it only when one
+// of the arrays changed.
+extern "C" int wva_ctx_set_greedy_static(void *ctx, const int *cell_type, const int *cell_units,
+                                         const int *srv_prio) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || cell_type == nullptr || cell_units == nullptr || srv_prio == nullptr)
+    return -31;
+  if (c->n_cells <= 0 || c->n_srv <= 0) return -33;
+  const size_t b_c = wva_align256((size_t)c->n_cells * sizeof(int));
+  const size_t b_s = wva_align256((size_t)c->n_srv * sizeof(int));
+  if (c->lim_static == nullptr) {
+    void *d = nullptr;
+    bool ok;
+    {
+      WvaDeviceGuard on_dev(c->dev_dyn);
+      ok = hipMalloc(&d, 2 * b_c + b_s) == hipSuccess && d != nullptr;
+    }
+    if (!ok) {
+      (void)hipGetLastError();
+      return -34;
+    }
+    c->lim_static = d;
+    c->lim_cell_type = (const int *)d;
+    c->lim_cell_units = (const int *)((char *)d + b_c);
+    c->lim_srv_prio = (const int *)((char *)d + 2 * b_c);
+  }
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -1;
+  char *d = (char *)c->lim_static;
+  if (hipMemcpy(d, cell_type, (size_t)c->n_cells * sizeof(int), hipMemcpyHostToDevice) !=
+          hipSuccess ||
+      hipMemcpy(d + b_c, cell_units, (size_t)c->n_cells * sizeof(int), hipMemcpyHostToDevice) !=
+          hipSuccess ||
+      hipMemcpy(d + 2 * b_c, srv_prio, (size_t)c->n_srv * sizeof(int), hipMemcpyHostToDevice) !=
+          hipSuccess)
+    return -2;
+  return 0;
+}
+
+// One planning pass. scen_arrival: host, [n_scen][n_cells] fp32 (req/min).
+// The caller has filled the context's pinned dynamic arrays and set the
+// buckets, exactly as for wva_reconcile. On success the three out pointers
+// name the context's pinned result buffers, valid until the next
+// wva_ctx_plan or wva_ctx_destroy: pf [n_scen][6][n_srv] fp32 (cost, value,
+// itl, ttft, rho, max_rate), pi [n_scen][4][n_srv] i32 (acc code, replicas,
+// batch, winner cell), totals [n_scen][n_acc] u64.
+//
+// lim == nullptr is the unlimited plan (wva_ctx_plan). With lim, step 3 is
+// wva_plan_greedy instead of wva_plan_reduce and the capacity rows go up and
+// come back (wva_ctx_plan_limited); everything else is the same pass.
+struct WvaLimArgs {
+  int n_types;
+  const int *capacity;  // host [n_scen][n_types]
+  int delayed;
+  int policy;
+};
+
+static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arrival,
+                        const WvaLimArgs *lim, const void **out_pf, const void **out_pi,
+                        const void **out_totals) {
+  if (c == nullptr || scen_arrival == nullptr) return -31;
+  if (n_scen < 1 || n_scen > WVA_PLAN_MAX_S || n_acc < 1) return -32;
+  if (c->n_cells <= 0 || c->n_srv <= 0) return -33;
+  c->plan_s = 0;
+  int rc = wva_plan_reserve(c, n_scen, n_acc);
+  if (rc != 0) return rc;
+  if (lim != nullptr) {
+    rc = wva_lim_reserve(c, n_scen, lim->n_types);
+    if (rc != 0) return rc;
+  }
+  const size_t cells = (size_t)n_scen * (size_t)c->n_cells;
+  hipError_t err;
+
+  // 1. uploads: scenario arrivals through the pinned staging buffer, then the
+  // dynamic arrays as wva_enqueue_pipeline does
+  for (size_t i = 0; i < cells; ++i) c->plan_pin_scen[i] = scen_arrival[i];
+  err = hipMemcpyAsync(c->plan_scen, c->plan_pin_scen, cells * sizeof(float),
+                       hipMemcpyHostToDevice, c->s0);
+  if (err != hipSuccess) return (int)err;
+  err = hipMemcpyAsync(c->dev_dyn, c->pin_dyn, (size_t)WVA_DYN_ROWS * c->n_cells * 4,
+                       hipMemcpyHostToDevice, c->s0);
+  if (err != hipSuccess) return (int)err;
+  err = hipMemsetAsync(c->plan_tot, 0, (size_t)n_scen * n_acc * sizeof(unsigned long long),
+                       c->s0);
+  if (err != hipSuccess) return (int)err;
+  const size_t n_capacity = lim != nullptr ? (size_t)n_scen * (size_t)lim->n_types : 0;
+  if (lim != nullptr) {
+    for (size_t i = 0; i < n_capacity; ++i) c->lim_pin_capacity[i] = lim->capacity[i];
+    err = hipMemcpyAsync(c->lim_capacity, c->lim_pin_capacity, n_capacity * sizeof(int),
+                         hipMemcpyHostToDevice, c->s0);
+    if (err != hipSuccess) return (int)err;
+  }
+
+  // 2. planning buckets: same streams, fork/join and order as the reconcile
+  const WvaPlanArgs pa = {c->n_cells, n_scen, c->plan_scen};
+  rc = wva_run_buckets(c, c->plan_out, &pa);
+  if (rc != 0) return rc;
+
+  // 3. winners, records and totals for all (server, scenario) pairs
+  if (lim == nullptr) {
+    hipLaunchKernelGGL(wva_plan_reduce, dim3(c->n_srv, n_scen), dim3(WVA_WAVE), 0, c->s0,
+                       c->plan_out.value, c->plan_out.feasible, c->plan_out.zero_empty,
+                       c->cell_acc, c->plan_out.num_replicas, c->plan_out.batch, c->plan_out.cost,
+                       c->plan_out.itl, c->plan_out.ttft, c->plan_out.rho, c->plan_out.max_rate,
+                       c->seg_start, c->n_srv, c->n_cells, n_scen, n_acc, c->plan_pf, c->plan_pi,
+                       c->plan_tot);
+  } else {
+    size_t lds = wva_greedy_lds_bytes(c->n_srv, c->n_cells);
+    if (lds > c->lim_lds_budget ||
+        wva_optin_lds(reinterpret_cast<const void *>(&wva_plan_greedy), lds) != 0) {
+      (void)hipGetLastError();
+      lds = 0;  // hot state in the global workspace
+    }
+    hipLaunchKernelGGL(wva_plan_greedy, dim3(n_scen), dim3(WVA_WAVE), lds, c->s0,
+                       c->plan_out.value, c->plan_out.feasible, c->plan_out.zero_empty,
+                       c->cell_acc, c->plan_out.num_replicas, c->plan_out.batch, c->plan_out.cost,
+                       c->plan_out.itl, c->plan_out.ttft, c->plan_out.rho, c->plan_out.max_rate,
+                       c->seg_start, c->lim_cell_type, c->lim_cell_units, c->lim_srv_prio,
+                       c->n_srv, c->n_cells, n_scen, n_acc, lim->n_types, lim->delayed,
+                       lim->policy, lds > 0 ? 1 : 0, c->lim_capacity, c->lim_wsi, c->lim_wsd, c->plan_pf,
+                       c->plan_pi, c->lim_px, c->plan_tot);
+  }
+  err = hipGetLastError();
+  if (err != hipSuccess) return (int)err;
+  if (lim != nullptr) {
+    err = hipMemcpyAsync(c->lim_pin_capacity, c->lim_capacity, n_capacity * sizeof(int),
+                         hipMemcpyDeviceToHost, c->s0);
+    if (err != hipSuccess) return (int)err;
+    err = hipMemcpyAsync(c->lim_pin_px, c->lim_px, (size_t)n_scen * 2 * c->n_srv * sizeof(int),
+                         hipMemcpyDeviceToHost, c->s0);
+    if (err != hipSuccess) return (int)err;
+  }
+
+  // 4. downloads
+  err = hipMemcpyAsync(c->plan_pin_pf, c->plan_pf, (size_t)n_scen * 6 * c->n_srv * sizeof(float),
+                       hipMemcpyDeviceToHost, c->s0);
+  if (err != hipSuccess) return (int)err;
+  err = hipMemcpyAsync(c->plan_pin_pi, c->plan_pi, (size_t)n_scen * 4 * c->n_srv * sizeof(int),
+                       hipMemcpyDeviceToHost, c->s0);
+  if (err != hipSuccess) return (int)err;
+  err = hipMemcpyAsync(c->plan_pin_tot, c->plan_tot,
+                       (size_t)n_scen * n_acc * sizeof(unsigned long long),
+                       hipMemcpyDeviceToHost, c->s0);
+  if (err != hipSuccess) return (int)err;
+  err = hipStreamSynchronize(c->s0);
+  if (err != hipSuccess) return (int)err;
+  c->plan_s = n_scen;
+  if (out_pf) *out_pf = c->plan_pin_pf;
+  if (out_pi) *out_pi = c->plan_pin_pi;
+  if (out_totals) *out_totals = c->plan_pin_tot;
+  return 0;
+}
+
+extern "C" int wva_ctx_plan(void *ctx, int n_scen, int n_acc, const float *scen_arrival,
+                            const void **out_pf, const void **out_pi,
+                            const void **out_totals) {
+  return wva_plan_run((WvaCtx *)ctx, n_scen, n_acc, scen_arrival, nullptr, out_pf, out_pi,
+                      out_totals);
+}
+
+// One capacity-limited planning pass: wva_ctx_plan's uploads and buckets, then
+// one greedy solve per scenario on the device. capacity: host, [n_scen]
+// [n_types] int32 units per accelerator type. policy: 0 None,
+// 1 PriorityExhaustive, 2 PriorityRoundRobin, 3 RoundRobin. The static inputs
+// must have been set (wva_ctx_set_greedy_static). pf, pi and totals are as for
+// wva_ctx_plan, holding the limited solution (pi row 0 is the granted
+// accelerator or -1, row 1 the granted replicas). out_px: pinned i32 [n_scen]
+// [2][n_srv] (the granted cell's pre-cut replicas; the server's feasible
+// candidates that are not zero-load). out_capacity: pinned i32 [n_scen]
+// [n_types], the capacity left.
+extern "C" int wva_ctx_plan_limited(void *ctx, int n_scen, int n_acc, const float *scen_arrival,
+                                    int n_types, const int *capacity, int delayed, int policy,
+                                    const void **out_pf, const void **out_pi,
+                                    const void **out_totals, const void **out_px,
+                                    const void **out_capacity) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || capacity == nullptr) return -31;
+  if (n_types < 1 || policy < 0 || policy > 3) return -32;
+  if (c->lim_static == nullptr) return -35;
+  const WvaLimArgs lim = {n_types, capacity, delayed ? 1 : 0, policy};
+  const int rc = wva_plan_run(c, n_scen, n_acc, scen_arrival, &lim, out_pf, out_pi, out_totals);
+  if (rc != 0) return rc;
+  if (out_px) *out_px = c->lim_pin_px;
+  if (out_capacity) *out_capacity = c->lim_pin_capacity;
+  return 0;
+}
+
+// Per-cell outputs of the last successful wva_ctx_plan, copied into ten host
+// arrays of plan_s * n_cells elements each, in WvaCellsOut order (feasible,
+// zero_empty: u8; num_replicas, batch: i32; cost, value, itl, ttft, rho,
+// max_rate: f32). Synchronous; inspection and tests, not the hot path.
+extern "C" int wva_ctx_plan_cells(void *ctx, void **dst) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || dst == nullptr || c->plan_s < 1) return -31;
+  const size_t cells = (size_t)c->plan_s * (size_t)c->n_cells;
+  const void *src[10] = {c->plan_out.feasible, c->plan_out.zero_empty, c->plan_out.num_replicas,
+                         c->plan_out.batch,    c->plan_out.cost,       c->plan_out.value,
+                         c->plan_out.itl,      c->plan_out.ttft,       c->plan_out.rho,
+                         c->plan_out.max_rate};
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -1;
+  for (int i = 0; i < 10; ++i) {
+    const size_t bytes = cells * (i < 2 ? 1 : 4);
+    if (hipMemcpy(dst[i], src[i], bytes, hipMemcpyDeviceToHost) != hipSuccess) return -2;
+  }
+  return 0;
+}
+
+extern "C" void wva_ctx_destroy(void *ctx) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr) return;
+  if (c->graph_state == 1) (void)hipGraphExecDestroy(c->graph_exec);
+  (void)hipStreamDestroy(c->s0);
+  (void)hipEventDestroy(c->e_up);
+  for (int i = 0; i < WVA_MAX_BUCKETS - 1; ++i) {
+    (void)hipStreamDestroy(c->side[i]);
+    (void)hipEventDestroy(c->e_b[i]);
+  }
+  if (c->memo != nullptr) (void)hipFree(c->memo);
+  wva_plan_release(c);
+  wva_lim_release(c);
+  if (c->lim_static != nullptr) (void)hipFree(c->lim_static);
+  free(c->topo);
+  delete c;
+}

@@ -42,11 +42,27 @@
 //
 //   K2 wva_argmin: segmented argmin over the sweep output per server
 //       (value = transition-penalty-adjusted cost), deterministic
-//       lowest-cell-index tie-break.
+//       lowest-cell-index tie-break (the one-shot API; the context uses K4b).
+//
+//   K1 also comes as wva_plan_t<NT>: the same sweep over S arrival-rate
+//       scenarios per cell (planning).
+//
+//   K4 wva_plan_reduce: per (server, scenario) K2's selection, the winner
+//       record and the per-accelerator replica totals, in one launch.
+//
+//   K4b wva_winner: the reconcile tick's winner step, K4 on one scenario
+//       without the totals.
+//
+//   K5 wva_plan_greedy: the capacity-limited solution of every scenario, one
+//       wave per scenario.
+//
+//   (K3 is unused: the numbers are kept stable for the documents that cite
+//   them.)
 //
 // Built standalone with hipcc (no torch headers); exposed as a C ABI and
 // driven from Python via ctypes on torch tensors' device pointers
-// (ops/sweep.py one-shot API; engine/fastpath.py persistent-state hot path).
+// (ops/sweep.py one-shot API; engine/native_ctx.py persistent-state hot path,
+// whose host side is wva_ctx.inc, included at the end of this file).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -1254,25 +1270,6 @@ extern "C" int wva_sweep_launch_bucket(
                             nullptr, nullptr);  // one-shot API: no sizing memo
 }
 
-// single-bucket convenience wrapper (whole sweep with one block size)
-extern "C" int wva_sweep_launch(
-    int n_cells, int max_n, void *stream,
-    const int *in_tok, const int *out_tok, const int *batch_n, const int *min_replicas,
-    const int *perf_max_batch, const int *cur_replicas, const int *flags,
-    const float *alpha, const float *beta, const float *gamma, const float *delta,
-    const float *arrival_rate, const float *t_itl, const float *t_ttft, const float *t_tps,
-    const float *acc_cost, const float *cur_cost,
-    uint8_t *feasible, uint8_t *zero_empty, int *num_replicas, int *batch, float *cost,
-    float *value, float *itl, float *ttft, float *rho, float *max_rate) {
-  int nt = (max_n <= WVA_N_SMALL) ? 64 : (max_n <= WVA_N_MED ? 256 : 1024);
-  return wva_sweep_launch_bucket(n_cells, max_n, nt, nullptr, 0, 1.0f, stream, in_tok, out_tok,
-                                 batch_n,
-                                 min_replicas, perf_max_batch, cur_replicas, flags, alpha, beta,
-                                 gamma, delta, arrival_rate, t_itl, t_ttft, t_tps, acc_cost,
-                                 cur_cost, feasible, zero_empty, num_replicas, batch, cost,
-                                 value, itl, ttft, rho, max_rate, nullptr, nullptr);
-}
-
 extern "C" int wva_argmin_launch(int n_servers, void *stream, const float *value,
                                  const uint8_t *feasible, const int *seg_start, int *winner) {
   if (n_servers <= 0) return 0;
@@ -1284,40 +1281,17 @@ extern "C" int wva_argmin_launch(int n_servers, void *stream, const float *value
 extern "C" int wva_device_count(int *count) { return (int)hipGetDeviceCount(count); }
 
 // ---------------------------------------------------------------------------
-// K3 wva_gather: materialize per-server winner records on-device (one thread
-// per server) so the host reads back two small pinned buffers.
-// gf rows: cost, value, itl, ttft, rho, max_rate; gi rows: acc_code
+// The per-server winner record, which the host reads back from small pinned
+// buffers. gf rows: cost, value, itl, ttft, rho, max_rate; gi rows: acc_code
 // (-1 none, -2 zero-load empty, else accelerator index), num_replicas,
-// batch, winner cell index.
-// ---------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(256) wva_gather(
-    const int *winner, const uint8_t *zero_empty, const int *cell_acc,
-    const int *num_replicas, const int *batch, const float *cost, const float *value,
-    const float *itl, const float *ttft, const float *rho, const float *max_rate,
-    int n_srv, float *gf, int *gi) {
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n_srv) return;
-  const int w = winner[s];
-  const bool has = w >= 0;
-  const int wc = has ? w : 0;
-  gf[0 * n_srv + s] = has ? cost[wc] : 0.0f;
-  gf[1 * n_srv + s] = has ? value[wc] : 0.0f;
-  gf[2 * n_srv + s] = has ? itl[wc] : 0.0f;
-  gf[3 * n_srv + s] = has ? ttft[wc] : 0.0f;
-  gf[4 * n_srv + s] = has ? rho[wc] : 0.0f;
-  gf[5 * n_srv + s] = has ? max_rate[wc] : 0.0f;
-  gi[0 * n_srv + s] = has ? (zero_empty[wc] ? -2 : cell_acc[wc]) : -1;
-  gi[1 * n_srv + s] = has ? num_replicas[wc] : 0;
-  gi[2 * n_srv + s] = has ? batch[wc] : 0;
-  gi[3 * n_srv + s] = w;
-}
-
-// ---------------------------------------------------------------------------
+// batch, winner cell index. K4 and K4b select the winner and write its record
+// in one launch.
+//
 // K4 wva_plan_reduce: winner selection + winner record + per-accelerator
 // replica totals for every (server, scenario) of a planning sweep in one
 // launch. Grid (n_srv, n_scen), one wave each. The selection is wva_argmin's
 // rule on scenario slice s (minimum value over feasible cells, lowest cell
-// index on ties), the record is wva_gather's, written into
+// index on ties), the record is the one above, written into
 // pf[n_scen][6][n_srv] / pi[n_scen][4][n_srv]. totals[n_scen][n_acc] must be
 // zero on entry; the winner's replica count is added with a 64-bit integer
 // atomic (a cell may hold 2 147 483 000 replicas, and integer adds make the
@@ -1395,7 +1369,7 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_reduce(
 
 // ---------------------------------------------------------------------------
 // K4b wva_winner: the reconcile tick's winner step in one launch, one wave
-// per server: wva_argmin's selection followed by wva_gather's record, i.e.
+// per server: wva_argmin's selection followed by the winner record, i.e.
 // wva_plan_reduce on a single scenario without the totals. rec is the
 // 10 x n_srv winner block (six fp32 rows, then four int32 rows); winner[srv]
 // gets the winning cell index as wva_argmin leaves it.
@@ -1843,806 +1817,8 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_greedy(
                                 capacity, wsi, wsd, pf, pi, px, totals, s_cap);
 }
 
-// ---------------------------------------------------------------------------
-// Native reconcile context: the whole per-tick device pipeline behind ONE C
-// call (host staging of the per-server state, one H2D copy, regime-bucketed
-// sweep launches overlapped via events on side streams, the fused winner
-// kernel, one D2H copy, sync) — no per-step host dispatch beyond
-// wva_ctx_tick(ctx, ...); wva_reconcile(ctx) runs an already staged tick.
-// ---------------------------------------------------------------------------
-#define WVA_MAX_BUCKETS 5
+// The native reconcile context (WvaCtx: the per-tick pipeline and the planning
+// passes behind the wva_ctx_* C ABI) launches the kernels above; it is host
+// code of this translation unit.
+#include "wva_ctx.inc"
 
-struct WvaBucket {
-  int nt;
-  const int *cell_ids;  // nullptr = identity
-  int n_blocks;
-  int max_n;
-  float *g_inv;      // non-null: global-memory geometry slab (huge-N spill)
-  double *g_anchor;
-};
-
-struct WvaCtx {
-  int n_cells;
-  int n_srv;
-  int analyzer_mode;
-  float cv2;
-  // device SoA
-  WvaCellsIn in;
-  WvaCellsOut out;
-  const int *seg_start;
-  int *winner;
-  const int *cell_acc;
-  // dynamic block: WVA_DYN_ROWS x n_cells 4-byte words (six int32 rows, then
-  // arrival_rate and cur_cost), one device allocation and its pinned source;
-  // `in` points into the device one
-  void *dev_dyn;
-  void *pin_dyn;
-  // winner records: 10 x n_srv words (six fp32 rows, then four int32 rows),
-  // one device block and its pinned mirror
-  void *gather;
-  void *pin_out;
-  // host-side staging (wva_ctx_tick): the static per-cell topology and the
-  // batch_n row the current bucket layout was chosen for (one host
-  // allocation, carved up)
-  int *topo;  // nullptr until wva_ctx_set_topology
-  const int *topo_cell_server, *topo_cell_acc, *topo_cfg, *topo_at_tokens, *topo_override;
-  int *bucket_batch_n;
-  int bucket_batch_valid;  // 0 until set_buckets recorded a batch_n row
-  WvaBucket buckets[WVA_MAX_BUCKETS];
-  int n_buckets;
-  hipStream_t s0;                           // primary stream
-  hipStream_t side[WVA_MAX_BUCKETS - 1];    // overlap streams for buckets 1..
-  hipEvent_t e_up;                          // upload-complete
-  hipEvent_t e_b[WVA_MAX_BUCKETS - 1];      // side-bucket completion
-  // hipGraph capture of the whole per-tick pipeline (H2D copies, bucket
-  // kernels on their streams, winner kernel, D2H): replayed as ONE launch
-  // per reconcile. State: 0 = not captured, 1 = exec valid, -1 = capture
-  // failed once -> stay on the eager path. Invalidated by set_buckets.
-  hipGraphExec_t graph_exec;
-  int graph_state;
-  // sizing memo (one device allocation: n_cells records, then the hit and
-  // miss counters). nullptr = memo off (INFERNO_SIZING_MEMO=0 or the
-  // allocation failed). Stable for the life of the ctx, so a captured graph
-  // stays valid.
-  WvaMemoRec *memo;
-  unsigned *memo_cnt;
-  // scenario planning (wva_ctx_plan): buffers allocated on first use, grown
-  // to the largest scenario count / accelerator count seen, freed in destroy
-  int plan_cap;      // scenarios the buffers hold (0 = not allocated)
-  int plan_acc_cap;  // accelerators per totals row the buffers hold
-  int plan_s;        // scenario count of the last successful plan (0 = none)
-  void *plan_dev;    // one device allocation, carved up below
-  void *plan_pin;    // one pinned host allocation, carved up below
-  float *plan_scen;  // device [S][n_cells]
-  WvaCellsOut plan_out;  // device, each [S][n_cells]
-  float *plan_pf;    // device [S][6][n_srv]
-  int *plan_pi;      // device [S][4][n_srv]
-  unsigned long long *plan_tot;  // device [S][n_acc]
-  float *plan_pin_scen;  // pinned mirrors of plan_scen / pf / pi / tot
-  float *plan_pin_pf;
-  int *plan_pin_pi;
-  unsigned long long *plan_pin_tot;
-  // capacity-limited planning (wva_ctx_plan_limited): the static greedy
-  // inputs (wva_ctx_set_greedy_static) and the per-scenario workspace, both
-  // allocated on first use and freed in destroy
-  void *lim_static;     // device: cell_type, cell_units [n_cells], srv_prio [n_srv]
-  const int *lim_cell_type;
-  const int *lim_cell_units;
-  const int *lim_srv_prio;
-  int lim_cap;          // scenarios the workspace holds (0 = not allocated)
-  int lim_types_cap;    // accelerator types per capacity row it holds
-  void *lim_dev;        // one device allocation, carved up below
-  void *lim_pin;        // one pinned host allocation, carved up below
-  size_t lim_lds_budget;  // dynamic LDS the greedy may take (INFERNO_PLAN_GREEDY_LDS)
-  double *lim_wsd;      // device [S][n_srv + n_cells] 8-byte words
-  int *lim_wsi;         // device [S][15 * n_srv + 3 * n_cells]
-  int *lim_capacity;    // device [S][n_types]
-  int *lim_px;          // device [S][2][n_srv]
-  int *lim_pin_capacity;  // pinned mirrors of lim_capacity / lim_px
-  int *lim_pin_px;
-};
-
-// pointer-slot order for wva_ctx_create (host mirrors in ops/sweep.py):
-//  0 dev_dyn (8*n_cells words: in_tok, out_tok, batch_n, perf_max_batch,
-//    cur_replicas, flags i32; arrival_rate, cur_cost f32)
-//  1 min_replicas            2 alpha  3 beta  4 gamma  5 delta
-//  6 t_itl  7 t_ttft  8 t_tps  9 acc_cost
-//  10 feasible  11 zero_empty  12 num_replicas  13 batch  14 cost
-//  15 value  16 itl  17 ttft  18 rho  19 max_rate
-//  20 seg_start  21 winner  22 cell_acc
-//  23 gather (10*n_srv words: cost, value, itl, ttft, rho, max_rate f32;
-//     acc code, num_replicas, batch, winner cell i32)
-//  24 pin_dyn (pinned source of 0)  25 pin_out (pinned mirror of 23)
-#define WVA_CTX_SLOTS 26
-#define WVA_REC_ROWS 10
-
-extern "C" void *wva_ctx_create(int n_cells, int n_srv, void **p) {
-  WvaCtx *c = new WvaCtx();
-  c->n_cells = n_cells;
-  c->n_srv = n_srv;
-  c->analyzer_mode = 0;
-  c->cv2 = 1.0f;
-  c->n_buckets = 0;
-  c->graph_exec = nullptr;
-  c->graph_state = 0;
-  c->memo = nullptr;
-  c->memo_cnt = nullptr;
-  c->plan_cap = 0;
-  c->plan_acc_cap = 0;
-  c->plan_s = 0;
-  c->plan_dev = nullptr;
-  c->plan_pin = nullptr;
-  c->lim_static = nullptr;
-  c->lim_cap = 0;
-  c->lim_types_cap = 0;
-  c->lim_dev = nullptr;
-  c->lim_pin = nullptr;
-  // Dynamic LDS wva_plan_greedy may take for its hot state, in bytes; fleets
-  // that need more keep it in the global workspace (same code, same result).
-  // INFERNO_PLAN_GREEDY_LDS overrides it (0 = always global), read here once.
-  c->lim_lds_budget = 120 * 1024;
-  if (const char *lds_env = getenv("INFERNO_PLAN_GREEDY_LDS")) {
-    char *end = nullptr;
-    const long v = strtol(lds_env, &end, 10);
-    if (end != lds_env && *end == '\0' && v >= 0 && v <= 120 * 1024)
-      c->lim_lds_budget = (size_t)v;
-  }
-  c->topo = nullptr;
-  c->bucket_batch_valid = 0;
-  char *dd = (char *)p[0];
-  size_t cw = (size_t)n_cells * 4;  // one row of the dynamic block
-  c->in.in_tok = (const int *)(dd + 0 * cw);
-  c->in.out_tok = (const int *)(dd + 1 * cw);
-  c->in.batch_n = (const int *)(dd + 2 * cw);
-  c->in.perf_max_batch = (const int *)(dd + 3 * cw);
-  c->in.cur_replicas = (const int *)(dd + 4 * cw);
-  c->in.flags = (const int *)(dd + 5 * cw);
-  c->in.arrival_rate = (const float *)(dd + 6 * cw);
-  c->in.cur_cost = (const float *)(dd + 7 * cw);
-  c->in.min_replicas = (const int *)p[1];
-  c->in.alpha = (const float *)p[2];
-  c->in.beta = (const float *)p[3];
-  c->in.gamma = (const float *)p[4];
-  c->in.delta = (const float *)p[5];
-  c->in.t_itl = (const float *)p[6];
-  c->in.t_ttft = (const float *)p[7];
-  c->in.t_tps = (const float *)p[8];
-  c->in.acc_cost = (const float *)p[9];
-  c->out.feasible = (uint8_t *)p[10];
-  c->out.zero_empty = (uint8_t *)p[11];
-  c->out.num_replicas = (int *)p[12];
-  c->out.batch = (int *)p[13];
-  c->out.cost = (float *)p[14];
-  c->out.value = (float *)p[15];
-  c->out.itl = (float *)p[16];
-  c->out.ttft = (float *)p[17];
-  c->out.rho = (float *)p[18];
-  c->out.max_rate = (float *)p[19];
-  c->seg_start = (const int *)p[20];
-  c->winner = (int *)p[21];
-  c->cell_acc = (const int *)p[22];
-  c->gather = p[23];
-  c->dev_dyn = p[0];
-  c->pin_dyn = p[24];
-  c->pin_out = p[25];
-  bool ok = hipStreamCreateWithFlags(&c->s0, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreateWithFlags(&c->e_up, hipEventDisableTiming) == hipSuccess;
-  for (int i = 0; ok && i < WVA_MAX_BUCKETS - 1; ++i)
-    ok = hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking) == hipSuccess &&
-         hipEventCreateWithFlags(&c->e_b[i], hipEventDisableTiming) == hipSuccess;
-  if (!ok) {
-    delete c;
-    return nullptr;
-  }
-  // sizing memo: INFERNO_SIZING_MEMO=0 is the kill switch (A/B measurement,
-  // tests) — read per call, never cached. Any failure here leaves the memo
-  // off; the context itself is still good.
-  const char *memo_env = getenv("INFERNO_SIZING_MEMO");
-  const bool memo_on = !(memo_env != nullptr && memo_env[0] == '0' && memo_env[1] == '\0');
-  if (memo_on && n_cells > 0) {
-    // allocate on the device that owns dev_dyn (the kernels' inputs)
-    int prev_dev = -1, dev = -1;
-    hipPointerAttribute_t attr;
-    if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
-    if (hipPointerGetAttributes(&attr, p[0]) == hipSuccess) dev = attr.device;
-    const bool switched = dev >= 0 && prev_dev >= 0 && dev != prev_dev &&
-                          hipSetDevice(dev) == hipSuccess;
-    const size_t bytes = (size_t)n_cells * sizeof(WvaMemoRec) + 2 * sizeof(unsigned);
-    void *m = nullptr;
-    if (hipMalloc(&m, bytes) == hipSuccess && m != nullptr) {
-      if (hipMemsetAsync(m, 0, bytes, c->s0) == hipSuccess) {
-        c->memo = (WvaMemoRec *)m;
-        c->memo_cnt = (unsigned *)((char *)m + (size_t)n_cells * sizeof(WvaMemoRec));
-      } else {
-        (void)hipFree(m);
-      }
-    }
-    if (c->memo == nullptr) (void)hipGetLastError();  // clear the non-fatal error
-    if (switched) (void)hipSetDevice(prev_dev);
-  }
-  return c;
-}
-
-// hit/miss counters of the sizing memo since the context was created
-// (unsigned, wrapping). Synchronous small D2H — diagnostics only, never on
-// the hot path. Returns 1 when the memo is off, <0 on a runtime error.
-extern "C" int wva_ctx_memo_stats(void *ctx, unsigned *hits, unsigned *misses) {
-  WvaCtx *c = (WvaCtx *)ctx;
-  if (c == nullptr || c->memo == nullptr) return 1;
-  unsigned h[2] = {0u, 0u};
-  if (hipStreamSynchronize(c->s0) != hipSuccess) return -1;
-  if (hipMemcpy(h, c->memo_cnt, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -2;
-  if (hits) *hits = h[0];
-  if (misses) *misses = h[1];
-  return 0;
-}
-
-// The static per-cell topology wva_ctx_tick stages from, five host int32
-// arrays of n_cells each (copied): the cell's server, its accelerator index,
-// the profile's maxBatchSize and atTokens, the server's batch override.
-extern "C" int wva_ctx_set_topology(void *ctx, const int *cell_server, const int *cell_acc_idx,
-                                    const int *perf_max_batch_cfg, const int *at_tokens,
-                                    const int *override_n) {
-  WvaCtx *c = (WvaCtx *)ctx;
-  if (c == nullptr) return -1;
-  const size_t n = (size_t)c->n_cells;
-  if (n > 0 && (cell_server == nullptr || cell_acc_idx == nullptr ||
-                perf_max_batch_cfg == nullptr || at_tokens == nullptr || override_n == nullptr))
-    return -1;
-  for (size_t k = 0; k < n; ++k)
-    if (cell_server[k] < 0 || cell_server[k] >= c->n_srv) return -2;
-  if (c->topo == nullptr) {
-    c->topo = (int *)malloc((6 * n + 1) * sizeof(int));
-    if (c->topo == nullptr) return -3;
-  }
-  const int *src[5] = {cell_server, cell_acc_idx, perf_max_batch_cfg, at_tokens, override_n};
-  for (int r = 0; r < 5; ++r)
-    if (n > 0) memcpy(c->topo + r * n, src[r], n * sizeof(int));
-  c->topo_cell_server = c->topo + 0 * n;
-  c->topo_cell_acc = c->topo + 1 * n;
-  c->topo_cfg = c->topo + 2 * n;
-  c->topo_at_tokens = c->topo + 3 * n;
-  c->topo_override = c->topo + 4 * n;
-  c->bucket_batch_n = c->topo + 5 * n;
-  c->bucket_batch_valid = 0;
-  return 0;
-}
-
-// batch_n (may be null): the host batch_n row [n_cells] the layout was chosen
-// for. It is recorded; wva_ctx_tick reports a stale layout when a tick's
-// batch_n differs from it (or when none was recorded).
-extern "C" int wva_ctx_set_buckets(void *ctx, int n_buckets, const int *nts,
-                                   const void **cell_ids, const int *n_blocks,
-                                   const int *max_ns, int analyzer_mode, float cv2,
-                                   const void **g_invs, const void **g_anchors,
-                                   const int *batch_n) {
-  WvaCtx *c = (WvaCtx *)ctx;
-  if (n_buckets < 0 || n_buckets > WVA_MAX_BUCKETS) return -1;
-  c->bucket_batch_valid = 0;
-  if (batch_n != nullptr && c->topo != nullptr) {
-    if (c->n_cells > 0) memcpy(c->bucket_batch_n, batch_n, (size_t)c->n_cells * sizeof(int));
-    c->bucket_batch_valid = 1;
-  }
-  c->n_buckets = n_buckets;
-  for (int i = 0; i < n_buckets; ++i) {
-    c->buckets[i].nt = nts[i];
-    c->buckets[i].cell_ids = (const int *)cell_ids[i];
-    c->buckets[i].n_blocks = n_blocks[i];
-    c->buckets[i].max_n = max_ns[i];
-    c->buckets[i].g_inv = g_invs ? (float *)g_invs[i] : nullptr;
-    c->buckets[i].g_anchor = g_anchors ? (double *)g_anchors[i] : nullptr;
-  }
-  c->analyzer_mode = analyzer_mode;
-  c->cv2 = cv2;
-  // bucket layout / analyzer change: drop the captured pipeline (unless
-  // capture already proved unsupported, which is sticky)
-  if (c->graph_state == 1) (void)hipGraphExecDestroy(c->graph_exec);
-  if (c->graph_state != -1) c->graph_state = 0;
-  return 0;
-}
-
-static int wva_launch_bucket_on(WvaCtx *c, const WvaBucket &b, hipStream_t s) {
-  return wva_sweep_dispatch(b.n_blocks, b.max_n, b.nt, b.cell_ids, c->analyzer_mode, c->cv2, s,
-                            c->in, c->out, b.g_inv, b.g_anchor, c->memo, c->memo_cnt);
-}
-
-// enqueue the whole per-tick pipeline on the ctx's streams (used both for
-// eager execution and for stream capture into a hipGraph)
-static int wva_enqueue_pipeline(WvaCtx *c) {
-  hipError_t err;
-  // 1. dynamic H2D (pinned -> device), the whole block in one copy
-  err = hipMemcpyAsync(c->dev_dyn, c->pin_dyn, (size_t)WVA_DYN_ROWS * c->n_cells * 4,
-                       hipMemcpyHostToDevice, c->s0);
-  if (err != hipSuccess) return (int)err;
-  if (hipEventRecord(c->e_up, c->s0) != hipSuccess) return -10;
-
-  // 2. bucket launches: bucket 0 on s0; others overlap on side streams after
-  // the upload event
-  for (int i = 0; i < c->n_buckets; ++i) {
-    hipStream_t s = (i == 0) ? c->s0 : c->side[i - 1];
-    if (i > 0 && hipStreamWaitEvent(s, c->e_up, 0) != hipSuccess) return -11;
-    int rc = wva_launch_bucket_on(c, c->buckets[i], s);
-    if (rc != 0) return rc;
-    if (i > 0 && hipEventRecord(c->e_b[i - 1], s) != hipSuccess) return -12;
-  }
-  for (int i = 1; i < c->n_buckets; ++i)
-    if (hipStreamWaitEvent(c->s0, c->e_b[i - 1], 0) != hipSuccess) return -14;
-
-  // 3. winner selection + winner records on s0, one launch
-  hipLaunchKernelGGL(wva_winner, dim3(c->n_srv), dim3(WVA_WAVE), 0, c->s0, c->out.value,
-                     c->out.feasible, c->out.zero_empty, c->cell_acc, c->out.num_replicas,
-                     c->out.batch, c->out.cost, c->out.itl, c->out.ttft, c->out.rho,
-                     c->out.max_rate, c->seg_start, c->n_srv, c->gather, c->winner);
-  err = hipGetLastError();
-  if (err != hipSuccess) return (int)err;
-
-  // 4. D2H of the winner records, one copy
-  err = hipMemcpyAsync(c->pin_out, c->gather, (size_t)WVA_REC_ROWS * c->n_srv * 4,
-                       hipMemcpyDeviceToHost, c->s0);
-  if (err != hipSuccess) return (int)err;
-  return 0;
-}
-
-// One reconcile tick behind one call: stage the six per-server arrays
-// ([n_srv] each; cur_acc -3 none, -1 empty, >= 0 accelerator index) into the
-// pinned dynamic block, then
-//   launch != 0: if the tick's batch_n equals the row the bucket layout was
-//     set for, run the pipeline and synchronise (returns 0, or a negative /
-//     HIP error code); otherwise launch nothing and return WVA_TICK_STALE.
-//     The caller then reads batch_n from the pinned block, calls
-//     wva_ctx_set_buckets and wva_reconcile, which runs the staged tick.
-//   launch == 0: stage only (the planning passes); returns 0 or
-//     WVA_TICK_STALE by the same comparison.
-// zero_arrival (may be null) replaces arrival in the zero-load decision.
-extern "C" int wva_reconcile(void *ctx);
-extern "C" int wva_ctx_tick(void *ctx, const float *arrival, const int *in_tok, const int *out_tok,
-                            const int *cur_acc, const int *cur_rep, const float *cur_cost,
-                            const float *zero_arrival, int launch) {
-  WvaCtx *c = (WvaCtx *)ctx;
-  if (c == nullptr || c->topo == nullptr) return -41;
-  int changed = 1;
-  const int rc = wva_stage_dynamic(
-      c->n_srv, c->n_cells, arrival, in_tok, out_tok, cur_acc, cur_rep, cur_cost, zero_arrival,
-      c->topo_cell_server, c->topo_cell_acc, c->topo_cfg, c->topo_at_tokens, c->topo_override,
-      c->pin_dyn, c->bucket_batch_valid ? c->bucket_batch_n : nullptr, &changed);
-  if (rc != 0) return -42;
-  if (changed) return WVA_TICK_STALE;
-  return launch ? wva_reconcile(ctx) : 0;
-}
-
-extern "C" int wva_reconcile(void *ctx) {
-  WvaCtx *c = (WvaCtx *)ctx;
-  // replay the captured pipeline when available: every buffer pointer and
-  // kernel argument is ctx-stable between ticks, so the graph stays valid
-  // until the bucket layout changes (set_buckets invalidates)
-  if (c->graph_state == 1) {
-    if (hipGraphLaunch(c->graph_exec, c->s0) != hipSuccess) {
-      (void)hipGraphExecDestroy(c->graph_exec);
-      c->graph_state = -1;  // fall back to eager permanently
-    } else {
-      return (int)hipStreamSynchronize(c->s0);
-    }
-  }
-  if (c->graph_state == 0) {
-    // OPT-IN (INFERNO_HIPGRAPH=1): measured SLOWER than eager on MI355X for
-    // this pipeline (0.55 vs 0.45 ms/step, same-box x3) — graph replay does
-    // not preserve the 4-HW-queue bucket overlap the eager path gets. Kept
-    // as an option for launch-bound configurations (many tiny buckets).
-    static int enabled = -1;
-    if (enabled < 0) enabled = getenv("INFERNO_HIPGRAPH") != nullptr ? 1 : 0;
-    if (!enabled) c->graph_state = -1;
-  }
-  if (c->graph_state == 0) {
-    // capture once: the side-stream forks/joins via events become graph
-    // dependencies (capture mode relaxed — no other thread uses these
-    // streams)
-    hipGraph_t graph = nullptr;
-    bool ok = hipStreamBeginCapture(c->s0, hipStreamCaptureModeRelaxed) == hipSuccess;
-    int rc = ok ? wva_enqueue_pipeline(c) : -20;
-    if (ok) {
-      if (hipStreamEndCapture(c->s0, &graph) != hipSuccess) ok = false;
-    }
-    if (ok && rc == 0 && graph != nullptr &&
-        hipGraphInstantiate(&c->graph_exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-      c->graph_state = 1;
-      (void)hipGraphDestroy(graph);
-      if (hipGraphLaunch(c->graph_exec, c->s0) == hipSuccess)
-        return (int)hipStreamSynchronize(c->s0);
-      (void)hipGraphExecDestroy(c->graph_exec);
-      c->graph_state = -1;
-    } else {
-      if (graph != nullptr) (void)hipGraphDestroy(graph);
-      c->graph_state = -1;  // capture unsupported here: stay eager
-      // a failed capture may have left the stream in capture state; make
-      // sure it is usable again
-      hipStreamCaptureStatus st;
-      if (hipStreamIsCapturing(c->s0, &st) == hipSuccess &&
-          st != hipStreamCaptureStatusNone) {
-        hipGraph_t dead = nullptr;
-        (void)hipStreamEndCapture(c->s0, &dead);
-        if (dead != nullptr) (void)hipGraphDestroy(dead);
-      }
-    }
-  }
-  int rc = wva_enqueue_pipeline(c);
-  if (rc != 0) return rc;
-  return (int)hipStreamSynchronize(c->s0);
-}
-
-// ---------------------------------------------------------------------------
-// Scenario planning: S arrival-rate scenarios of the whole fleet in one pass.
-// Shares the context's static arrays, dynamic int arrays, buckets and sizing
-// memo with wva_reconcile; owns only the scenario arrivals, the [S][n_cells]
-// outputs and the reduce outputs. The hipGraph path is not involved.
-// ---------------------------------------------------------------------------
-#define WVA_PLAN_MAX_S 256
-
-static void wva_plan_release(WvaCtx *c) {
-  if (c->plan_dev != nullptr) (void)hipFree(c->plan_dev);
-  if (c->plan_pin != nullptr) (void)hipHostFree(c->plan_pin);
-  c->plan_dev = nullptr;
-  c->plan_pin = nullptr;
-  c->plan_cap = 0;
-  c->plan_acc_cap = 0;
-  c->plan_s = 0;
-}
-
-static size_t wva_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// (re)allocate the planning buffers for n_scen scenarios and n_acc
-// accelerators; on failure nothing is held and the context is otherwise intact
-static int wva_plan_reserve(WvaCtx *c, int n_scen, int n_acc) {
-  if (n_scen <= c->plan_cap && n_acc <= c->plan_acc_cap) return 0;
-  const int cap = n_scen > c->plan_cap ? n_scen : c->plan_cap;
-  const int acap = n_acc > c->plan_acc_cap ? n_acc : c->plan_acc_cap;
-  wva_plan_release(c);
-  const size_t cells = (size_t)cap * (size_t)c->n_cells;
-  const size_t b_scen = wva_align256(cells * sizeof(float));
-  const size_t b_w = wva_align256(cells * 4);  // one 4-byte per-cell array
-  const size_t b_b = wva_align256(cells);      // one 1-byte per-cell array
-  const size_t b_pf = wva_align256((size_t)cap * 6 * c->n_srv * sizeof(float));
-  const size_t b_pi = wva_align256((size_t)cap * 4 * c->n_srv * sizeof(int));
-  const size_t b_tot = wva_align256((size_t)cap * acap * sizeof(unsigned long long));
-  const size_t dev_bytes = b_scen + 8 * b_w + 2 * b_b + b_pf + b_pi + b_tot;
-  const size_t pin_bytes = b_scen + b_pf + b_pi + b_tot;
-
-  int prev_dev = -1, dev = -1;
-  hipPointerAttribute_t attr;
-  if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
-  if (hipPointerGetAttributes(&attr, c->dev_dyn) == hipSuccess) dev = attr.device;
-  const bool switched = dev >= 0 && prev_dev >= 0 && dev != prev_dev &&
-                        hipSetDevice(dev) == hipSuccess;
-  void *d = nullptr, *h = nullptr;
-  bool ok = hipMalloc(&d, dev_bytes) == hipSuccess && d != nullptr;
-  ok = ok && hipHostMalloc(&h, pin_bytes, hipHostMallocDefault) == hipSuccess && h != nullptr;
-  // infeasible cells write only their two flags; start from zeros so the
-  // other fields of such cells are defined
-  ok = ok && hipMemsetAsync(d, 0, dev_bytes, c->s0) == hipSuccess;
-  if (switched) (void)hipSetDevice(prev_dev);
-  if (!ok) {
-    if (d != nullptr) (void)hipFree(d);
-    if (h != nullptr) (void)hipHostFree(h);
-    (void)hipGetLastError();  // the context stays usable for wva_reconcile
-    return -30;
-  }
-  c->plan_dev = d;
-  c->plan_pin = h;
-  c->plan_cap = cap;
-  c->plan_acc_cap = acap;
-  char *q = (char *)d;
-  c->plan_scen = (float *)q;             q += b_scen;
-  c->plan_out.num_replicas = (int *)q;   q += b_w;
-  c->plan_out.batch = (int *)q;          q += b_w;
-  c->plan_out.cost = (float *)q;         q += b_w;
-  c->plan_out.value = (float *)q;        q += b_w;
-  c->plan_out.itl = (float *)q;          q += b_w;
-  c->plan_out.ttft = (float *)q;         q += b_w;
-  c->plan_out.rho = (float *)q;          q += b_w;
-  c->plan_out.max_rate = (float *)q;     q += b_w;
-  c->plan_out.feasible = (uint8_t *)q;   q += b_b;
-  c->plan_out.zero_empty = (uint8_t *)q; q += b_b;
-  c->plan_pf = (float *)q;               q += b_pf;
-  c->plan_pi = (int *)q;                 q += b_pi;
-  c->plan_tot = (unsigned long long *)q;
-  q = (char *)h;
-  c->plan_pin_scen = (float *)q;         q += b_scen;
-  c->plan_pin_pf = (float *)q;           q += b_pf;
-  c->plan_pin_pi = (int *)q;             q += b_pi;
-  c->plan_pin_tot = (unsigned long long *)q;
-  return 0;
-}
-
-// One planning pass. scen_arrival: host, [n_scen][n_cells] fp32 (req/min).
-// The caller has filled the context's pinned dynamic arrays and set the
-// buckets, exactly as for wva_reconcile. On success the three out pointers
-// name the context's pinned result buffers, valid until the next
-// wva_ctx_plan or wva_ctx_destroy: pf [n_scen][6][n_srv] fp32 (cost, value,
-// itl, ttft, rho, max_rate), pi [n_scen][4][n_srv] i32 (acc code, replicas,
-// batch, winner cell), totals [n_scen][n_acc] u64.
-//
-// lim == nullptr is the unlimited plan (wva_ctx_plan). With lim, step 3 is
-// wva_plan_greedy instead of wva_plan_reduce and the capacity rows go up and
-// come back (wva_ctx_plan_limited); everything else is the same pass.
-struct WvaLimArgs {
-  int n_types;
-  const int *capacity;  // host [n_scen][n_types]
-  int delayed;
-  int policy;
-};
-
-static void wva_lim_release(WvaCtx *c) {
-  if (c->lim_dev != nullptr) (void)hipFree(c->lim_dev);
-  if (c->lim_pin != nullptr) (void)hipHostFree(c->lim_pin);
-  c->lim_dev = nullptr;
-  c->lim_pin = nullptr;
-  c->lim_cap = 0;
-  c->lim_types_cap = 0;
-}
-
-// (re)allocate the greedy workspace for n_scen scenarios and n_types
-// accelerator types; on failure nothing is held and reconciles and unlimited
-// plans keep working
-static int wva_lim_reserve(WvaCtx *c, int n_scen, int n_types) {
-  if (n_scen <= c->lim_cap && n_types <= c->lim_types_cap) return 0;
-  const int cap = n_scen > c->lim_cap ? n_scen : c->lim_cap;
-  const int tcap = n_types > c->lim_types_cap ? n_types : c->lim_types_cap;
-  wva_lim_release(c);
-  const size_t b_wsd =
-      wva_align256((size_t)cap * ((size_t)c->n_srv + (size_t)c->n_cells) * sizeof(double));
-  const size_t b_wsi = wva_align256((size_t)cap *
-                                    ((size_t)15 * c->n_srv + (size_t)3 * c->n_cells) * sizeof(int));
-  const size_t b_cap = wva_align256((size_t)cap * tcap * sizeof(int));
-  const size_t b_px = wva_align256((size_t)cap * 2 * c->n_srv * sizeof(int));
-  const size_t dev_bytes = b_wsd + b_wsi + b_cap + b_px;
-  const size_t pin_bytes = b_cap + b_px;
-
-  int prev_dev = -1, dev = -1;
-  hipPointerAttribute_t attr;
-  if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
-  if (hipPointerGetAttributes(&attr, c->dev_dyn) == hipSuccess) dev = attr.device;
-  const bool switched = dev >= 0 && prev_dev >= 0 && dev != prev_dev &&
-                        hipSetDevice(dev) == hipSuccess;
-  void *d = nullptr, *h = nullptr;
-  bool ok = hipMalloc(&d, dev_bytes) == hipSuccess && d != nullptr;
-  ok = ok && hipHostMalloc(&h, pin_bytes, hipHostMallocDefault) == hipSuccess && h != nullptr;
-  if (switched) (void)hipSetDevice(prev_dev);
-  if (!ok) {
-    if (d != nullptr) (void)hipFree(d);
-    if (h != nullptr) (void)hipHostFree(h);
-    (void)hipGetLastError();
-    return -34;
-  }
-  c->lim_dev = d;
-  c->lim_pin = h;
-  c->lim_cap = cap;
-  c->lim_types_cap = tcap;
-  char *q = (char *)d;
-  c->lim_wsd = (double *)q;       q += b_wsd;
-  c->lim_wsi = (int *)q;          q += b_wsi;
-  c->lim_capacity = (int *)q;     q += b_cap;
-  c->lim_px = (int *)q;
-  q = (char *)h;
-  c->lim_pin_capacity = (int *)q; q += b_cap;
-  c->lim_pin_px = (int *)q;
-  return 0;
-}
-
-// Static inputs of wva_plan_greedy: host cell_type, cell_units [n_cells] and
-// srv_prio [n_srv]. Synchronous upload; the caller repeats it only when one
-// of the arrays changed.
-extern "C" int wva_ctx_set_greedy_static(void *ctx, const int *cell_type, const int *cell_units,
-                                         const int *srv_prio) {
-  WvaCtx *c = (WvaCtx *)ctx;
-  if (c == nullptr || cell_type == nullptr || cell_units == nullptr || srv_prio == nullptr)
-    return -31;
-  if (c->n_cells <= 0 || c->n_srv <= 0) return -33;
-  const size_t b_c = wva_align256((size_t)c->n_cells * sizeof(int));
-  const size_t b_s = wva_align256((size_t)c->n_srv * sizeof(int));
-  if (c->lim_static == nullptr) {
-    int prev_dev = -1, dev = -1;
-    hipPointerAttribute_t attr;
-    if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
-    if (hipPointerGetAttributes(&attr, c->dev_dyn) == hipSuccess) dev = attr.device;
-    const bool switched = dev >= 0 && prev_dev >= 0 && dev != prev_dev &&
-                          hipSetDevice(dev) == hipSuccess;
-    void *d = nullptr;
-    const bool ok = hipMalloc(&d, 2 * b_c + b_s) == hipSuccess && d != nullptr;
-    if (switched) (void)hipSetDevice(prev_dev);
-    if (!ok) {
-      (void)hipGetLastError();
-      return -34;
-    }
-    c->lim_static = d;
-    c->lim_cell_type = (const int *)d;
-    c->lim_cell_units = (const int *)((char *)d + b_c);
-    c->lim_srv_prio = (const int *)((char *)d + 2 * b_c);
-  }
-  if (hipStreamSynchronize(c->s0) != hipSuccess) return -1;
-  char *d = (char *)c->lim_static;
-  if (hipMemcpy(d, cell_type, (size_t)c->n_cells * sizeof(int), hipMemcpyHostToDevice) !=
-          hipSuccess ||
-      hipMemcpy(d + b_c, cell_units, (size_t)c->n_cells * sizeof(int), hipMemcpyHostToDevice) !=
-          hipSuccess ||
-      hipMemcpy(d + 2 * b_c, srv_prio, (size_t)c->n_srv * sizeof(int), hipMemcpyHostToDevice) !=
-          hipSuccess)
-    return -2;
-  return 0;
-}
-
-static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arrival,
-                        const WvaLimArgs *lim, const void **out_pf, const void **out_pi,
-                        const void **out_totals) {
-  if (c == nullptr || scen_arrival == nullptr) return -31;
-  if (n_scen < 1 || n_scen > WVA_PLAN_MAX_S || n_acc < 1) return -32;
-  if (c->n_cells <= 0 || c->n_srv <= 0) return -33;
-  c->plan_s = 0;
-  int rc = wva_plan_reserve(c, n_scen, n_acc);
-  if (rc != 0) return rc;
-  if (lim != nullptr) {
-    rc = wva_lim_reserve(c, n_scen, lim->n_types);
-    if (rc != 0) return rc;
-  }
-  const size_t cells = (size_t)n_scen * (size_t)c->n_cells;
-  hipError_t err;
-
-  // 1. uploads: scenario arrivals through the pinned staging buffer, then the
-  // dynamic arrays as wva_enqueue_pipeline does
-  for (size_t i = 0; i < cells; ++i) c->plan_pin_scen[i] = scen_arrival[i];
-  err = hipMemcpyAsync(c->plan_scen, c->plan_pin_scen, cells * sizeof(float),
-                       hipMemcpyHostToDevice, c->s0);
-  if (err != hipSuccess) return (int)err;
-  err = hipMemcpyAsync(c->dev_dyn, c->pin_dyn, (size_t)WVA_DYN_ROWS * c->n_cells * 4,
-                       hipMemcpyHostToDevice, c->s0);
-  if (err != hipSuccess) return (int)err;
-  err = hipMemsetAsync(c->plan_tot, 0, (size_t)n_scen * n_acc * sizeof(unsigned long long),
-                       c->s0);
-  if (err != hipSuccess) return (int)err;
-  const size_t n_capacity = lim != nullptr ? (size_t)n_scen * (size_t)lim->n_types : 0;
-  if (lim != nullptr) {
-    for (size_t i = 0; i < n_capacity; ++i) c->lim_pin_capacity[i] = lim->capacity[i];
-    err = hipMemcpyAsync(c->lim_capacity, c->lim_pin_capacity, n_capacity * sizeof(int),
-                         hipMemcpyHostToDevice, c->s0);
-    if (err != hipSuccess) return (int)err;
-  }
-  if (hipEventRecord(c->e_up, c->s0) != hipSuccess) return -10;
-
-  // 2. planning buckets: same streams, fork/join and order as the reconcile
-  const WvaPlanArgs pa = {c->n_cells, n_scen, c->plan_scen};
-  for (int i = 0; i < c->n_buckets; ++i) {
-    hipStream_t s = (i == 0) ? c->s0 : c->side[i - 1];
-    if (i > 0 && hipStreamWaitEvent(s, c->e_up, 0) != hipSuccess) return -11;
-    const WvaBucket &b = c->buckets[i];
-    rc = wva_sweep_dispatch(b.n_blocks, b.max_n, b.nt, b.cell_ids, c->analyzer_mode, c->cv2, s,
-                            c->in, c->plan_out, b.g_inv, b.g_anchor, c->memo, c->memo_cnt, &pa);
-    if (rc != 0) return rc;
-    if (i > 0 && hipEventRecord(c->e_b[i - 1], s) != hipSuccess) return -12;
-  }
-  for (int i = 1; i < c->n_buckets; ++i)
-    if (hipStreamWaitEvent(c->s0, c->e_b[i - 1], 0) != hipSuccess) return -14;
-
-  // 3. winners, records and totals for all (server, scenario) pairs
-  if (lim == nullptr) {
-    hipLaunchKernelGGL(wva_plan_reduce, dim3(c->n_srv, n_scen), dim3(WVA_WAVE), 0, c->s0,
-                       c->plan_out.value, c->plan_out.feasible, c->plan_out.zero_empty,
-                       c->cell_acc, c->plan_out.num_replicas, c->plan_out.batch, c->plan_out.cost,
-                       c->plan_out.itl, c->plan_out.ttft, c->plan_out.rho, c->plan_out.max_rate,
-                       c->seg_start, c->n_srv, c->n_cells, n_scen, n_acc, c->plan_pf, c->plan_pi,
-                       c->plan_tot);
-  } else {
-    size_t lds = wva_greedy_lds_bytes(c->n_srv, c->n_cells);
-    if (lds > c->lim_lds_budget ||
-        wva_optin_lds(reinterpret_cast<const void *>(&wva_plan_greedy), lds) != 0) {
-      (void)hipGetLastError();
-      lds = 0;  // hot state in the global workspace
-    }
-    hipLaunchKernelGGL(wva_plan_greedy, dim3(n_scen), dim3(WVA_WAVE), lds, c->s0,
-                       c->plan_out.value, c->plan_out.feasible, c->plan_out.zero_empty,
-                       c->cell_acc, c->plan_out.num_replicas, c->plan_out.batch, c->plan_out.cost,
-                       c->plan_out.itl, c->plan_out.ttft, c->plan_out.rho, c->plan_out.max_rate,
-                       c->seg_start, c->lim_cell_type, c->lim_cell_units, c->lim_srv_prio,
-                       c->n_srv, c->n_cells, n_scen, n_acc, lim->n_types, lim->delayed,
-                       lim->policy, lds > 0 ? 1 : 0, c->lim_capacity, c->lim_wsi, c->lim_wsd, c->plan_pf,
-                       c->plan_pi, c->lim_px, c->plan_tot);
-  }
-  err = hipGetLastError();
-  if (err != hipSuccess) return (int)err;
-  if (lim != nullptr) {
-    err = hipMemcpyAsync(c->lim_pin_capacity, c->lim_capacity, n_capacity * sizeof(int),
-                         hipMemcpyDeviceToHost, c->s0);
-    if (err != hipSuccess) return (int)err;
-    err = hipMemcpyAsync(c->lim_pin_px, c->lim_px, (size_t)n_scen * 2 * c->n_srv * sizeof(int),
-                         hipMemcpyDeviceToHost, c->s0);
-    if (err != hipSuccess) return (int)err;
-  }
-
-  // 4. downloads
-  err = hipMemcpyAsync(c->plan_pin_pf, c->plan_pf, (size_t)n_scen * 6 * c->n_srv * sizeof(float),
-                       hipMemcpyDeviceToHost, c->s0);
-  if (err != hipSuccess) return (int)err;
-  err = hipMemcpyAsync(c->plan_pin_pi, c->plan_pi, (size_t)n_scen * 4 * c->n_srv * sizeof(int),
-                       hipMemcpyDeviceToHost, c->s0);
-  if (err != hipSuccess) return (int)err;
-  err = hipMemcpyAsync(c->plan_pin_tot, c->plan_tot,
-                       (size_t)n_scen * n_acc * sizeof(unsigned long long),
-                       hipMemcpyDeviceToHost, c->s0);
-  if (err != hipSuccess) return (int)err;
-  err = hipStreamSynchronize(c->s0);
-  if (err != hipSuccess) return (int)err;
-  c->plan_s = n_scen;
-  if (out_pf) *out_pf = c->plan_pin_pf;
-  if (out_pi) *out_pi = c->plan_pin_pi;
-  if (out_totals) *out_totals = c->plan_pin_tot;
-  return 0;
-}
-
-extern "C" int wva_ctx_plan(void *ctx, int n_scen, int n_acc, const float *scen_arrival,
-                            const void **out_pf, const void **out_pi,
-                            const void **out_totals) {
-  return wva_plan_run((WvaCtx *)ctx, n_scen, n_acc, scen_arrival, nullptr, out_pf, out_pi,
-                      out_totals);
-}
-
-// One capacity-limited planning pass: wva_ctx_plan's uploads and buckets, then
-// one greedy solve per scenario on the device. capacity: host, [n_scen]
-// [n_types] int32 units per accelerator type. policy: 0 None,
-// 1 PriorityExhaustive, 2 PriorityRoundRobin, 3 RoundRobin. The static inputs
-// must have been set (wva_ctx_set_greedy_static). pf, pi and totals are as for
-// wva_ctx_plan, holding the limited solution (pi row 0 is the granted
-// accelerator or -1, row 1 the granted replicas). out_px: pinned i32 [n_scen]
-// [2][n_srv] (the granted cell's pre-cut replicas; the server's feasible
-// candidates that are not zero-load). out_capacity: pinned i32 [n_scen]
-// [n_types], the capacity left.
-extern "C" int wva_ctx_plan_limited(void *ctx, int n_scen, int n_acc, const float *scen_arrival,
-                                    int n_types, const int *capacity, int delayed, int policy,
-                                    const void **out_pf, const void **out_pi,
-                                    const void **out_totals, const void **out_px,
-                                    const void **out_capacity) {
-  WvaCtx *c = (WvaCtx *)ctx;
-  if (c == nullptr || capacity == nullptr) return -31;
-  if (n_types < 1 || policy < 0 || policy > 3) return -32;
-  if (c->lim_static == nullptr) return -35;
-  const WvaLimArgs lim = {n_types, capacity, delayed ? 1 : 0, policy};
-  const int rc = wva_plan_run(c, n_scen, n_acc, scen_arrival, &lim, out_pf, out_pi, out_totals);
-  if (rc != 0) return rc;
-  if (out_px) *out_px = c->lim_pin_px;
-  if (out_capacity) *out_capacity = c->lim_pin_capacity;
-  return 0;
-}
-
-// Per-cell outputs of the last successful wva_ctx_plan, copied into ten host
-// arrays of plan_s * n_cells elements each, in WvaCellsOut order (feasible,
-// zero_empty: u8; num_replicas, batch: i32; cost, value, itl, ttft, rho,
-// max_rate: f32). Synchronous; inspection and tests, not the hot path.
-extern "C" int wva_ctx_plan_cells(void *ctx, void **dst) {
-  WvaCtx *c = (WvaCtx *)ctx;
-  if (c == nullptr || dst == nullptr || c->plan_s < 1) return -31;
-  const size_t cells = (size_t)c->plan_s * (size_t)c->n_cells;
-  const void *src[10] = {c->plan_out.feasible, c->plan_out.zero_empty, c->plan_out.num_replicas,
-                         c->plan_out.batch,    c->plan_out.cost,       c->plan_out.value,
-                         c->plan_out.itl,      c->plan_out.ttft,       c->plan_out.rho,
-                         c->plan_out.max_rate};
-  if (hipStreamSynchronize(c->s0) != hipSuccess) return -1;
-  for (int i = 0; i < 10; ++i) {
-    const size_t bytes = cells * (i < 2 ? 1 : 4);
-    if (hipMemcpy(dst[i], src[i], bytes, hipMemcpyDeviceToHost) != hipSuccess) return -2;
-  }
-  return 0;
-}
-
-extern "C" void wva_ctx_destroy(void *ctx) {
-  WvaCtx *c = (WvaCtx *)ctx;
-  if (c == nullptr) return;
-  if (c->graph_state == 1) (void)hipGraphExecDestroy(c->graph_exec);
-  (void)hipStreamDestroy(c->s0);
-  (void)hipEventDestroy(c->e_up);
-  for (int i = 0; i < WVA_MAX_BUCKETS - 1; ++i) {
-    (void)hipStreamDestroy(c->side[i]);
-    (void)hipEventDestroy(c->e_b[i]);
-  }
-  if (c->memo != nullptr) (void)hipFree(c->memo);
-  wva_plan_release(c);
-  wva_lim_release(c);
-  if (c->lim_static != nullptr) (void)hipFree(c->lim_static);
-  free(c->topo);
-  delete c;
-}

@@ -5,7 +5,8 @@
 // Random topologies and loads at 0, 1 and a few hundred cells; every output
 // buffer is allocated at its exact size so an out-of-bounds access trips the
 // sanitizer. Results are checked against a plain restatement of the rules.
-// Exits 0 when all is well.
+// Also checks the arena layout of wva_arena.h (the context's planning and
+// greedy buffers). Exits 0 when all is well.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -14,6 +15,7 @@
 #include <random>
 #include <vector>
 
+#include "wva_arena.h"
 #include "wva_stage.h"
 
 static int failures = 0;
@@ -188,8 +190,61 @@ static void check_aggregate(std::mt19937 &rng, int n_srv, int n_acc, int n_types
   delete[] csum;
 }
 
+// wva_arena_layout: offsets 256-aligned, segments disjoint and in table
+// order, total = the sum of the padded sizes; a zero-sized segment takes no
+// room. The table is written into a block of exactly `total` bytes, each
+// segment filled with its own index, so an overlap or an overrun shows.
+static void check_arena(const std::vector<size_t> &sizes) {
+  const int n = (int)sizes.size();
+  std::vector<size_t> off((size_t)n + 1, (size_t)-1);  // one spare slot: must stay untouched
+  const size_t total = wva_arena_layout(sizes.data(), n, off.data());
+  CHECK(off[(size_t)n] == (size_t)-1);
+  size_t want = 0;
+  for (int i = 0; i < n; ++i) {
+    CHECK(off[i] % 256 == 0);
+    CHECK(off[i] == want);  // in order, right behind the padded predecessor
+    CHECK(off[i] + sizes[i] <= (i + 1 < n ? off[i + 1] : total));  // disjoint
+    want += (sizes[i] + 255) / 256 * 256;
+  }
+  CHECK(total == want);
+  CHECK(total % 256 == 0);
+  unsigned char *block = new unsigned char[total + (total == 0 ? 1 : 0)];
+  for (int i = 0; i < n; ++i) std::memset(block + off[i], i + 1, sizes[i]);
+  for (int i = 0; i < n; ++i)
+    for (size_t k = 0; k < sizes[i]; ++k)
+      if (block[off[i] + k] != (unsigned char)(i + 1)) {
+        CHECK(!"segment overwritten by a later one");
+        break;
+      }
+  delete[] block;
+}
+
+static void check_arenas(std::mt19937 &rng) {
+  CHECK(wva_align256(0) == 0 && wva_align256(1) == 256 && wva_align256(255) == 256);
+  CHECK(wva_align256(256) == 256 && wva_align256(257) == 512);
+  size_t none = 12345;
+  CHECK(wva_arena_layout(nullptr, 0, &none) == 0 && none == 12345);  // empty table
+  const size_t edge[] = {0, 1, 255, 256, 257, 4096, 100001};
+  for (size_t a : edge) {
+    check_arena({a});
+    for (size_t b : edge) {
+      check_arena({a, b});
+      check_arena({a, 0, b, 0});
+      check_arena({0, 0, a, b, 1});
+    }
+  }
+  // the planning arena's shape: nine 4-byte and two 1-byte per-cell arrays, three tails
+  for (int rep = 0; rep < 50; ++rep) {
+    const size_t cells = rng() % 3000, pf = rng() % 5000, tot = rng() % 300;
+    std::vector<size_t> t(9, cells * 4);
+    t.insert(t.end(), {cells, cells, pf * 6, pf * 4, tot * 8});
+    check_arena(t);
+  }
+}
+
 int main() {
   std::mt19937 rng(20240607u);
+  check_arenas(rng);
   const int sizes[] = {0, 1, 2, 7, 64, 130, 300};
   for (int n_srv : sizes)
     for (int n_acc : {1, 3, 8})

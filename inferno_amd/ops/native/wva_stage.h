@@ -1,7 +1,8 @@
 // Shared by ops/native/stage.cpp, its stand-alone driver and
 // ops/hip/wva_kernels.hip: the layout of the dynamic block, the tick code and
 // the C ABI of the host-only staging and aggregation. ops/sweep.py mirrors
-// WVA_DYN_ROWS (DYN_ROWS) and WVA_TICK_STALE (TICK_STALE).
+// WVA_DYN_ROWS (DYN_ROWS) and WVA_TICK_STALE (TICK_STALE); load_library()
+// checks both against wva_abi().
 #ifndef WVA_STAGE_H
 #define WVA_STAGE_H
 

@@ -14,18 +14,38 @@ from typing import Optional
 
 from .build import LIB_PATH, build, needs_build
 
-MAX_N = 8192  # must match WVA_MAX_N in wva_kernels.hip (64KB-LDS limit)
-# XL LDS tier: fits CDNA4's 160 KiB LDS with the >64KB dynamic-LDS opt-in
-# (must match WVA_XL_MAX_N); override to MAX_N to force such cells to GMEM
-XL_MAX_N = int(os.environ.get("INFERNO_XL_MAX_N", "32768"))
-HUGE_MAX_N = 1 << 22  # must match WVA_HUGE_MAX_N (global-memory spill limit)
-PLAN_MAX_S = 256  # must match WVA_PLAN_MAX_S (scenarios per planning pass)
-# N-bucket thresholds (must match WVA_N_SMALL / WVA_N_MED): cells are
-# dispatched to 64- and 256-thread blocks by batch size — widths picked by
-# A/B measurement on MI355X (see choose_buckets); small/medium cells run one
-# barrier-free wave each, large-N cells get 4-wave blocks.
-N_SMALL = int(os.environ.get("INFERNO_N_SMALL", "512"))
-N_MED = int(os.environ.get("INFERNO_N_MED", "2048"))
+# Mirrors of the native library's constants, by their C names. load_library()
+# checks every one against wva_abi() once, so a drift fails loudly at load.
+_ABI = {
+    "WVA_MAX_N": 8192,  # 64KB-LDS limit
+    "WVA_XL_MAX_N": 32768,  # XL LDS tier (default)
+    "WVA_HUGE_MAX_N": 1 << 22,  # global-memory spill limit
+    "WVA_PLAN_MAX_S": 256,  # scenarios per planning pass
+    "WVA_N_SMALL": 512,  # N-bucket thresholds (defaults)
+    "WVA_N_MED": 2048,
+    "WVA_TICK_STALE": 1 << 20,  # wva_ctx_tick: layout stale, nothing launched
+    "WVA_DYN_ROWS": 8,  # rows of the dynamic block
+    "WVA_REC_ROWS": 10,  # rows of the winner-record block
+    "WVA_MAX_BUCKETS": 5,  # buckets a context holds (choose_buckets' regimes)
+}
+MAX_N = _ABI["WVA_MAX_N"]
+# XL LDS tier: fits CDNA4's 160 KiB LDS with the >64KB dynamic-LDS opt-in;
+# override to MAX_N to force such cells to GMEM
+XL_MAX_N = int(os.environ.get("INFERNO_XL_MAX_N", _ABI["WVA_XL_MAX_N"]))
+HUGE_MAX_N = _ABI["WVA_HUGE_MAX_N"]
+PLAN_MAX_S = _ABI["WVA_PLAN_MAX_S"]
+# N-bucket thresholds: cells are dispatched to 64- and 256-thread blocks by
+# batch size — widths picked by A/B measurement on MI355X (see
+# choose_buckets); small/medium cells run one barrier-free wave each, large-N
+# cells get 4-wave blocks. The env overrides are deliberate (A/B tuning).
+N_SMALL = int(os.environ.get("INFERNO_N_SMALL", _ABI["WVA_N_SMALL"]))
+N_MED = int(os.environ.get("INFERNO_N_MED", _ABI["WVA_N_MED"]))
+# the tick code of wva_ctx_tick for "the bucket layout does not fit the staged
+# batch_n, nothing was launched", and the block shapes of ops/native/wva_stage.h
+TICK_STALE = _ABI["WVA_TICK_STALE"]
+DYN_ROWS = _ABI["WVA_DYN_ROWS"]
+REC_ROWS = _ABI["WVA_REC_ROWS"]
+MAX_BUCKETS = _ABI["WVA_MAX_BUCKETS"]
 
 
 def choose_buckets(batch_n):
@@ -139,7 +159,15 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
             )
         build()
     lib = ctypes.CDLL(LIB_PATH)
-    lib.wva_sweep_launch.restype = ctypes.c_int
+    lib.wva_abi.restype = ctypes.c_int
+    lib.wva_abi.argtypes = [ctypes.c_char_p]
+    for name, mirror in _ABI.items():
+        native = lib.wva_abi(name.encode())
+        if native != mirror:
+            raise HipKernelError(
+                f"{name} is {native} in {LIB_PATH} but {mirror} in ops/sweep.py: "
+                "the library and the Python package are out of step"
+            )
     lib.wva_sweep_launch_bucket.restype = ctypes.c_int
     lib.wva_argmin_launch.restype = ctypes.c_int
     lib.wva_device_count.restype = ctypes.c_int
@@ -390,13 +418,6 @@ def run_greedy_native(cand_value, cand_acc_type, cand_units, cand_replicas,
     if rc != 0:
         raise HipKernelError(f"wva_greedy_solve failed: {rc}")
     return out_cand, out_reps
-
-
-# mirrors of ops/native/wva_stage.h: the tick code of wva_ctx_tick for "the
-# bucket layout does not fit the staged batch_n, nothing was launched"
-# (WVA_TICK_STALE) and the rows of the dynamic block (WVA_DYN_ROWS)
-TICK_STALE = 1 << 20
-DYN_ROWS = 8
 
 
 def run_stage_dynamic(arrival, in_tok, out_tok, cur_acc, cur_rep, cur_cost, cell_server,

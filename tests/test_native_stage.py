@@ -274,3 +274,40 @@ def check_world1(fast, slow):
         assert np.float64(a.cost).view(np.uint64) == np.float64(b.cost).view(np.uint64)
     assert fast.solution == slow.solution
     assert list(fast.solution) == list(slow.solution)
+
+
+def test_abi_constants_match_the_python_mirrors(ops):
+    """What wva_abi() reports is what ops/sweep.py and engine/native_ctx.py
+    assume (load_library has already refused a library where it is not), and
+    the dead one-shot entry points are gone from the library."""
+    import ctypes
+
+    from inferno_amd.engine import native_ctx
+
+    lib = ops.load_library()
+    got = {name: lib.wva_abi(name.encode()) for name in ops._ABI}
+    assert got == ops._ABI
+    assert got == {
+        "WVA_MAX_N": ops.MAX_N, "WVA_XL_MAX_N": 32768, "WVA_HUGE_MAX_N": ops.HUGE_MAX_N,
+        "WVA_PLAN_MAX_S": ops.PLAN_MAX_S, "WVA_N_SMALL": 512, "WVA_N_MED": 2048,
+        "WVA_TICK_STALE": ops.TICK_STALE, "WVA_DYN_ROWS": ops.DYN_ROWS,
+        "WVA_REC_ROWS": ops.REC_ROWS, "WVA_MAX_BUCKETS": ops.MAX_BUCKETS,
+    }
+    assert (ops.MAX_N, ops.HUGE_MAX_N, ops.PLAN_MAX_S) == (8192, 1 << 22, 256)
+    assert (ops.TICK_STALE, ops.DYN_ROWS, ops.REC_ROWS, ops.MAX_BUCKETS) == (1 << 20, 8, 10, 5)
+    assert lib.wva_abi(b"WVA_CTX_SLOTS") == len(native_ctx.CTX_SLOT_NAMES) == 26
+    assert len(set(native_ctx.CTX_SLOT_NAMES)) == 26
+    assert ops.DYN_ROWS == len(native_ctx.DYN_INT) + len(native_ctx.DYN_F32)
+    assert lib.wva_abi(b"WVA_NO_SUCH_CONSTANT") == -1 and lib.wva_abi(None) == -1
+    for gone in ("wva_gather", "wva_sweep_launch"):
+        with pytest.raises(AttributeError):
+            getattr(ctypes.CDLL(LIB_PATH), gone)
+    assert ctypes.CDLL(LIB_PATH).wva_sweep_launch_bucket is not None
+
+
+def test_abi_mismatch_is_refused_by_name(ops, monkeypatch):
+    ops.load_library()
+    monkeypatch.setattr(ops, "_lib", None)
+    monkeypatch.setitem(ops._ABI, "WVA_REC_ROWS", 11)
+    with pytest.raises(ops.HipKernelError, match="WVA_REC_ROWS"):
+        ops.load_library(allow_build=False)

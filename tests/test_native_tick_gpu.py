@@ -102,8 +102,8 @@ def test_winner_records_equal_host_argmin_and_gather():
         got = getattr(w, k)
         assert got.dtype == np.float32 and got.tobytes() == rec[k].tobytes(), k
     # the winner cell index: row 9 of the record block and the device array
-    assert fs._gpu["pin_out_np"][9].tobytes() == win.tobytes()
-    assert fs._gpu["winner"].cpu().numpy().tobytes() == win.tobytes()
+    assert fs._gpu.pin_out_np[9].tobytes() == win.tobytes()
+    assert fs._gpu.winner.cpu().numpy().tobytes() == win.tobytes()
 
 
 DYN_ROWS = ("in_tok", "out_tok", "batch_n", "perf_max_batch", "cur_replicas", "flags",
@@ -112,7 +112,7 @@ DYN_ROWS = ("in_tok", "out_tok", "batch_n", "perf_max_batch", "cur_replicas", "f
 
 def assert_staged_block(fs, want, what):
     """The pinned dynamic block the context staged against _refresh_dynamic()'s arrays."""
-    got = fs._gpu["pin_dyn_np"]
+    got = fs._gpu.pin_dyn_np
     assert got.shape == (len(DYN_ROWS), fs.n_cells)
     for j, k in enumerate(DYN_ROWS):
         ref = np.ascontiguousarray(want[k])
@@ -153,7 +153,7 @@ def one_tick(monkeypatch, load, cur):
     fs = FastSweep(system, backend="gpu")
     fs.load_override, fs.cur_override = load, cur
     w = fs.reconcile()
-    assert fs._gpu["tick_stale"], "a context's first tick must set its buckets"
+    assert fs._gpu.tick_stale, "a context's first tick must set its buckets"
     assert fs.memo_stats() is None
     monkeypatch.delenv("INFERNO_SIZING_MEMO")
     return w
@@ -174,13 +174,13 @@ def test_feedback_loop_across_layout_changes(monkeypatch):
         want_stale.append(prev_batch is None or not np.array_equal(batch_n, prev_batch))
         prev_batch = batch_n.copy()
         w = fs.reconcile()
-        stale.append(fs._gpu["tick_stale"])
+        stale.append(fs._gpu.tick_stale)
         assert_records_equal(w, one_tick(monkeypatch, load, cur), f"tick {tick}")
         assert (w.acc_idx[ZERO_SRV] == -2) == (tick == 2)
         cur = feed_back(cur, w)
     assert want_stale == [True, False, True, True]
     assert stale == want_stale
-    assert fs._gpu["stale_ticks"] == 3
+    assert fs._gpu.stale_ticks == 3
     hits, _ = fs.memo_stats()
     assert hits > 0, "the long-lived context never took a memo hit"
 
@@ -192,14 +192,14 @@ def test_no_stale_output_survives_a_tick():
     fs.load_override = (arrival, in_tok, out_tok)
     fs.cur_override = initial_cur(system, fs)
     first = fs.reconcile()
-    pin = fs._gpu["pin_out_np"]
+    pin = fs._gpu.pin_out_np
     assert pin.shape == (10, len(fs.server_names))
     pin[:] = SENTINEL
-    fs._gpu["pin_dyn_np"][:] = SENTINEL  # the staging block is rewritten in full, too
+    fs._gpu.pin_dyn_np[:] = SENTINEL  # the staging block is rewritten in full, too
     second = fs.reconcile()
-    assert not fs._gpu["tick_stale"]
+    assert not fs._gpu.tick_stale
     assert not (pin == SENTINEL).any(), "part of the winner block was not written"
-    assert not (fs._gpu["pin_dyn_np"] == SENTINEL).any()
+    assert not (fs._gpu.pin_dyn_np == SENTINEL).any()
     assert_records_equal(first, second, "same inputs")
     for f in dataclasses.fields(second):
         assert not (getattr(second, f.name).view(np.int32) == SENTINEL).any(), f.name

@@ -311,3 +311,46 @@ def test_limited_pass_leaves_no_state_behind():
     ra, rb = used.reconcile(), clean.reconcile()
     for f in WINNER_INT + WINNER_FLOAT:
         assert getattr(ra, f).tobytes() == getattr(rb, f).tobytes(), f
+
+
+def test_arenas_grow_recarve_and_reuse():
+    """One context through limited S=2, limited S=5, unlimited S=7, limited S=2
+    and a reconcile: the planning arena grows twice, the greedy workspace once,
+    both are carved anew and then used below their capacity. Every call must
+    give, byte for byte, what it gives on a FastSweep that never did anything
+    else."""
+    _, scen, free = planner("a")
+    used = FastSweep(fleet_a(), backend="gpu")
+    assert used.n_cells >= 24 and scen.shape[0] == 7
+    rows = row_capacity(used, free)
+
+    def limited(fs, sl):
+        res = fs.plan(arrival=scen[sl], capacity=rows[sl], saturation_policy="PriorityRoundRobin")
+        return res, fs._plan_limited_cells.copy()
+
+    def same_winners(a, b, what):
+        for f in WINNER_INT + WINNER_FLOAT:
+            x, y = getattr(a, f), getattr(b, f)
+            assert x.dtype == y.dtype and x.shape == y.shape, (what, f)
+            assert x.tobytes() == y.tobytes(), (what, f)
+
+    def same_arrays(a, b, what):
+        assert a.dtype == b.dtype and a.shape == b.shape, what
+        assert a.tobytes() == b.tobytes(), what
+
+    steps = [("limited S=2", slice(0, 2)), ("limited S=5", slice(0, 5)), ("unlimited S=7", None),
+             ("limited S=2 again", slice(5, 7))]
+    for what, sl in steps:
+        fresh = FastSweep(fleet_a(), backend="gpu")
+        if sl is None:
+            a, b = used.plan(arrival=scen), fresh.plan(arrival=scen)
+            assert a.capacity_left is None and a.desired_replicas is None
+        else:
+            (a, a_cells), (b, b_cells) = limited(used, sl), limited(fresh, sl)
+            same_arrays(a_cells, b_cells, what)
+            assert a.winners.acc_idx.shape == (sl.stop - sl.start, len(used.server_names))
+            for f in ("desired_replicas", "capacity_left"):
+                same_arrays(getattr(a, f), getattr(b, f), (what, f))
+        same_winners(a.winners, b.winners, what)
+        same_arrays(a.replicas_by_acc, b.replicas_by_acc, what)
+    same_winners(used.reconcile(), FastSweep(fleet_a(), backend="gpu").reconcile(), "reconcile")
