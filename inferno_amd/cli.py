@@ -5,6 +5,7 @@ pkg/config wire format) and print the allocation solution.
   python -m inferno_amd.cli analyze system.json --server NAME:NS
   python -m inferno_amd.cli plan system.json --scales 0.5,1,1.5,2 [--backend ...] [--json]
       [--limited] [--capacity TYPE=N,...] [--saturation-policy P] [--delayed-best-effort]
+  python -m inferno_amd.cli plan system.json --slo-scales 0.5,1,2 [--scales ...] [--json]
 """
 from __future__ import annotations
 
@@ -65,13 +66,13 @@ def cmd_solve(args) -> int:
     return 0
 
 
-def _parse_scales(text: str) -> list[float]:
+def _parse_scales(text: str, flag: str = "--scales") -> list[float]:
     try:
         scales = [float(t) for t in text.split(",") if t.strip()]
     except ValueError:
-        raise SystemExit(f"--scales: not a comma-separated list of numbers: {text!r}")
+        raise SystemExit(f"{flag}: not a comma-separated list of numbers: {text!r}")
     if not scales:
-        raise SystemExit("--scales: at least one scale is required")
+        raise SystemExit(f"{flag}: at least one scale is required")
     return scales
 
 
@@ -97,11 +98,18 @@ def cmd_plan(args) -> int:
 
     from .engine import FastSweep, SweepEngine
 
+    limited = args.limited or args.capacity is not None
+    if args.slo_scales is not None:
+        if limited:
+            raise SystemExit("plan: --slo-scales is an unlimited-mode plan; it does not "
+                             "combine with --limited or --capacity")
+        return _cmd_plan_slo(args)
+    if args.scales is None:
+        raise SystemExit("plan: one of --scales and --slo-scales is required")
     scales = _parse_scales(args.scales)
     system, opt = _load_system(args.spec)
     backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
     fs = FastSweep(system, backend=backend)
-    limited = args.limited or args.capacity is not None
     kw = {}
     if limited:
         kw["capacity"] = (_parse_capacity(args.capacity) if args.capacity is not None
@@ -163,6 +171,59 @@ def cmd_plan(args) -> int:
     return 0
 
 
+def _cmd_plan_slo(args) -> int:
+    """What-if SLO plan: the unlimited-mode solution at each SLO scale (the
+    factor on every TTFT and ITL target) and each load scale."""
+    import numpy as np
+
+    from .engine import FastSweep, SweepEngine
+
+    slo_scales = _parse_scales(args.slo_scales, "--slo-scales")
+    scales = _parse_scales(args.scales) if args.scales is not None else [1.0]
+    system, _ = _load_system(args.spec)
+    backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
+    fs = FastSweep(system, backend=backend)
+    try:
+        res = fs.plan_slo(slo_scales=slo_scales, scales=scales)
+    except ValueError as e:
+        print(f"plan: {e}", file=sys.stderr)
+        return 2
+    # accelerator changes are relative to SLO scale 1.0 at load scale 1.0 (the
+    # first of either when 1.0 is not among them)
+    tref = slo_scales.index(1.0) if 1.0 in slo_scales else 0
+    sref = scales.index(1.0) if 1.0 in scales else 0
+    acc = res.winners.acc_idx
+    blocks = []
+    for t, slo_scale in enumerate(slo_scales):
+        rows = [{
+            "scale": scale,
+            "totalCost": round(float(res.cost_total[t, s]), 2),
+            "replicas": {
+                name: int(res.replicas_by_acc[t, s, j]) for j, name in enumerate(fs.acc_names)
+            },
+            "infeasibleServers": int(res.infeasible_servers[t, s]),
+            "acceleratorChanges": int(np.count_nonzero(acc[t, s] != acc[tref, sref])),
+        } for s, scale in enumerate(scales)]
+        blocks.append({"sloScale": slo_scale, "scenarios": rows})
+    if args.json:
+        print(json.dumps({"backend": backend, "referenceSloScale": slo_scales[tref],
+                          "referenceScale": scales[sref], "servers": len(fs.server_names),
+                          "sloScenarios": blocks}, indent=2))
+        return 0
+    names = fs.acc_names
+    for b in blocks:
+        print(f"SLO scale {b['sloScale']:g} (TTFT and ITL targets x {b['sloScale']:g})")
+        print(f"{'scale':>8} {'cost':>12} " + " ".join(f"{n:>10}" for n in names)
+              + f" {'infeasible':>10} {'acc-changes':>11}")
+        for r in b["scenarios"]:
+            print(f"{r['scale']:>8g} {r['totalCost']:>12.2f} "
+                  + " ".join(f"{r['replicas'][n]:>10}" for n in names)
+                  + f" {r['infeasibleServers']:>10} {r['acceleratorChanges']:>11}")
+    print(f"({len(fs.server_names)} servers, backend {backend}; acc-changes are relative to "
+          f"SLO scale {slo_scales[tref]:g} at load scale {scales[sref]:g})")
+    return 0
+
+
 def cmd_analyze(args) -> int:
     from .api import v1alpha1 as api
     from .controller.modelanalyzer import ModelAnalyzer
@@ -194,8 +255,11 @@ def main() -> None:
     ps.set_defaults(fn=cmd_solve)
     pp = sub.add_parser("plan", help="what-if plan: the fleet at several load scales")
     pp.add_argument("spec")
-    pp.add_argument("--scales", required=True,
+    pp.add_argument("--scales", default=None,
                     help="comma-separated load factors, e.g. 0.5,1,1.5,2")
+    pp.add_argument("--slo-scales", default=None,
+                    help="comma-separated factors on every TTFT and ITL target, e.g. 0.5,1,2: "
+                         "one block per SLO scale (load scale 1 unless --scales is given)")
     pp.add_argument("--backend", choices=["auto", "gpu", "cpu"], default="auto")
     pp.add_argument("--json", action="store_true")
     pp.add_argument("--limited", action="store_true",

@@ -33,7 +33,7 @@ from ..config import SaturationPolicy
 from ..core import create_allocation
 from ..core.system import System
 from ..ops.sweep import PLAN_MAX_S, run_greedy_native
-from .native_ctx import NativeCtx
+from .native_ctx import CELL_KEYS, NativeCtx
 from .snapshot import FLAG_CUR_EMPTY, FLAG_CUR_SAME, FLAG_HAS_CUR
 
 _INT_KEYS = ("in_tok", "out_tok", "batch_n", "min_replicas", "perf_max_batch",
@@ -76,6 +76,21 @@ class PlanResult:
     partial_servers: Optional[np.ndarray] = None  # int64 [S]: 0 < granted < desired
     capacity_left: Optional[np.ndarray] = None  # int64 [S, n_types]
     capacity_types: Optional[list] = None  # columns of capacity_left
+
+
+@dataclass
+class SloPlanResult:
+    """What-if SLO plan: the unlimited-mode solution of T SLO-target sets
+    times S arrival-rate scenarios of one fleet (FastSweep.plan_slo)."""
+
+    winners: WinnerRecord  # every array [T, S, n_servers]
+    replicas_by_acc: np.ndarray  # int64 [T, S, n_acc], columns = FastSweep.acc_names
+    cost_total: np.ndarray  # float64 [T, S]: fp64 sum of the winners' fp32 cost
+    infeasible_servers: np.ndarray  # int64 [T, S]: servers with acc_idx == -1
+    arrival: np.ndarray  # float32 [S, n_servers]: the load scenarios evaluated
+    t_ttft: np.ndarray  # float32 [T, n_servers]: the TTFT targets evaluated (msec, 0 = none)
+    t_itl: np.ndarray  # float32 [T, n_servers]: the ITL targets evaluated
+    cells: Optional[dict] = None  # reconcile_cells() layout, arrays [T, S, n_cells]
 
 
 _WINNER_FIELDS = ("acc_idx", "num_replicas", "batch", "cost", "value", "itl", "ttft", "rho",
@@ -485,7 +500,22 @@ class FastSweep:
     def _plan_result(self, scen, winners: WinnerRecord, totals, cells, **limited) -> PlanResult:
         """The PlanResult of a solved plan; ``totals`` None = count the
         winners' replicas here. ``limited``: the limited-mode fields."""
-        n_scen = scen.shape[0]
+        totals, cost_total, infeasible = self._plan_totals(winners, totals)
+        return PlanResult(
+            winners=winners,
+            replicas_by_acc=totals,
+            cost_total=cost_total,
+            infeasible_servers=infeasible,
+            arrival=scen,
+            cells=cells,
+            **limited,
+        )
+
+    def _plan_totals(self, winners: WinnerRecord, totals):
+        """(replicas_by_acc, cost_total, infeasible_servers) of solved winners
+        [n_scen, n_servers]; ``totals`` None = count the winners' replicas
+        here."""
+        n_scen = winners.acc_idx.shape[0]
         has = winners.acc_idx != -1
         if totals is None:
             totals = np.zeros((n_scen, len(self.acc_names)), dtype=np.int64)
@@ -499,15 +529,7 @@ class FastSweep:
             [winners.cost[s][has[s]].astype(np.float64).sum() for s in range(n_scen)],
             dtype=np.float64,
         )
-        return PlanResult(
-            winners=winners,
-            replicas_by_acc=totals,
-            cost_total=cost_total,
-            infeasible_servers=(~has).sum(axis=1).astype(np.int64),
-            arrival=scen,
-            cells=cells,
-            **limited,
-        )
+        return totals, cost_total, (~has).sum(axis=1).astype(np.int64)
 
     def _plan_scenarios(self, scales, arrival) -> np.ndarray:
         """Validate plan()'s input and return the [S, n_servers] fp32 rates."""
@@ -561,6 +583,179 @@ class FastSweep:
     def _plan_cells_gpu(self, n_scen: int) -> dict:
         """Per-cell outputs of the planning pass that just ran."""
         return self._with_cell_meta(self._gpu.plan_cells(n_scen))
+
+    # ------------------------------------------------------------------
+    # What-if SLO planning
+    # ------------------------------------------------------------------
+    def plan_slo(self, slo_scales=None, targets=None, scales=None, arrival=None,
+                 return_cells: bool = False) -> SloPlanResult:
+        """Solve T SLO-target sets times S arrival-rate scenarios of the fleet
+        in one pass: what a tighter or looser SLO costs, at each load.
+
+        Target axis, exactly one of: ``slo_scales`` (T finite factors > 0;
+        target set t is ``float32(base) * float32(scale)`` of every server's
+        TTFT and ITL target) and ``targets=(ttft, itl)`` (two [T, n_servers]
+        arrays in msec, taken as float32, finite and >= 0). A target of 0 is
+        "no target"; a zero base target stays zero. The TPS target is the
+        server's own in every set. Load axis: ``scales`` or ``arrival`` as in
+        plan(); with neither, the base load alone (S = 1). 1 <= T * S <= 256.
+
+        Slice (t, s) of the result is what reconcile() returns on a fresh
+        FastSweep of an identical system whose per-server targets are
+        ``t_ttft[t]`` / ``t_itl[t]`` and whose arrival rates are
+        ``arrival[s]``. Servers that resolve to one Target object (same
+        service class and model) cannot be given different targets.
+
+        On the GPU each cell builds its chain geometry once, is sized once
+        per target set and every sizing is evaluated at every load. Only a
+        target set equal to the targets this FastSweep was built with uses the
+        sizing memo (one lookup per loaded cell and call); the others are
+        sized from scratch and leave the memo alone, so a following
+        reconcile() is neither changed nor slowed. Unlimited mode only."""
+        n_srv = len(self.server_names)
+        srv_targets, owner = self._server_targets()
+        if (slo_scales is None) == (targets is None):
+            raise ValueError("plan_slo() takes exactly one of slo_scales and targets")
+        if slo_scales is not None:
+            try:
+                sc = np.asarray(slo_scales, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"slo_scales is not numeric: {e}") from None
+            if sc.ndim != 1:
+                raise ValueError(f"slo_scales must be 1-D, got shape {sc.shape}")
+            if not np.isfinite(sc).all() or (sc <= 0).any():
+                raise ValueError("slo_scales must be finite and positive")
+            f32 = sc.astype(np.float32)
+            if (f32 == 0).any():
+                raise ValueError("slo_scales underflows float32")
+            base_ttft = np.array([0.0 if t is None else t.ttft for t in srv_targets],
+                                 dtype=np.float32)
+            base_itl = np.array([0.0 if t is None else t.itl for t in srv_targets],
+                                dtype=np.float32)
+            with np.errstate(over="ignore"):
+                t_ttft = base_ttft[None, :] * f32[:, None]
+                t_itl = base_itl[None, :] * f32[:, None]
+        else:
+            try:
+                ttft, itl = targets
+                t_ttft = np.asarray(ttft, dtype=np.float64)
+                t_itl = np.asarray(itl, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"targets is not a (ttft, itl) pair of numeric arrays: {e}") \
+                    from None
+            for a, what in ((t_ttft, "ttft"), (t_itl, "itl")):
+                if a.ndim != 2 or a.shape[1] != n_srv:
+                    raise ValueError(f"targets {what} must have shape [T, {n_srv}], got {a.shape}")
+                if not np.isfinite(a).all() or (a < 0).any():
+                    raise ValueError(f"targets {what} must be finite and non-negative")
+            if t_ttft.shape != t_itl.shape:
+                raise ValueError("targets ttft and itl differ in shape")
+            with np.errstate(over="ignore"):
+                t_ttft, t_itl = t_ttft.astype(np.float32), t_itl.astype(np.float32)
+        t_ttft = np.ascontiguousarray(t_ttft, dtype=np.float32)
+        t_itl = np.ascontiguousarray(t_itl, dtype=np.float32)
+        if not (np.isfinite(t_ttft).all() and np.isfinite(t_itl).all()):
+            raise ValueError("SLO targets overflow float32")
+        n_tgt = t_ttft.shape[0]
+        if scales is None and arrival is None:
+            scen = np.ascontiguousarray(self._base_load()[0][None, :], dtype=np.float32)
+        else:
+            scen = self._plan_scenarios(scales, arrival)
+        n_load = scen.shape[0]
+        if not 1 <= n_tgt * n_load <= PLAN_MAX_S:
+            raise ValueError(
+                f"plan_slo() takes 1..{PLAN_MAX_S} (target set, load) pairs, "
+                f"got {n_tgt} x {n_load}"
+            )
+        # one Target object, one pair of targets per set, on both backends
+        # (owner[i]: the first server that resolves to server i's Target)
+        split = ((t_ttft != t_ttft[:, owner]) | (t_itl != t_itl[:, owner])).any(axis=0)
+        if split.any():
+            i = int(np.argmax(split))
+            raise ValueError(
+                f"servers {self.server_names[owner[i]]} and {self.server_names[i]} share one "
+                "service-class target and cannot be given different targets"
+            )
+
+        n_acc = len(self.acc_names)
+        cells = totals = None
+        if self.backend != "gpu":
+            rows = []
+            with self._scenario_targets(srv_targets) as set_targets:
+                for t in range(n_tgt):
+                    set_targets(t_ttft[t], t_itl[t])
+                    rows.append(self._plan_cpu(scen))
+            flat = WinnerRecord(**{
+                f: np.concatenate([getattr(r, f) for r in rows]) for f in _WINNER_FIELDS
+            })
+        elif self.n_cells == 0 or n_acc == 0:
+            flat = _empty_winners(n_tgt * n_load, n_srv)
+        else:
+            self._tick(plan_arrival=scen, launch=False)  # stage + bucket layout
+            cs = self.cell_server
+            f32 = np.float32
+            of, oi, totals = self._gpu.plan_slo(
+                np.ascontiguousarray(scen[:, cs], dtype=f32),
+                np.ascontiguousarray(t_ttft[:, cs], dtype=f32),
+                np.ascontiguousarray(t_itl[:, cs], dtype=f32), n_acc,
+            )
+            flat = _winner_record(of, oi)
+            if return_cells:
+                cells = self._plan_cells_gpu(n_tgt * n_load)
+                for k in CELL_KEYS:
+                    cells[k] = cells[k].reshape(n_tgt, n_load, self.n_cells)
+        totals, cost_total, infeasible = self._plan_totals(flat, totals)
+        grid = (n_tgt, n_load)
+        return SloPlanResult(
+            winners=WinnerRecord(**{
+                f: getattr(flat, f).reshape(grid + (n_srv,)) for f in _WINNER_FIELDS
+            }),
+            replicas_by_acc=totals.reshape(grid + (n_acc,)),
+            cost_total=cost_total.reshape(grid),
+            infeasible_servers=infeasible.reshape(grid),
+            arrival=scen,
+            t_ttft=t_ttft,
+            t_itl=t_itl,
+            cells=cells,
+        )
+
+    def _server_targets(self):
+        """(targets, owner), cached per fleet topology: the Target object each
+        server resolves to (None: no service class or no target for its
+        model), as create_allocation resolves it, and per server the index of
+        the first server that resolves to the same object (its own index for a
+        server without one)."""
+        cached = getattr(self, "_server_targets_cache", None)
+        if cached is not None:
+            return cached
+        out, first = [], {}
+        owner = np.arange(len(self._srv_objs), dtype=np.int64)
+        for i, server in enumerate(self._srv_objs):
+            svc = self.system.service_classes.get(server.service_class_name)
+            tgt = svc.model_target(server.model_name) if svc is not None else None
+            out.append(tgt)
+            if tgt is not None:
+                owner[i] = first.setdefault(id(tgt), i)
+        self._server_targets_cache = (out, owner)
+        return self._server_targets_cache
+
+    @contextlib.contextmanager
+    def _scenario_targets(self, srv_targets):
+        """For the CPU golden path: yields set_targets(ttft_row, itl_row), which
+        puts one target set on the servers' Target objects; their targets are
+        restored afterwards in any case."""
+        saved = {id(t): (t, t.ttft, t.itl) for t in srv_targets if t is not None}
+
+        def set_targets(ttft_row, itl_row):
+            for i, t in enumerate(srv_targets):
+                if t is not None:
+                    t.ttft, t.itl = float(ttft_row[i]), float(itl_row[i])
+
+        try:
+            yield set_targets
+        finally:
+            for t, ttft, itl in saved.values():
+                t.ttft, t.itl = ttft, itl
 
     # ------------------------------------------------------------------
     # Capacity-limited planning

@@ -270,6 +270,27 @@ class NativeCtx:
                     _copy_out(out[4], ctypes.c_int32, cap.shape).astype(np.int64))
         return res
 
+    def plan_slo(self, cell_scen: np.ndarray, cell_ttft: np.ndarray, cell_itl: np.ndarray,
+                 n_acc: int):
+        """wva_ctx_plan_slo on [S, n_cells] fp32 arrivals and [T, n_cells] fp32
+        TTFT / ITL targets (the tick is staged and the buckets are set):
+        plan()'s first three arrays with T * S leading, slice t * S + s being
+        target set t at arrival rates s."""
+        n_load, n_tgt = cell_scen.shape[0], cell_ttft.shape[0]
+        n_scen = n_tgt * n_load
+        out = [ctypes.c_void_p() for _ in range(3)]
+        rc = self._lib.wva_ctx_plan_slo(
+            self.ctx, n_tgt, n_scen, n_acc, cell_scen.ctypes.data, cell_ttft.ctypes.data,
+            cell_itl.ctypes.data, *[ctypes.byref(p) for p in out],
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_plan_slo failed: {rc}")
+        return (
+            _copy_out(out[0], ctypes.c_float, (n_scen, 6, self.n_srv)),
+            _copy_out(out[1], ctypes.c_int32, (n_scen, 4, self.n_srv)),
+            _copy_out(out[2], ctypes.c_uint64, (n_scen, n_acc)).astype(np.int64),
+        )
+
     def plan_cells(self, n_scen: int) -> dict:
         """Per-cell outputs [S, n_cells] of the planning pass that just ran."""
         cells = {k: np.empty((n_scen, self.n_cells), dtype=d)

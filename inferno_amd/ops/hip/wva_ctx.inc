@@ -82,6 +82,15 @@ struct WvaCtx {
   float *plan_pin_pf;
   int *plan_pin_pi;
   unsigned long long *plan_pin_tot;
+  // SLO planning (wva_ctx_plan_slo): the per-cell target sets, allocated on
+  // first use, grown to the largest count seen, freed in destroy
+  int slo_cap;       // target sets the buffers hold (0 = not allocated)
+  void *slo_dev;     // one device allocation, carved up below
+  void *slo_pin;     // one pinned host allocation, carved up below
+  float *slo_ttft;   // device [T][n_cells]
+  float *slo_itl;    // device [T][n_cells]
+  float *slo_pin_ttft;  // pinned mirrors
+  float *slo_pin_itl;
   // capacity-limited planning (wva_ctx_plan_limited): the static greedy
   // inputs (wva_ctx_set_greedy_static) and the per-scenario workspace, both
   // allocated on first use and freed in destroy
@@ -317,10 +326,12 @@ extern "C" int wva_ctx_set_buckets(void *ctx, int n_buckets, const int *nts,
 // The bucket sweeps of one pass, after the uploads queued on s0: record the
 // upload event, launch bucket 0 on s0 and the others on the side streams
 // behind that event, then join them back onto s0. `out` receives the per-cell
-// results; `plan` (may be null) selects the planning kernels. Enqueues only —
+// results; `plan` (may be null) selects the planning kernels, `slo` (may be
+// null) the SLO-planning ones. Enqueues only —
 // no synchronising call, since the reconcile pipeline runs under stream
 // capture.
-static int wva_run_buckets(WvaCtx *c, const WvaCellsOut &out, const WvaPlanArgs *plan) {
+static int wva_run_buckets(WvaCtx *c, const WvaCellsOut &out, const WvaPlanArgs *plan,
+                           const WvaSloArgs *slo = nullptr) {
   if (hipEventRecord(c->e_up, c->s0) != hipSuccess) return -10;
   for (int i = 0; i < c->n_buckets; ++i) {
     hipStream_t s = (i == 0) ? c->s0 : c->side[i - 1];
@@ -328,7 +339,7 @@ static int wva_run_buckets(WvaCtx *c, const WvaCellsOut &out, const WvaPlanArgs 
     const WvaBucket &b = c->buckets[i];
     const int rc =
         wva_sweep_dispatch(b.n_blocks, b.max_n, b.nt, b.cell_ids, c->analyzer_mode, c->cv2, s,
-                           c->in, out, b.g_inv, b.g_anchor, c->memo, c->memo_cnt, plan);
+                           c->in, out, b.g_inv, b.g_anchor, c->memo, c->memo_cnt, plan, slo);
     if (rc != 0) return rc;
     if (i > 0 && hipEventRecord(c->e_b[i - 1], s) != hipSuccess) return -12;
   }
@@ -543,6 +554,31 @@ static int wva_plan_reserve(WvaCtx *c, int n_scen, int n_acc) {
   return 0;
 }
 
+static void wva_slo_release(WvaCtx *c) {
+  wva_arena_free(c->slo_dev, c->slo_pin);
+  c->slo_cap = 0;
+}
+
+// (re)allocate the SLO-planning target arrays for n_tgt target sets; on
+// failure nothing is held and reconciles and load plans keep working
+static int wva_slo_reserve(WvaCtx *c, int n_tgt) {
+  if (n_tgt <= c->slo_cap) return 0;
+  wva_slo_release(c);
+  const size_t b_t = (size_t)n_tgt * (size_t)c->n_cells * sizeof(float);
+  enum { A_TTFT, A_ITL, A_N };  // the same two arrays on the device and pinned
+  const size_t size[A_N] = {b_t, b_t};
+  size_t off[A_N];
+  const size_t bytes = wva_arena_layout(size, A_N, off);
+  if (!wva_arena_alloc(c, bytes, bytes, false, &c->slo_dev, &c->slo_pin)) return -36;
+  c->slo_cap = n_tgt;
+  char *d = (char *)c->slo_dev, *h = (char *)c->slo_pin;
+  c->slo_ttft = (float *)(d + off[A_TTFT]);
+  c->slo_itl = (float *)(d + off[A_ITL]);
+  c->slo_pin_ttft = (float *)(h + off[A_TTFT]);
+  c->slo_pin_itl = (float *)(h + off[A_ITL]);
+  return 0;
+}
+
 static void wva_lim_release(WvaCtx *c) {
   wva_arena_free(c->lim_dev, c->lim_pin);
   c->lim_cap = c->lim_types_cap = 0;
@@ -631,27 +667,44 @@ extern "C" int wva_ctx_set_greedy_static(void *ctx, const int *cell_type, const 
 // lim == nullptr is the unlimited plan (wva_ctx_plan). With lim, step 3 is
 // wva_plan_greedy instead of wva_plan_reduce and the capacity rows go up and
 // come back (wva_ctx_plan_limited); everything else is the same pass.
+//
+// With slo (wva_ctx_plan_slo) the n_scen slices are n_tgt target sets times
+// n_scen / n_tgt arrival-rate scenarios, target-major: scen_arrival holds the
+// arrival-rate scenarios only, the target sets go up next to it, and step 2
+// launches the SLO-planning kernels; everything else is the same pass.
 struct WvaLimArgs {
   int n_types;
   const int *capacity;  // host [n_scen][n_types]
   int delayed;
   int policy;
 };
+struct WvaSloTargets {
+  int n_tgt;
+  const float *scen_ttft;  // host [n_tgt][n_cells]
+  const float *scen_itl;   // host [n_tgt][n_cells]
+};
 
 static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arrival,
                         const WvaLimArgs *lim, const void **out_pf, const void **out_pi,
-                        const void **out_totals) {
+                        const void **out_totals, const WvaSloTargets *slo = nullptr) {
   if (c == nullptr || scen_arrival == nullptr) return -31;
   if (n_scen < 1 || n_scen > WVA_PLAN_MAX_S || n_acc < 1) return -32;
+  if (slo != nullptr && (slo->n_tgt < 1 || n_scen % slo->n_tgt != 0)) return -32;
   if (c->n_cells <= 0 || c->n_srv <= 0) return -33;
   c->plan_s = 0;
   int rc = wva_plan_reserve(c, n_scen, n_acc);
   if (rc != 0) return rc;
+  if (slo != nullptr) {
+    rc = wva_slo_reserve(c, slo->n_tgt);
+    if (rc != 0) return rc;
+  }
   if (lim != nullptr) {
     rc = wva_lim_reserve(c, n_scen, lim->n_types);
     if (rc != 0) return rc;
   }
-  const size_t cells = (size_t)n_scen * (size_t)c->n_cells;
+  // arrival-rate scenarios: all n_scen slices, or one SLO plan's load axis
+  const int n_load = slo != nullptr ? n_scen / slo->n_tgt : n_scen;
+  const size_t cells = (size_t)n_load * (size_t)c->n_cells;
   hipError_t err;
 
   // 1. uploads: scenario arrivals through the pinned staging buffer, then the
@@ -660,6 +713,19 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   err = hipMemcpyAsync(c->plan_scen, c->plan_pin_scen, cells * sizeof(float),
                        hipMemcpyHostToDevice, c->s0);
   if (err != hipSuccess) return (int)err;
+  if (slo != nullptr) {
+    const size_t tcells = (size_t)slo->n_tgt * (size_t)c->n_cells;
+    for (size_t i = 0; i < tcells; ++i) {
+      c->slo_pin_ttft[i] = slo->scen_ttft[i];
+      c->slo_pin_itl[i] = slo->scen_itl[i];
+    }
+    err = hipMemcpyAsync(c->slo_ttft, c->slo_pin_ttft, tcells * sizeof(float),
+                         hipMemcpyHostToDevice, c->s0);
+    if (err != hipSuccess) return (int)err;
+    err = hipMemcpyAsync(c->slo_itl, c->slo_pin_itl, tcells * sizeof(float),
+                         hipMemcpyHostToDevice, c->s0);
+    if (err != hipSuccess) return (int)err;
+  }
   err = hipMemcpyAsync(c->dev_dyn, c->pin_dyn, (size_t)WVA_DYN_ROWS * c->n_cells * 4,
                        hipMemcpyHostToDevice, c->s0);
   if (err != hipSuccess) return (int)err;
@@ -675,8 +741,14 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   }
 
   // 2. planning buckets: same streams, fork/join and order as the reconcile
-  const WvaPlanArgs pa = {c->n_cells, n_scen, c->plan_scen};
-  rc = wva_run_buckets(c, c->plan_out, &pa);
+  if (slo != nullptr) {
+    const WvaSloArgs sa = {c->n_cells, n_load,       c->plan_scen,
+                           slo->n_tgt, c->slo_ttft, c->slo_itl};
+    rc = wva_run_buckets(c, c->plan_out, nullptr, &sa);
+  } else {
+    const WvaPlanArgs pa = {c->n_cells, n_scen, c->plan_scen};
+    rc = wva_run_buckets(c, c->plan_out, &pa);
+  }
   if (rc != 0) return rc;
 
   // 3. winners, records and totals for all (server, scenario) pairs
@@ -768,6 +840,23 @@ extern "C" int wva_ctx_plan_limited(void *ctx, int n_scen, int n_acc, const floa
   return 0;
 }
 
+// One SLO-planning pass: n_tgt target sets times n_load = n_scen / n_tgt
+// arrival-rate scenarios, n_scen slices in all (1..WVA_PLAN_MAX_S), slice
+// t * n_load + s being target set t at arrival rates s. scen_arrival: host
+// [n_load][n_cells] fp32 (req/min); scen_ttft, scen_itl: host [n_tgt][n_cells]
+// fp32 (msec, 0 = no target). Staging, buckets and the three out pointers
+// ([n_scen] leading) are as for wva_ctx_plan; wva_ctx_plan_cells works on the
+// result. -36: the target arrays could not be allocated (the context is intact).
+extern "C" int wva_ctx_plan_slo(void *ctx, int n_tgt, int n_scen, int n_acc,
+                                const float *scen_arrival, const float *scen_ttft,
+                                const float *scen_itl, const void **out_pf, const void **out_pi,
+                                const void **out_totals) {
+  if (scen_ttft == nullptr || scen_itl == nullptr) return -31;
+  const WvaSloTargets slo = {n_tgt, scen_ttft, scen_itl};
+  return wva_plan_run((WvaCtx *)ctx, n_scen, n_acc, scen_arrival, nullptr, out_pf, out_pi,
+                      out_totals, &slo);
+}
+
 // Per-cell outputs of the last successful wva_ctx_plan, copied into ten host
 // arrays of plan_s * n_cells elements each, in WvaCellsOut order (feasible,
 // zero_empty: u8; num_replicas, batch: i32; cost, value, itl, ttft, rho,
@@ -800,6 +889,7 @@ extern "C" void wva_ctx_destroy(void *ctx) {
   }
   if (c->memo != nullptr) (void)hipFree(c->memo);
   wva_plan_release(c);
+  wva_slo_release(c);
   wva_lim_release(c);
   if (c->lim_static != nullptr) (void)hipFree(c->lim_static);
   free(c->topo);

@@ -45,7 +45,8 @@
 //       lowest-cell-index tie-break (the one-shot API; the context uses K4b).
 //
 //   K1 also comes as wva_plan_t<NT>: the same sweep over S arrival-rate
-//       scenarios per cell (planning).
+//       scenarios per cell (planning), and as wva_slo_plan_t<NT>: T SLO-target
+//       sets times S arrival-rate scenarios per cell (SLO planning).
 //
 //   K4 wva_plan_reduce: per (server, scenario) K2's selection, the winner
 //       record and the per-accelerator replica totals, in one launch.
@@ -793,8 +794,66 @@ struct WvaPlanArgs {
   const float *scen_arrival;  // device, [n_scen][n_cells]
 };
 struct WvaNoPlan {};
-template <bool PLAN>
-using WvaPlanParam = typename std::conditional<PLAN, WvaPlanArgs, WvaNoPlan>::type;
+// SLO planning: n_tgt target sets times n_load arrival-rate scenarios of the
+// cell; outputs are [n_tgt][n_load][n_cells], target-major
+struct WvaSloArgs {
+  int n_cells;
+  int n_load;
+  const float *scen_arrival;  // device, [n_load][n_cells]
+  int n_tgt;
+  const float *scen_ttft;  // device, [n_tgt][n_cells]
+  const float *scen_itl;   // device, [n_tgt][n_cells]
+};
+// what one launch of the sweep body covers per cell
+#define WVA_MODE_SWEEP 0  // the cell's own targets and arrival rate
+#define WVA_MODE_PLAN 1   // the cell's own targets, n_scen arrival rates
+#define WVA_MODE_SLO 2    // n_tgt target sets x n_load arrival rates
+template <int MODE>
+using WvaPlanParam = typename std::conditional<
+    MODE == WVA_MODE_PLAN, WvaPlanArgs,
+    typename std::conditional<MODE == WVA_MODE_SLO, WvaSloArgs, WvaNoPlan>::type>::type;
+
+// The SLO sizing of one cell under targets (t_ttft, t_itl): the concurrent
+// TTFT+ITL bisections (ref queueanalyzer.go:185-255), the minimum of the sized
+// rates and the analysis at that rate (ref allocation.go:126-131). Returns
+// false when a target cannot be met; else tput is the throughput at the sized
+// rate (req/msec). Every thread of the block calls this with the same
+// arguments and gets the same result.
+template <int NT>
+__device__ __forceinline__ bool wva_size_cell(float t_ttft, float t_itl, float t_tps,
+                                              double lam_min, double lam_max,
+                                              const ChainGeom &geom, double logsN, int N,
+                                              int Kstates, float gamma, float delta, float alpha,
+                                              float beta, int in_tok, int out_tok,
+                                              double *scratch, double *res_slot,
+                                              int analyzer_mode, double cv2d, double mu,
+                                              double &tput) {
+  double lam_star[2];
+  int inds[2];
+  dual_bisect<NT>(lam_min, lam_max, t_ttft, t_itl, geom, logsN, N, Kstates, gamma, delta, alpha,
+                  beta, in_tok, out_tok, scratch, res_slot, lam_star, inds, analyzer_mode, cv2d,
+                  mu);
+  bool feasible = true;
+  double lam_ttft = lam_max;
+  if (t_ttft > 0.0f) {
+    lam_ttft = lam_star[0];
+    if (inds[0] < 0) feasible = false;
+  }
+  double lam_itl = lam_max;
+  if (feasible && t_itl > 0.0f) {
+    lam_itl = lam_star[1];
+    if (inds[1] < 0) feasible = false;
+  }
+  if (!feasible) return false;
+  double lam_tps = (t_tps > 0.0f) ? lam_max * (1.0 - WVA_STABILITY_FRACTION) : lam_max;
+  double lam = fmin(fmin(lam_ttft, lam_itl), lam_tps);
+  if (analyzer_mode == 1) {
+    tput = mg1_eval(lam, mu, Kstates, cv2d, N).throughput;
+  } else {
+    tput = chain_eval<NT, 1>(lam, geom, logsN, N, Kstates, scratch).throughput;
+  }
+  return true;
+}
 
 // ---------------------------------------------------------------------------
 // K1: allocate-sweep — one block per cell; cell_ids selects this launch's
@@ -815,13 +874,23 @@ using WvaPlanParam = typename std::conditional<PLAN, WvaPlanArgs, WvaNoPlan>::ty
 // bit what a single-scenario launch with that arrival rate writes. Both
 // variants compile from this one body; every difference is an
 // `if constexpr (PLAN)`.
-template <int NT, bool GMEM, bool PLAN>
+//
+// MODE = WVA_MODE_SLO is the SLO-planning variant: the geometry, which reads
+// no target, is built once; the cell is then sized under each of n_tgt target
+// sets (scen_ttft / scen_itl[t * n_cells + cell]; the TPS target stays the
+// cell's own) and every sizing is evaluated at each of n_load arrival rates
+// into slot (t * n_load + s) * n_cells + cell. Slice (t, s) is bit for bit what
+// a single-scenario launch with those targets and that arrival rate writes.
+// Its differences are `if constexpr (SLO)`.
+template <int NT, bool GMEM, int MODE>
 __device__ __forceinline__ void wva_sweep_body(const WvaCellsIn &in, const WvaCellsOut &out,
                                                int n_blocks, const int *cell_ids, int max_n,
                                                int analyzer_mode, float cv2, float *g_inv,
                                                double *g_anchor, WvaMemoRec *memo,
                                                unsigned *memo_cnt,
-                                               const WvaPlanParam<PLAN> &plan) {
+                                               const WvaPlanParam<MODE> &plan) {
+  constexpr bool PLAN = MODE == WVA_MODE_PLAN;
+  constexpr bool SLO = MODE == WVA_MODE_SLO;
   // memo: per-cell sizing records (nullptr = memo off: every cell is sized
   // from scratch and nothing is recorded); memo_cnt: [0] hits, [1] misses
   extern __shared__ double smem[];
@@ -873,12 +942,53 @@ __device__ __forceinline__ void wva_sweep_body(const WvaCellsIn &in, const WvaCe
           out.zero_empty[o] = 0;                                                            \
         }                                                                                   \
       }                                                                                     \
+    } else if constexpr (SLO) {                                                             \
+      for (int t = 0; t < plan.n_tgt; ++t) WVA_SLO_WRITE_INFEASIBLE(t);                     \
     } else {                                                                                \
       out.feasible[cell] = 0;                                                               \
       out.zero_empty[cell] = 0;                                                             \
     }                                                                                       \
   } while (0)
-  if constexpr (PLAN) {
+  // (thread 0 only, SLO planning) the same verdict for target set t alone:
+  // its n_load slices
+#define WVA_SLO_WRITE_INFEASIBLE(t)                                                         \
+  do {                                                                                      \
+    for (int s = 0; s < plan.n_load; ++s) {                                                 \
+      const size_t o = ((size_t)(t) * (size_t)plan.n_load + (size_t)s) *                    \
+                           (size_t)plan.n_cells + (size_t)cell;                             \
+      if (plan.scen_arrival[(size_t)s * (size_t)plan.n_cells + (size_t)cell] == 0.0f) {     \
+        WVA_WRITE_ZERO(o);                                                                  \
+      } else {                                                                              \
+        out.feasible[o] = 0;                                                                \
+        out.zero_empty[o] = 0;                                                              \
+      }                                                                                     \
+    }                                                                                       \
+  } while (0)
+  // SLO planning: the first target set whose two targets are bit-equal to the
+  // cell's own, -1 if none. Only that one may use the sizing memo, whose
+  // record is keyed on the cell's own targets. Block-uniform.
+  int slo_base = -1;
+  if constexpr (SLO) {
+    // zero-traffic in EVERY load scenario, hence in every (t, s) slice: the
+    // decision reads no target (block-uniform: depends on the cell only)
+    bool any_load = false;
+    if (out_tok != 0)
+      for (int s = 0; s < plan.n_load; ++s)
+        any_load = any_load ||
+                   (plan.scen_arrival[(size_t)s * (size_t)plan.n_cells + (size_t)cell] != 0.0f);
+    if (!any_load) {
+      if (tid == 0)
+        for (int o = 0; o < plan.n_tgt * plan.n_load; ++o)
+          WVA_WRITE_ZERO((size_t)o * (size_t)plan.n_cells + (size_t)cell);
+      return;
+    }
+    for (int t = plan.n_tgt - 1; t >= 0; --t) {
+      const size_t k = (size_t)t * (size_t)plan.n_cells + (size_t)cell;
+      if (__float_as_uint(plan.scen_ttft[k]) == __float_as_uint(t_ttft) &&
+          __float_as_uint(plan.scen_itl[k]) == __float_as_uint(t_itl))
+        slo_base = t;
+    }
+  } else if constexpr (PLAN) {
     // zero-traffic in EVERY scenario (block-uniform: depends on the cell only)
     bool any_load = false;
     if (out_tok != 0)
@@ -903,7 +1013,9 @@ __device__ __forceinline__ void wva_sweep_body(const WvaCellsIn &in, const WvaCe
   // every barrier below stays uniform. The only writer is this block's
   // thread 0 at one of the miss exits, which all lie behind a barrier (or,
   // for the single-wave block, later in the same wave's program order).
-  WvaMemoRec *const rec = memo ? memo + cell : nullptr;
+  // SLO planning: the lookup, its counter and the miss store belong to target
+  // set slo_base; without one the memo is neither read nor written.
+  WvaMemoRec *const rec = (memo && (!SLO || slo_base >= 0)) ? memo + cell : nullptr;
   unsigned memo_status = WVA_MEMO_EMPTY;
   double memo_tput = 0.0;
   if (rec) {
@@ -918,16 +1030,21 @@ __device__ __forceinline__ void wva_sweep_body(const WvaCellsIn &in, const WvaCe
       memo_tput = r.tput;
     }
     if (tid == 0) atomicAdd(memo_cnt + (same ? 0 : 1), 1u);
-    if (memo_status == WVA_MEMO_INFEASIBLE) {
-      // replay of the infeasible verdict: no geometry, no evaluations
-      if (tid == 0) WVA_WRITE_INFEASIBLE();
-      return;
+    if constexpr (!SLO) {
+      if (memo_status == WVA_MEMO_INFEASIBLE) {
+        // replay of the infeasible verdict: no geometry, no evaluations
+        if (tid == 0) WVA_WRITE_INFEASIBLE();
+        return;
+      }
     }
+    // (SLO planning replays it for target set slo_base in the loop below: the
+    // other target sets still need the geometry)
   }
   // miss exits (degenerate, infeasible, sized) record their outcome; the key
   // is rebuilt here rather than kept live across the sizing phase
   auto memo_miss_store = [&](double tput, unsigned status) {
-    if (rec && tid == 0)
+    // (SLO planning reaches the degenerate exit after a hit too: no store then)
+    if (rec && tid == 0 && (!SLO || memo_status == WVA_MEMO_EMPTY))
       memo_store(rec,
                  memo_make_key(in_tok, out_tok, N, alpha, beta, gamma, delta, t_ttft, t_itl,
                                t_tps, cv2, analyzer_mode, NT),
@@ -1027,73 +1144,141 @@ __device__ __forceinline__ void wva_sweep_body(const WvaCellsIn &in, const WvaCe
   const double cv2d = (double)cv2;
   const int Kstates = 11 * N;  // maxQueue (10N) + N  (ref allocation.go:87)
 
-  double tput_at_lam;
-  if (memo_status == WVA_MEMO_FEASIBLE) {
-    // memo hit (block-uniform): the sizing below would reproduce this value
-    tput_at_lam = memo_tput;
-  } else {
-    // ---- SLO sizing: concurrent TTFT+ITL bisections (queueanalyzer.go:185-255)
-    double lam_star[2];
-    int inds[2];
-    dual_bisect<NT>(lam_min, lam_max, t_ttft, t_itl, geom, logsN, N, Kstates, gamma, delta,
-                    alpha, beta, in_tok, out_tok, scratch, total_slot + 1, lam_star, inds,
-                    analyzer_mode, cv2d, mu);
-    bool feasible = true;
-    double lam_ttft = lam_max;
-    if (t_ttft > 0.0f) {
-      lam_ttft = lam_star[0];
-      if (inds[0] < 0) feasible = false;
-    }
-    double lam_itl = lam_max;
-    if (feasible && t_itl > 0.0f) {
-      lam_itl = lam_star[1];
-      if (inds[1] < 0) feasible = false;
-    }
-    if (!feasible) {
-      if (tid == 0) WVA_WRITE_INFEASIBLE();
-      memo_miss_store(0.0, WVA_MEMO_INFEASIBLE);
-      return;
-    }
-    double lam_tps = (t_tps > 0.0f) ? lam_max * (1.0 - WVA_STABILITY_FRACTION) : lam_max;
-    double lam = fmin(fmin(lam_ttft, lam_itl), lam_tps);
-
-    // ---- analyze at sized rate -> rate* (ref allocation.go:126-131) ----
-    if (analyzer_mode == 1) {
-      tput_at_lam = mg1_eval(lam, mu, Kstates, cv2d, N).throughput;
-    } else {
-      tput_at_lam = chain_eval<NT, 1>(lam, geom, logsN, N, Kstates, scratch).throughput;
-    }
-    memo_miss_store(tput_at_lam, WVA_MEMO_FEASIBLE);
-  }
-  const double rate_star = tput_at_lam * 1000.0;  // req/sec
-
-  // ---- per scenario: replicas, cost and the per-replica analysis (the
-  // single-scenario instantiations evaluate the cell's own arrival rate).
-  // Block-uniform: the arrival rate depends only on (cell, scenario), so every
-  // barrier inside chain_eval stays uniform; consecutive chain_eval calls are
-  // ordered as the sized-rate and per-replica evaluations always were (single-
-  // wave blocks only READ LDS there, wider blocks enter each reduction through
-  // a barrier).
-  if constexpr (PLAN) {
-    for (int s = 0; s < plan.n_scen; ++s) {
-      // output slot s * n_cells + cell (up to 256 scenarios of the fleet)
-      const size_t o = (size_t)s * (size_t)plan.n_cells + (size_t)cell;
-      const float arr = plan.scen_arrival[o];
-      if (arr == 0.0f) {
-        if (tid == 0) WVA_WRITE_ZERO(o);
+  if constexpr (SLO) {
+    // ---- per target set: size (or, for slo_base, take the memo's word), then
+    // per load scenario the single-scenario tail. Per slice the order is the
+    // single-scenario kernel's: zero-traffic decision, infeasible verdict,
+    // evaluation.
+    //
+    // Block-uniform: the targets depend on (cell, t) only and the verdict comes
+    // from the shared result slots, so every barrier inside dual_bisect and
+    // chain_eval stays uniform.
+    //
+    // Consecutive sizings reuse the reduction scratch and the four bisection
+    // result slots behind total_slot. Blocks wider than one wave: every write
+    // to the scratch (red_max_p, red_sum2_p, chain_eval's broadcast) sits
+    // behind a barrier that follows the previous reads of it, whichever call
+    // made them, so the order of calls does not matter. The result slots are
+    // written at the end of dual_bisect and read by all threads right after
+    // its closing barrier; the next write to them is at the end of the next
+    // dual_bisect, whose loop runs at least one step and every step ends in a
+    // barrier (__syncthreads_and), in both analyzer modes — so a barrier
+    // separates the reads of iteration t from the writes of iteration t + 1,
+    // also when iteration t ends early on the infeasible verdict. Single-wave
+    // blocks use no scratch at all (their reductions are shuffles), and their
+    // result slots are written and read by one wave in program order: LDS
+    // serves a wave's accesses in issue order, and the s_waitcnt in
+    // dual_bisect completes the write before the reads. Nothing else in LDS is
+    // written after the geometry build.
+    for (int t = 0; t < plan.n_tgt; ++t) {
+      const size_t kt = (size_t)t * (size_t)plan.n_cells + (size_t)cell;
+      const bool base = (t == slo_base);
+      double tput_at_lam = 0.0;
+      bool feasible;
+      if (base && memo_status == WVA_MEMO_FEASIBLE) {
+        tput_at_lam = memo_tput;  // memo hit
+        feasible = true;
+      } else if (base && memo_status == WVA_MEMO_INFEASIBLE) {
+        feasible = false;  // replay of the infeasible verdict, for this t only
+      } else {
+        feasible = wva_size_cell<NT>(plan.scen_ttft[kt], plan.scen_itl[kt], t_tps, lam_min,
+                                     lam_max, geom, logsN, N, Kstates, gamma, delta, alpha, beta,
+                                     in_tok, out_tok, scratch, total_slot + 1, analyzer_mode,
+                                     cv2d, mu, tput_at_lam);
+        // only slo_base records its outcome (rec is null without one)
+        if (base) memo_miss_store(tput_at_lam, feasible ? WVA_MEMO_FEASIBLE : WVA_MEMO_INFEASIBLE);
+      }
+      if (!feasible) {
+        if (tid == 0) WVA_SLO_WRITE_INFEASIBLE(t);
         continue;
       }
-      wva_eval_scenario<NT>(out, o, arr, tid, t_tps, K, rate_star, min_rep, acc_cost,
+      const double rate_star = tput_at_lam * 1000.0;  // req/sec
+      for (int s = 0; s < plan.n_load; ++s) {
+        const float arr = plan.scen_arrival[(size_t)s * (size_t)plan.n_cells + (size_t)cell];
+        const size_t o = ((size_t)t * (size_t)plan.n_load + (size_t)s) * (size_t)plan.n_cells +
+                         (size_t)cell;
+        if (arr == 0.0f) {
+          if (tid == 0) WVA_WRITE_ZERO(o);
+          continue;
+        }
+        wva_eval_scenario<NT>(out, o, arr, tid, t_tps, K, rate_star, min_rep, acc_cost,
+                              analyzer_mode, mu, Kstates, cv2d, N, geom, logsN, scratch, gamma,
+                              delta, alpha, beta, in_tok, out_tok, has_cur, cur_same, cur_empty,
+                              cur_rep, cur_cost);
+      }
+    }
+  } else {
+    double tput_at_lam;
+    if (memo_status == WVA_MEMO_FEASIBLE) {
+      // memo hit (block-uniform): the sizing below would reproduce this value
+      tput_at_lam = memo_tput;
+    } else {
+      // ---- SLO sizing: concurrent TTFT+ITL bisections (queueanalyzer.go:185-255)
+      // (kept inline: the same steps as wva_size_cell, but routing these two
+      // modes through it moves their register allocation)
+      double lam_star[2];
+      int inds[2];
+      dual_bisect<NT>(lam_min, lam_max, t_ttft, t_itl, geom, logsN, N, Kstates, gamma, delta,
+                      alpha, beta, in_tok, out_tok, scratch, total_slot + 1, lam_star, inds,
+                      analyzer_mode, cv2d, mu);
+      bool feasible = true;
+      double lam_ttft = lam_max;
+      if (t_ttft > 0.0f) {
+        lam_ttft = lam_star[0];
+        if (inds[0] < 0) feasible = false;
+      }
+      double lam_itl = lam_max;
+      if (feasible && t_itl > 0.0f) {
+        lam_itl = lam_star[1];
+        if (inds[1] < 0) feasible = false;
+      }
+      if (!feasible) {
+        if (tid == 0) WVA_WRITE_INFEASIBLE();
+        memo_miss_store(0.0, WVA_MEMO_INFEASIBLE);
+        return;
+      }
+      double lam_tps = (t_tps > 0.0f) ? lam_max * (1.0 - WVA_STABILITY_FRACTION) : lam_max;
+      double lam = fmin(fmin(lam_ttft, lam_itl), lam_tps);
+
+      // ---- analyze at sized rate -> rate* (ref allocation.go:126-131) ----
+      if (analyzer_mode == 1) {
+        tput_at_lam = mg1_eval(lam, mu, Kstates, cv2d, N).throughput;
+      } else {
+        tput_at_lam = chain_eval<NT, 1>(lam, geom, logsN, N, Kstates, scratch).throughput;
+      }
+      memo_miss_store(tput_at_lam, WVA_MEMO_FEASIBLE);
+    }
+    const double rate_star = tput_at_lam * 1000.0;  // req/sec
+
+    // ---- per scenario: replicas, cost and the per-replica analysis (the
+    // single-scenario instantiations evaluate the cell's own arrival rate).
+    // Block-uniform: the arrival rate depends only on (cell, scenario), so every
+    // barrier inside chain_eval stays uniform; consecutive chain_eval calls are
+    // ordered as the sized-rate and per-replica evaluations always were (single-
+    // wave blocks only READ LDS there, wider blocks enter each reduction through
+    // a barrier).
+    if constexpr (PLAN) {
+      for (int s = 0; s < plan.n_scen; ++s) {
+        // output slot s * n_cells + cell (up to 256 scenarios of the fleet)
+        const size_t o = (size_t)s * (size_t)plan.n_cells + (size_t)cell;
+        const float arr = plan.scen_arrival[o];
+        if (arr == 0.0f) {
+          if (tid == 0) WVA_WRITE_ZERO(o);
+          continue;
+        }
+        wva_eval_scenario<NT>(out, o, arr, tid, t_tps, K, rate_star, min_rep, acc_cost,
+                              analyzer_mode, mu, Kstates, cv2d, N, geom, logsN, scratch, gamma,
+                              delta, alpha, beta, in_tok, out_tok, has_cur, cur_same, cur_empty,
+                              cur_rep, cur_cost);
+      }
+    } else {
+      wva_eval_scenario<NT>(out, cell, arrival, tid, t_tps, K, rate_star, min_rep, acc_cost,
                             analyzer_mode, mu, Kstates, cv2d, N, geom, logsN, scratch, gamma, delta,
                             alpha, beta, in_tok, out_tok, has_cur, cur_same, cur_empty, cur_rep,
                             cur_cost);
     }
-  } else {
-    wva_eval_scenario<NT>(out, cell, arrival, tid, t_tps, K, rate_star, min_rep, acc_cost,
-                          analyzer_mode, mu, Kstates, cv2d, N, geom, logsN, scratch, gamma, delta,
-                          alpha, beta, in_tok, out_tok, has_cur, cur_same, cur_empty, cur_rep,
-                          cur_cost);
   }
+#undef WVA_SLO_WRITE_INFEASIBLE
 #undef WVA_WRITE_INFEASIBLE
 #undef WVA_WRITE_ZERO
 }
@@ -1104,8 +1289,8 @@ __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut 
                                                   int analyzer_mode, float cv2,
                                                   float *g_inv, double *g_anchor,
                                                   WvaMemoRec *memo, unsigned *memo_cnt) {
-  wva_sweep_body<NT, GMEM, false>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2, g_inv,
-                                  g_anchor, memo, memo_cnt, WvaNoPlan{});
+  wva_sweep_body<NT, GMEM, WVA_MODE_SWEEP>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2,
+                                           g_inv, g_anchor, memo, memo_cnt, WvaNoPlan{});
 }
 
 // scenario-planning sweep: out arrays are [n_scen][n_cells]; in.arrival_rate
@@ -1123,8 +1308,21 @@ __global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES) wva_plan_t(WvaCellsIn 
                                                  int analyzer_mode, float cv2, float *g_inv,
                                                  double *g_anchor, WvaMemoRec *memo,
                                                  unsigned *memo_cnt, WvaPlanArgs plan) {
-  wva_sweep_body<NT, GMEM, true>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2, g_inv,
-                                 g_anchor, memo, memo_cnt, plan);
+  wva_sweep_body<NT, GMEM, WVA_MODE_PLAN>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2,
+                                          g_inv, g_anchor, memo, memo_cnt, plan);
+}
+
+// SLO-planning sweep: out arrays are [n_tgt][n_load][n_cells]; in.arrival_rate
+// is not read, in.t_ttft / in.t_itl only to find the target set that may use
+// the sizing memo. Built for the planning kernels' register budget
+// (docs/design/kernels.md, "SLO planning").
+template <int NT, bool GMEM>
+__global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
+    wva_slo_plan_t(WvaCellsIn in, WvaCellsOut out, int n_blocks, const int *cell_ids, int max_n,
+                   int analyzer_mode, float cv2, float *g_inv, double *g_anchor, WvaMemoRec *memo,
+                   unsigned *memo_cnt, WvaSloArgs plan) {
+  wva_sweep_body<NT, GMEM, WVA_MODE_SLO>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2,
+                                         g_inv, g_anchor, memo, memo_cnt, plan);
 }
 
 // ---------------------------------------------------------------------------
@@ -1197,7 +1395,8 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
                               int analyzer_mode, float cv2, hipStream_t s,
                               const WvaCellsIn &in, const WvaCellsOut &out, float *g_inv,
                               double *g_anchor, WvaMemoRec *memo, unsigned *memo_cnt,
-                              const WvaPlanArgs *plan = nullptr) {
+                              const WvaPlanArgs *plan = nullptr,
+                              const WvaSloArgs *slo = nullptr) {
   if (n_blocks <= 0) return 0;
   const bool gmem = g_inv != nullptr && g_anchor != nullptr;
   if (max_n < 1) return -2;
@@ -1214,6 +1413,15 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
   // width opts in separately from the reconcile one
 #define WVA_LAUNCH(NTV, GM)                                                                 \
   do {                                                                                      \
+    if (slo != nullptr) {                                                                   \
+      int src =                                                                             \
+          wva_optin_lds(reinterpret_cast<const void *>(&wva_slo_plan_t<NTV, GM>), lds);     \
+      if (src != 0) return src;                                                             \
+      hipLaunchKernelGGL((wva_slo_plan_t<NTV, GM>), dim3(n_blocks), dim3(NTV), lds, s, in,  \
+                         out, n_blocks, cell_ids, max_n, analyzer_mode, cv2, g_inv,         \
+                         g_anchor, memo, memo_cnt, *slo);                                   \
+      break;                                                                                \
+    }                                                                                       \
     if (plan != nullptr) {                                                                  \
       int prc =                                                                             \
           wva_optin_lds(reinterpret_cast<const void *>(&wva_plan_t<NTV, GM>), lds);  \

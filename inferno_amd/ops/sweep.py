@@ -223,6 +223,20 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_scen][4][n_srv]
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][n_acc]
     ]
+    # SLO planning (engine/fastpath.py FastSweep.plan_slo)
+    lib.wva_ctx_plan_slo.restype = ctypes.c_int
+    lib.wva_ctx_plan_slo.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_int,  # n_tgt
+        ctypes.c_int,  # n_scen = n_tgt * n_load (1..PLAN_MAX_S)
+        ctypes.c_int,  # n_acc
+        ctypes.c_void_p,  # host fp32 [n_load][n_cells] arrival rates
+        ctypes.c_void_p,  # host fp32 [n_tgt][n_cells] TTFT targets
+        ctypes.c_void_p,  # host fp32 [n_tgt][n_cells] ITL targets
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned fp32 [n_scen][6][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_scen][4][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][n_acc]
+    ]
     lib.wva_ctx_plan_cells.restype = ctypes.c_int
     lib.wva_ctx_plan_cells.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
     # capacity-limited planning (FastSweep.plan(capacity=...))
