@@ -237,6 +237,22 @@ class NativeCtx:
             return None
         return int(hits.value), int(misses.value)
 
+    def fused_state(self) -> dict:
+        """Diagnostics of the fused tick (synchronous, never on the hot path):
+        ``path`` 0 = bucket launches + wva_winner, 1 = one wva_tick_t launch,
+        2 = two; the task counts and LDS sizes of the launches; the CU count of
+        the residency rule; ``done_nonzero``, how many arrival counters are
+        not 0 (-1 when the fused tick is off; 0 after every completed tick)."""
+        info = (ctypes.c_int * 6)()
+        nz = ctypes.c_int(-1)
+        rc = self._lib.wva_ctx_fused_state(self.ctx, info, ctypes.byref(nz))
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_fused_state failed: {rc}")
+        keys = ("path", "n_tasks", "n_tasks_second", "lds_first", "lds_second", "n_cus")
+        out = dict(zip(keys, (int(v) for v in info)))
+        out["done_nonzero"] = int(nz.value)
+        return out
+
     # ------------------------------------------------------------------
     def plan(self, cell_scen: np.ndarray, n_acc: int, limited=None):
         """wva_ctx_plan on [S, n_cells] fp32 arrivals (the tick is staged and

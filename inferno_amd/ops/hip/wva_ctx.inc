@@ -1,10 +1,13 @@
 // wva_ctx.inc — host side of the native reconcile context, included at the end
 // of wva_kernels.hip (one translation unit: the kernels are launched from
 // here). The whole per-tick device pipeline behind ONE C call (host staging of
-// the per-server state, one H2D copy, regime-bucketed sweep launches
-// overlapped via events on side streams, the fused winner kernel, one D2H
-// copy, sync): wva_ctx_tick(ctx, ...); wva_reconcile(ctx) runs an already
+// the per-server state, one H2D copy, the fused tick kernel — or, for layouts
+// it does not cover, regime-bucketed sweep launches overlapped via events on
+// side streams and the winner kernel —, one D2H copy, sync):
+// wva_ctx_tick(ctx, ...); wva_reconcile(ctx) runs an already
 // staged tick; the planning passes share the context's arrays and buckets.
+#include <vector>
+
 #include "../native/wva_arena.h"  // 256-aligned arena layout (host only)
 
 #define WVA_MAX_BUCKETS 5
@@ -66,6 +69,32 @@ struct WvaCtx {
   // stays valid.
   WvaMemoRec *memo;
   unsigned *memo_cnt;
+  // fused tick (wva_tick_t): sweep and winner step of a tick in one launch.
+  // fused_on: INFERNO_FUSED_TICK is not 0 and the allocations below succeeded
+  // (read once at create). fused_path is decided by every wva_ctx_set_buckets:
+  // 0 = the bucket launches + wva_winner (a bucket is neither 64 nor 256
+  // threads wide, or spills to global memory), 1 = one launch of the task
+  // table, 2 = two launches (the widest bucket's tasks [0, n_tasks_b) with
+  // lds_b on side[0], the rest with lds_a on s0).
+  int fused_on;
+  int fused_path;
+  int n_cus_dev;         // CUs of the device (hipGetDeviceProperties at create)
+  int n_cus;             // CU count of the residency rule: n_cus_dev, or the
+                         // test-only INFERNO_FUSED_TICK_CUS
+  int *dev_cell_server;  // device [n_cells], uploaded by wva_ctx_set_topology
+  // done[n_srv]: arrivals of the current tick per server, an allocation of its
+  // own padded to a multiple of 16 bytes and zeroed from its start. Invariant:
+  // after a completed tick every word is 0 (the last arriver of each server
+  // resets it), so there is no per-tick memset; done_dirty asks for one before
+  // the next tick, after a tick that returned non-zero.
+  unsigned *done;
+  size_t done_bytes;
+  int done_dirty;
+  int4 *tasks;           // device task table, tasks_cap entries
+  int tasks_cap;
+  int n_tasks, n_tasks_b;
+  int narrow_stride;     // doubles between the LDS slices of a narrow block
+  size_t lds_a, lds_b;
   // scenario planning (wva_ctx_plan): buffers allocated on first use, grown
   // to the largest scenario count / accelerator count seen, freed in destroy
   int plan_cap;      // scenarios the buffers hold (0 = not allocated)
@@ -242,7 +271,73 @@ extern "C" void *wva_ctx_create(int n_cells, int n_srv, void **p) {
     }
     if (c->memo == nullptr) (void)hipGetLastError();  // clear the non-fatal error
   }
+  // fused tick: INFERNO_FUSED_TICK=0 forces the bucket launches (A/B runs,
+  // tests). A failure here leaves it off; the context itself is still good.
+  // INFERNO_FUSED_TICK_CUS (tests only) replaces the device's CU count in the
+  // residency rule (one or two launches), not in the decision to fuse.
+  const char *fused_env = getenv("INFERNO_FUSED_TICK");
+  const bool fused_req = !(fused_env != nullptr && fused_env[0] == '0' && fused_env[1] == '\0');
+  if (fused_req && n_cells > 0 && n_srv > 0) {
+    WvaDeviceGuard on_dev(c->dev_dyn);
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+      c->n_cus = c->n_cus_dev = prop.multiProcessorCount;
+    if (const char *cus_env = getenv("INFERNO_FUSED_TICK_CUS")) {
+      char *end = nullptr;
+      const long v = strtol(cus_env, &end, 10);
+      if (end != cus_env && *end == '\0' && v >= 1 && v <= (1 << 20)) c->n_cus = (int)v;
+    }
+    c->done_bytes = (((size_t)n_srv * sizeof(unsigned)) + 15) & ~(size_t)15;
+    void *d = nullptr, *cs = nullptr;
+    if (c->n_cus > 0 && hipMalloc(&d, c->done_bytes) == hipSuccess && d != nullptr &&
+        hipMalloc(&cs, (size_t)n_cells * sizeof(int)) == hipSuccess && cs != nullptr &&
+        hipMemsetAsync(d, 0, c->done_bytes, c->s0) == hipSuccess) {
+      c->done = (unsigned *)d;
+      c->dev_cell_server = (int *)cs;
+      c->fused_on = 1;
+    } else {
+      if (d != nullptr) (void)hipFree(d);
+      if (cs != nullptr) (void)hipFree(cs);
+      (void)hipGetLastError();
+    }
+  }
   return c;
+}
+
+// Diagnostics of the fused tick, never on the hot path (synchronous copy).
+// info[6]: fused_path (0 bucket launches, 1 one launch, 2 two launches), tasks
+// in all, tasks of the second launch, dynamic LDS bytes of the first and of the
+// second launch, CU count of the residency rule. done_nonzero: how many done[]
+// words are not 0 (-1 when the fused tick is off). Either pointer may be null.
+extern "C" int wva_ctx_fused_state(void *ctx, int *info, int *done_nonzero) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr) return -1;
+  if (info != nullptr) {
+    info[0] = c->fused_path;
+    info[1] = c->n_tasks;
+    info[2] = c->n_tasks_b;
+    info[3] = (int)c->lds_a;
+    info[4] = (int)c->lds_b;
+    info[5] = c->n_cus;
+  }
+  if (done_nonzero != nullptr) {
+    *done_nonzero = -1;
+    if (c->done != nullptr) {
+      unsigned *h = (unsigned *)malloc(c->done_bytes);
+      if (h == nullptr) return -3;
+      if (hipStreamSynchronize(c->s0) != hipSuccess ||
+          hipMemcpy(h, c->done, c->done_bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+        free(h);
+        return -2;
+      }
+      int nz = 0;
+      for (size_t i = 0; i < c->done_bytes / sizeof(unsigned); ++i) nz += h[i] != 0u;
+      free(h);
+      *done_nonzero = nz;
+    }
+  }
+  return 0;
 }
 
 // hit/miss counters of the sizing memo since the context was created
@@ -287,6 +382,194 @@ extern "C" int wva_ctx_set_topology(void *ctx, const int *cell_server, const int
   c->topo_override = c->topo + 4 * n;
   c->bucket_batch_n = c->topo + 5 * n;
   c->bucket_batch_valid = 0;
+  // the fused tick kernel finds a cell's server on the device. Synchronous
+  // upload, off the hot path; the next set_buckets rebuilds the task table.
+  c->fused_path = 0;
+  if (c->fused_on) {
+    if (hipStreamSynchronize(c->s0) != hipSuccess ||
+        hipMemcpy(c->dev_cell_server, cell_server, n * sizeof(int), hipMemcpyHostToDevice) !=
+            hipSuccess)
+      return -4;
+  }
+  return 0;
+}
+
+// Blocks of `lds` bytes of dynamic LDS that are resident at once: per CU what
+// fits in its 160 KiB, at most the 4 that wva_tick_t's launch bounds ask for.
+static long wva_tick_slots(const WvaCtx *c, size_t lds) {
+  const size_t per_cu = lds > 0 ? (size_t)(160 * 1024) / lds : 4;
+  return (long)c->n_cus * (long)(per_cu < 4 ? per_cu : 4);
+}
+
+// Build and upload the fused tick's task table from the bucket lists just
+// recorded, and decide fused_path. Any reason not to fuse leaves fused_path 0
+// (the bucket launches) and returns 0; a runtime error returns non-zero.
+//   order: wide tasks (256-thread buckets, one cell each) by descending bucket
+//   max_n, then narrow quads (64-thread buckets, up to four cells each, per
+//   bucket) by descending max_n: the stragglers are dispatched first.
+// Off the hot path: the bucket cell lists are copied back synchronously.
+static int wva_build_tasks(WvaCtx *c) {
+  c->fused_path = 0;
+  c->n_tasks = c->n_tasks_b = 0;
+  c->lds_a = c->lds_b = 0;
+  if (!c->fused_on) return 0;
+  // every set_buckets starts the counters from zero (s0 is idle: ticks are
+  // synchronous), whichever path the layout takes
+  if (hipMemsetAsync(c->done, 0, c->done_bytes, c->s0) != hipSuccess) return -55;
+  c->done_dirty = 0;
+  if (c->topo == nullptr || c->n_buckets < 1) return 0;
+  const int nb = c->n_buckets;
+  int order[WVA_MAX_BUCKETS];
+  size_t need[WVA_MAX_BUCKETS];
+  for (int i = 0; i < nb; ++i) {
+    const WvaBucket &b = c->buckets[i];
+    // only (64 or 256 threads, geometry in LDS) buckets fuse; anything else
+    // (an INFERNO_NT_* override, the huge tier) keeps the whole tick on the
+    // bucket launches, which also report a bad bucket as they always did
+    if ((b.nt != WVA_WAVE && b.nt != WVA_TICK_NT) || b.g_inv != nullptr ||
+        b.g_anchor != nullptr || b.max_n < 1 || b.max_n > WVA_XL_MAX_N || b.n_blocks < 0)
+      return 0;
+    need[i] = wva_cell_lds_bytes(b.max_n, b.nt);
+    order[i] = i;
+  }
+  // wide before narrow, then descending max_n (insertion sort, stable)
+  auto before = [&](int x, int y) {
+    const WvaBucket &bx = c->buckets[x], &by = c->buckets[y];
+    if (bx.nt != by.nt) return bx.nt > by.nt;
+    return bx.max_n > by.max_n;
+  };
+  for (int i = 1; i < nb; ++i)
+    for (int k = i; k > 0 && before(order[k], order[k - 1]); --k) {
+      const int t = order[k];
+      order[k] = order[k - 1];
+      order[k - 1] = t;
+    }
+
+  if (hipDeviceSynchronize() != hipSuccess) return -50;
+  std::vector<int> seg((size_t)c->n_srv + 1);
+  if (hipMemcpy(seg.data(), c->seg_start, seg.size() * sizeof(int), hipMemcpyDeviceToHost) !=
+      hipSuccess)
+    return -51;
+  // the kernel takes a server's cell count from seg_start and a cell's server
+  // from cell_server: they must describe the same segments
+  for (int k = 0; k < c->n_cells; ++k) {
+    const int s = c->topo_cell_server[k];
+    if (k < seg[s] || k >= seg[s + 1]) return 0;
+  }
+
+  std::vector<int4> tasks;
+  std::vector<int> ids;
+  std::vector<unsigned char> seen((size_t)c->n_cells, 0);
+  size_t narrow_need = 0, wide_top = 0, wide_rest = 0;
+  int n_top = 0;  // tasks of the widest (first) wide bucket
+  for (int q = 0; q < nb; ++q) {
+    const WvaBucket &b = c->buckets[order[q]];
+    if (b.n_blocks == 0) continue;
+    ids.resize((size_t)b.n_blocks);
+    if (b.cell_ids == nullptr) {
+      for (int k = 0; k < b.n_blocks; ++k) ids[k] = k;
+    } else if (hipMemcpy(ids.data(), b.cell_ids, ids.size() * sizeof(int),
+                         hipMemcpyDeviceToHost) != hipSuccess) {
+      return -52;
+    }
+    // every cell exactly once over all buckets, or a server's counter would
+    // never (or too early) reach its segment length
+    for (int k = 0; k < b.n_blocks; ++k) {
+      if (ids[k] < 0 || ids[k] >= c->n_cells || seen[ids[k]]) return 0;
+      seen[ids[k]] = 1;
+    }
+    if (b.nt == WVA_TICK_NT) {
+      if (tasks.empty()) {
+        wide_top = need[order[q]];
+        n_top = b.n_blocks;
+      } else if (need[order[q]] > wide_rest) {
+        wide_rest = need[order[q]];
+      }
+      for (int k = 0; k < b.n_blocks; ++k) tasks.push_back(make_int4(ids[k], WVA_TASK_WIDE, 0, 0));
+    } else {
+      if (need[order[q]] > narrow_need) narrow_need = need[order[q]];
+      for (int k = 0; k < b.n_blocks; k += 4) {
+        int4 t = make_int4(ids[k], -1, -1, -1);
+        if (k + 1 < b.n_blocks) t.y = ids[k + 1];
+        if (k + 2 < b.n_blocks) t.z = ids[k + 2];
+        if (k + 3 < b.n_blocks) t.w = ids[k + 3];
+        tasks.push_back(t);
+      }
+    }
+  }
+  for (int k = 0; k < c->n_cells; ++k)
+    if (!seen[k]) return 0;
+  if (tasks.empty()) return 0;
+
+  // LDS: a wide block takes its bucket's need, a narrow block four slices of
+  // the narrow buckets' largest need rounded up to 16 bytes
+  const size_t stride = (narrow_need + 15) & ~(size_t)15;
+  const size_t rest = wide_rest > 4 * stride ? wide_rest : 4 * stride;
+  const size_t all = wide_top > rest ? wide_top : rest;
+  const int n_tasks = (int)tasks.size();
+  // The fused launch pays where the tick is bound by launches and queues, not
+  // by the chip: a grid of at most one round of blocks at the kernel's launch
+  // bounds (4 per CU). A larger fleet is throughput-bound, and there the
+  // bucket launches, with their one-wave blocks, measured faster (config5,
+  // 32768 cells: 0.735 ms/step against 1.166).
+  if ((long)n_tasks > 4L * c->n_cus_dev) return 0;
+  int path = 1;
+  size_t lds_a = all, lds_b = 0;
+  // Residency rule. When the widest bucket (the XL tier) alone raises the
+  // launch's LDS, its tasks can go to a second launch with their own LDS
+  // size, and the rest keeps the smaller one (more blocks per CU). The
+  // fork/join of that launch measured 24 us on the flagship, about one round
+  // of narrow blocks, so it is taken only when the single launch would need
+  // more than one extra round: n_tasks > 2 x the blocks resident at once.
+  if (n_top > 0 && n_top < n_tasks && wide_top > rest &&
+      (long)n_tasks > 2 * wva_tick_slots(c, all)) {
+    path = 2;
+    lds_a = rest;
+    lds_b = wide_top;
+  }
+  if (all > (size_t)160 * 1024) return 0;
+  if (wva_optin_lds(reinterpret_cast<const void *>(&wva_tick_t), all) != 0) {
+    (void)hipGetLastError();
+    return 0;
+  }
+
+  // servers without cells never see an arrival: their record is the constant
+  // one wva_winner writes for them, stored here once
+  for (int s = 0; s < c->n_srv; ++s) {
+    if (seg[s + 1] != seg[s]) continue;
+    const int none = -1, zero = 0;
+    for (int r = 0; r < WVA_REC_ROWS; ++r) {
+      const int *v = (r == 6 || r == 9) ? &none : &zero;  // acc code, winner cell
+      if (hipMemcpy((int *)c->gather + (size_t)r * c->n_srv + s, v, sizeof(int),
+                    hipMemcpyHostToDevice) != hipSuccess)
+        return -53;
+    }
+    if (hipMemcpy(c->winner + s, &none, sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+      return -53;
+  }
+
+  if (n_tasks > c->tasks_cap) {
+    WvaDeviceGuard on_dev(c->dev_dyn);
+    if (c->tasks != nullptr) (void)hipFree(c->tasks);
+    c->tasks = nullptr;
+    c->tasks_cap = 0;
+    void *t = nullptr;
+    if (hipMalloc(&t, (size_t)n_tasks * sizeof(int4)) != hipSuccess || t == nullptr) {
+      (void)hipGetLastError();
+      return 0;
+    }
+    c->tasks = (int4 *)t;
+    c->tasks_cap = n_tasks;
+  }
+  if (hipMemcpy(c->tasks, tasks.data(), (size_t)n_tasks * sizeof(int4), hipMemcpyHostToDevice) !=
+      hipSuccess)
+    return -54;
+  c->n_tasks = n_tasks;
+  c->n_tasks_b = path == 2 ? n_top : 0;
+  c->narrow_stride = (int)(stride / sizeof(double));
+  c->lds_a = lds_a;
+  c->lds_b = lds_b;
+  c->fused_path = path;
   return 0;
 }
 
@@ -320,7 +603,8 @@ extern "C" int wva_ctx_set_buckets(void *ctx, int n_buckets, const int *nts,
   // capture already proved unsupported, which is sticky)
   if (c->graph_state == 1) (void)hipGraphExecDestroy(c->graph_exec);
   if (c->graph_state != -1) c->graph_state = 0;
-  return 0;
+  // the fused tick's task table follows the layout (and zeroes done[])
+  return wva_build_tasks(c);
 }
 
 // The bucket sweeps of one pass, after the uploads queued on s0: record the
@@ -348,8 +632,18 @@ static int wva_run_buckets(WvaCtx *c, const WvaCellsOut &out, const WvaPlanArgs 
   return 0;
 }
 
+// n tasks of the fused tick's table from task0 on, `lds` bytes of dynamic LDS
+static void wva_tick_launch(WvaCtx *c, int task0, int n, size_t lds, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(wva_tick_t, dim3(n), dim3(WVA_TICK_NT), lds, s, c->in, c->out, c->tasks,
+                     task0, n, c->narrow_stride, c->analyzer_mode, c->cv2, c->memo, c->memo_cnt,
+                     c->dev_cell_server, c->done, c->seg_start, c->cell_acc, c->n_srv, c->gather,
+                     c->winner);
+}
+
 // enqueue the whole per-tick pipeline on the ctx's streams (used both for
-// eager execution and for stream capture into a hipGraph)
+// eager execution and for stream capture into a hipGraph): H2D, then either
+// the fused tick's launch(es) or the bucket launches and wva_winner, then D2H
 static int wva_enqueue_pipeline(WvaCtx *c) {
   hipError_t err;
   // 1. dynamic H2D (pinned -> device), the whole block in one copy
@@ -357,17 +651,33 @@ static int wva_enqueue_pipeline(WvaCtx *c) {
                        hipMemcpyHostToDevice, c->s0);
   if (err != hipSuccess) return (int)err;
 
-  // 2. bucket launches, overlapped on the side streams
-  const int rc = wva_run_buckets(c, c->out, nullptr);
-  if (rc != 0) return rc;
+  if (c->fused_path != 0) {
+    // 2+3. sweep and winner records in one launch of the task table (two when
+    // the residency rule split off the widest bucket: those tasks go first, on
+    // side[0] behind the upload, and are joined before the download)
+    if (c->fused_path == 2) {
+      if (hipEventRecord(c->e_up, c->s0) != hipSuccess) return -10;
+      if (hipStreamWaitEvent(c->side[0], c->e_up, 0) != hipSuccess) return -11;
+      wva_tick_launch(c, 0, c->n_tasks_b, c->lds_b, c->side[0]);
+      if (hipEventRecord(c->e_b[0], c->side[0]) != hipSuccess) return -12;
+    }
+    wva_tick_launch(c, c->n_tasks_b, c->n_tasks - c->n_tasks_b, c->lds_a, c->s0);
+    if (c->fused_path == 2 && hipStreamWaitEvent(c->s0, c->e_b[0], 0) != hipSuccess) return -14;
+    err = hipGetLastError();
+    if (err != hipSuccess) return (int)err;
+  } else {
+    // 2. bucket launches, overlapped on the side streams
+    const int rc = wva_run_buckets(c, c->out, nullptr);
+    if (rc != 0) return rc;
 
-  // 3. winner selection + winner records on s0, one launch
-  hipLaunchKernelGGL(wva_winner, dim3(c->n_srv), dim3(WVA_WAVE), 0, c->s0, c->out.value,
-                     c->out.feasible, c->out.zero_empty, c->cell_acc, c->out.num_replicas,
-                     c->out.batch, c->out.cost, c->out.itl, c->out.ttft, c->out.rho,
-                     c->out.max_rate, c->seg_start, c->n_srv, c->gather, c->winner);
-  err = hipGetLastError();
-  if (err != hipSuccess) return (int)err;
+    // 3. winner selection + winner records on s0, one launch
+    hipLaunchKernelGGL(wva_winner, dim3(c->n_srv), dim3(WVA_WAVE), 0, c->s0, c->out.value,
+                       c->out.feasible, c->out.zero_empty, c->cell_acc, c->out.num_replicas,
+                       c->out.batch, c->out.cost, c->out.itl, c->out.ttft, c->out.rho,
+                       c->out.max_rate, c->seg_start, c->n_srv, c->gather, c->winner);
+    err = hipGetLastError();
+    if (err != hipSuccess) return (int)err;
+  }
 
   // 4. D2H of the winner records, one copy
   err = hipMemcpyAsync(c->pin_out, c->gather, (size_t)WVA_REC_ROWS * c->n_srv * 4,
@@ -403,8 +713,22 @@ extern "C" int wva_ctx_tick(void *ctx, const float *arrival, const int *in_tok, 
   return launch ? wva_reconcile(ctx) : 0;
 }
 
+static int wva_reconcile_run(WvaCtx *c);
+
 extern "C" int wva_reconcile(void *ctx) {
   WvaCtx *c = (WvaCtx *)ctx;
+  // a tick that failed may have left arrivals in done[]: zero it first. In
+  // steady state the last arrivers keep it zero and nothing is queued here.
+  if (c->fused_path != 0 && c->done_dirty) {
+    if (hipMemsetAsync(c->done, 0, c->done_bytes, c->s0) != hipSuccess) return -56;
+    c->done_dirty = 0;
+  }
+  const int rc = wva_reconcile_run(c);
+  if (rc != 0) c->done_dirty = 1;
+  return rc;
+}
+
+static int wva_reconcile_run(WvaCtx *c) {
   // replay the captured pipeline when available: every buffer pointer and
   // kernel argument is ctx-stable between ticks, so the graph stays valid
   // until the bucket layout changes (set_buckets invalidates)
@@ -888,6 +1212,9 @@ extern "C" void wva_ctx_destroy(void *ctx) {
     (void)hipEventDestroy(c->e_b[i]);
   }
   if (c->memo != nullptr) (void)hipFree(c->memo);
+  if (c->done != nullptr) (void)hipFree(c->done);
+  if (c->dev_cell_server != nullptr) (void)hipFree(c->dev_cell_server);
+  if (c->tasks != nullptr) (void)hipFree(c->tasks);
   wva_plan_release(c);
   wva_slo_release(c);
   wva_lim_release(c);

@@ -57,6 +57,13 @@
 //   K5 wva_plan_greedy: the capacity-limited solution of every scenario, one
 //       wave per scenario.
 //
+//   K6 wva_tick_t: the reconcile tick in ONE launch. K1's cell function per
+//       cell of a task table (one 256-thread cell or four one-wave cells per
+//       block) and K4b's winner step by whichever cell of a server arrives
+//       last (agent-scope release / acquire around a per-server counter;
+//       nobody waits). The context uses it whenever every bucket is 64 or 256
+//       threads wide with its geometry in LDS; K1 + K4b remain for the rest.
+//
 //   (K3 is unused: the numbers are kept stable for the documents that cite
 //   them.)
 //
@@ -144,7 +151,20 @@ struct WvaCellsOut {
 // scratch is LDS (>= 32 doubles); parts use disjoint scratch regions, and the
 // __syncthreads calls are executed uniformly by the whole block (both parts
 // run their evaluations in lock-step).
+//
+// A one-wave cell (NT == 64) takes only the shuffle branches below: no
+// barrier, no scratch, no threadIdx.x. The fused tick kernel depends on that:
+// the four waves of its narrow blocks run four independent cells and leave at
+// different times. The multi-wave branches index by threadIdx.x, which is the
+// cell's thread index there because a multi-wave cell always owns its block.
 // ---------------------------------------------------------------------------
+// true when a part of NT / PART threads reduces by shuffles alone
+template <int NT, int PART>
+constexpr bool wva_red_barrier_free() {
+  return NT / PART <= WVA_WAVE;
+}
+static_assert(wva_red_barrier_free<WVA_WAVE, 1>() && wva_red_barrier_free<WVA_WAVE, 2>(),
+              "one-wave cells must reduce without a barrier (fused tick, narrow blocks)");
 template <int NT, int PART>
 __device__ __forceinline__ double red_max_p(double v, double *scratch) {
   constexpr int W = NT / PART;  // threads per part
@@ -325,6 +345,10 @@ template <int NT, int PART>
 __device__ ChainOut chain_eval(double lam, const ChainGeom &g, double logsN, int N, int K,
                                double *scratch) {
   constexpr int W = NT / PART;
+  // the thread's index within its part. W divides 64 for a one-wave cell, so
+  // threadIdx.x % W is also right when such a cell is one wave of a wider
+  // block (its cell-relative index is threadIdx.x & 63)
+  static_assert(NT > WVA_WAVE || WVA_WAVE % W == 0, "one-wave cell: W must divide the wave");
   const int lane = threadIdx.x % W;
   const double loglam = log(lam);
 
@@ -426,7 +450,8 @@ __device__ ChainOut chain_eval(double lam, const ChainGeom &g, double logsN, int
     o.serv = scratch[part * 4 + 2];
     o.in_servers = scratch[part * 4 + 3];
   } else {
-    // single-wave part: lockstep execution makes the redundancy free
+    // single-wave part: lockstep execution makes the redundancy free (and the
+    // one-wave cell stays barrier-free, which the fused tick relies on)
     o = chain_tail_stats(lam, loglam, logsN, g.S_total, N, K, m, head_sum, head_n_sum);
   }
   return o;
@@ -504,14 +529,18 @@ __device__ __forceinline__ bool within_tol(double x, double value) {
 // the partial reductions stay uniform; a block-wide vote ends the loop when
 // both halves are done. This halves the sequential depth of the sizing
 // phase vs running the two searches back to back.
-template <int NT>
+template <int NT, bool SHARED = false>
 __device__ void dual_bisect(double lam_min, double lam_max, float t_ttft, float t_itl,
                             const ChainGeom &g, double logsN, int N, int K, float gamma,
                             float delta, float alpha, float beta, int in_tok, int out_tok,
                             double *scratch, double *res_slot, double lam_star[2],
                             int ind_out[2], int mode, double cv2, double mu) {
+  // tid: the thread's index within the cell's NT threads. SHARED: the cell is
+  // one wave of a wider block (fused tick, narrow blocks) and its threads are
+  // threadIdx.x & 63; otherwise the cell owns its block.
+  static_assert(!SHARED || NT == WVA_WAVE, "only a one-wave cell shares a block");
   constexpr int W = NT / 2;
-  const int tid = threadIdx.x;
+  const int tid = SHARED ? (int)(threadIdx.x & (WVA_WAVE - 1)) : (int)threadIdx.x;
   const int h = tid / W;  // 0 = TTFT, 1 = ITL
   const double target = (h == 0) ? (double)t_ttft : (double)t_itl;
   const bool active = target > 0.0;
@@ -582,6 +611,8 @@ __device__ void dual_bisect(double lam_min, double lam_max, float t_ttft, float 
     }
     const bool done = (phase == 3);
     if constexpr (NT == WVA_WAVE) {
+      // one-wave cell: a wave vote, no barrier (fused-tick narrow blocks rely
+      // on the NT == 64 instantiation executing no barrier at all)
       if (__all(done ? 1 : 0)) break;
     } else {
       if (__syncthreads_and(done ? 1 : 0)) break;
@@ -594,7 +625,7 @@ __device__ void dual_bisect(double lam_min, double lam_max, float t_ttft, float 
     res_slot[2 * h + 1] = (double)ind;
   }
   if constexpr (NT == WVA_WAVE) {
-    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_s_waitcnt(0);  // one-wave cell: barrier-free (see above)
   } else {
     __syncthreads();
   }
@@ -819,7 +850,7 @@ using WvaPlanParam = typename std::conditional<
 // false when a target cannot be met; else tput is the throughput at the sized
 // rate (req/msec). Every thread of the block calls this with the same
 // arguments and gets the same result.
-template <int NT>
+template <int NT, bool SHARED = false>
 __device__ __forceinline__ bool wva_size_cell(float t_ttft, float t_itl, float t_tps,
                                               double lam_min, double lam_max,
                                               const ChainGeom &geom, double logsN, int N,
@@ -830,7 +861,7 @@ __device__ __forceinline__ bool wva_size_cell(float t_ttft, float t_itl, float t
                                               double &tput) {
   double lam_star[2];
   int inds[2];
-  dual_bisect<NT>(lam_min, lam_max, t_ttft, t_itl, geom, logsN, N, Kstates, gamma, delta, alpha,
+  dual_bisect<NT, SHARED>(lam_min, lam_max, t_ttft, t_itl, geom, logsN, N, Kstates, gamma, delta, alpha,
                   beta, in_tok, out_tok, scratch, res_slot, lam_star, inds, analyzer_mode, cv2d,
                   mu);
   bool feasible = true;
@@ -882,21 +913,33 @@ __device__ __forceinline__ bool wva_size_cell(float t_ttft, float t_itl, float t
 // into slot (t * n_load + s) * n_cells + cell. Slice (t, s) is bit for bit what
 // a single-scenario launch with those targets and that arrival rate writes.
 // Its differences are `if constexpr (SLO)`.
-template <int NT, bool GMEM, int MODE>
-__device__ __forceinline__ void wva_sweep_body(const WvaCellsIn &in, const WvaCellsOut &out,
-                                               int n_blocks, const int *cell_ids, int max_n,
-                                               int analyzer_mode, float cv2, float *g_inv,
-                                               double *g_anchor, WvaMemoRec *memo,
-                                               unsigned *memo_cnt,
-                                               const WvaPlanParam<MODE> &plan) {
+//
+// wva_cell_body is the computation of ONE cell by NT threads, separate from
+// the block that runs it: `cell` is the cell, `tid` the thread's index within
+// the cell's NT threads, `smem` the base of the cell's LDS region and `slab`
+// the index of its global-memory slab (GMEM only). The bucket kernels
+// (WVA_SWEEP_BODY below) run one cell per block with tid = threadIdx.x, the
+// base of dynamic LDS and slab = blockIdx.x; the fused tick kernel (wva_tick_t)
+// also runs four one-wave cells side by side in one 256-thread block (SHARED:
+// the few places below the cell function that read threadIdx.x then mask it). It
+// returns at five exits (zero-traffic, memo-infeasible replay, degenerate
+// rate, SLO-infeasible, sized), every one uniform over the cell's threads.
+//
+// Outputs are stored by the cell's thread 0 ONLY, at every exit: each
+// WVA_WRITE_ZERO / WVA_WRITE_INFEASIBLE below sits under `tid == 0`,
+// wva_eval_scenario stores under `tid == 0`, and memo_miss_store does too.
+// The fused tick's hand-off (release by that one lane) depends on it.
+template <int NT, bool GMEM, int MODE, bool SHARED = false>
+__device__ __forceinline__ void wva_cell_body(const WvaCellsIn &in, const WvaCellsOut &out,
+                                              const int cell, const int tid, double *smem,
+                                              const unsigned slab, int max_n, int analyzer_mode,
+                                              float cv2, float *g_inv, double *g_anchor,
+                                              WvaMemoRec *memo, unsigned *memo_cnt,
+                                              const WvaPlanParam<MODE> &plan) {
   constexpr bool PLAN = MODE == WVA_MODE_PLAN;
   constexpr bool SLO = MODE == WVA_MODE_SLO;
   // memo: per-cell sizing records (nullptr = memo off: every cell is sized
   // from scratch and nothing is recorded); memo_cnt: [0] hits, [1] misses
-  extern __shared__ double smem[];
-  if ((int)blockIdx.x >= n_blocks) return;
-  const int cell = cell_ids ? cell_ids[blockIdx.x] : (int)blockIdx.x;
-  const int tid = threadIdx.x;
   // LDS layout: [0..31] reduction scratch, [32] S_total slot, [40..] chain
   // geometry (inv_s_t then S_anchor); 40-double header keeps alignment.
   double *scratch = smem;
@@ -1065,8 +1108,8 @@ __device__ __forceinline__ void wva_sweep_body(const WvaCellsIn &in, const WvaCe
     // per-block slab in global memory, strided by the bucket's max geometry
     const int chunk_max = (max_n + NT - 1) / NT;
     const int ksub_max = (chunk_max + WVA_SUB - 1) / WVA_SUB;
-    inv_s_t = g_inv + (size_t)blockIdx.x * ((size_t)chunk_max * NT);
-    S_anchor = g_anchor + (size_t)blockIdx.x * ((size_t)NT * ksub_max);
+    inv_s_t = g_inv + (size_t)slab * ((size_t)chunk_max * NT);
+    S_anchor = g_anchor + (size_t)slab * ((size_t)NT * ksub_max);
   } else {
     // LDS partition (S points at the dynamic smem base; scratch precedes)
     inv_s_t = (float *)S;                 // chunk*NT floats
@@ -1111,7 +1154,9 @@ __device__ __forceinline__ void wva_sweep_body(const WvaCellsIn &in, const WvaCe
     S_anchor[tid * ksub + k] += offset;
   if (tid == NT - 1) *total_slot = offset + local;  // S[N]
   if constexpr (NT == WVA_WAVE) {
-    __builtin_amdgcn_s_waitcnt(0);  // single wave: order LDS writes before reads
+    // single wave: order LDS writes before reads. No barrier anywhere in the
+    // geometry build of a one-wave cell (the scan above is shuffles only).
+    __builtin_amdgcn_s_waitcnt(0);
   } else {
     __syncthreads();
   }
@@ -1181,7 +1226,7 @@ __device__ __forceinline__ void wva_sweep_body(const WvaCellsIn &in, const WvaCe
       } else if (base && memo_status == WVA_MEMO_INFEASIBLE) {
         feasible = false;  // replay of the infeasible verdict, for this t only
       } else {
-        feasible = wva_size_cell<NT>(plan.scen_ttft[kt], plan.scen_itl[kt], t_tps, lam_min,
+        feasible = wva_size_cell<NT, SHARED>(plan.scen_ttft[kt], plan.scen_itl[kt], t_tps, lam_min,
                                      lam_max, geom, logsN, N, Kstates, gamma, delta, alpha, beta,
                                      in_tok, out_tok, scratch, total_slot + 1, analyzer_mode,
                                      cv2d, mu, tput_at_lam);
@@ -1218,7 +1263,7 @@ __device__ __forceinline__ void wva_sweep_body(const WvaCellsIn &in, const WvaCe
       // modes through it moves their register allocation)
       double lam_star[2];
       int inds[2];
-      dual_bisect<NT>(lam_min, lam_max, t_ttft, t_itl, geom, logsN, N, Kstates, gamma, delta,
+      dual_bisect<NT, SHARED>(lam_min, lam_max, t_ttft, t_itl, geom, logsN, N, Kstates, gamma, delta,
                       alpha, beta, in_tok, out_tok, scratch, total_slot + 1, lam_star, inds,
                       analyzer_mode, cv2d, mu);
       bool feasible = true;
@@ -1283,14 +1328,25 @@ __device__ __forceinline__ void wva_sweep_body(const WvaCellsIn &in, const WvaCe
 #undef WVA_WRITE_ZERO
 }
 
+// One cell per block: block blockIdx.x of a bucket launch computes cell
+// cell_ids[blockIdx.x] with all its threads in the whole of dynamic LDS.
+// (a macro, not one more function: the bucket kernels call the cell function
+// at the inlining depth the sweep body always had)
+#define WVA_SWEEP_BODY(MODE, plan)                                                          \
+  extern __shared__ double smem[];                                                          \
+  if ((int)blockIdx.x >= n_blocks) return;                                                  \
+  const int cell = cell_ids ? cell_ids[blockIdx.x] : (int)blockIdx.x;                       \
+  wva_cell_body<NT, GMEM, MODE>(in, out, cell, (int)threadIdx.x, smem, blockIdx.x,          \
+                                max_n, analyzer_mode, cv2, g_inv, g_anchor, memo, memo_cnt, \
+                                plan)
+
 template <int NT, bool GMEM>
 __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut out, int n_blocks,
                                                   const int *cell_ids, int max_n,
                                                   int analyzer_mode, float cv2,
                                                   float *g_inv, double *g_anchor,
                                                   WvaMemoRec *memo, unsigned *memo_cnt) {
-  wva_sweep_body<NT, GMEM, WVA_MODE_SWEEP>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2,
-                                           g_inv, g_anchor, memo, memo_cnt, WvaNoPlan{});
+  WVA_SWEEP_BODY(WVA_MODE_SWEEP, WvaNoPlan{});
 }
 
 // scenario-planning sweep: out arrays are [n_scen][n_cells]; in.arrival_rate
@@ -1308,8 +1364,7 @@ __global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES) wva_plan_t(WvaCellsIn 
                                                  int analyzer_mode, float cv2, float *g_inv,
                                                  double *g_anchor, WvaMemoRec *memo,
                                                  unsigned *memo_cnt, WvaPlanArgs plan) {
-  wva_sweep_body<NT, GMEM, WVA_MODE_PLAN>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2,
-                                          g_inv, g_anchor, memo, memo_cnt, plan);
+  WVA_SWEEP_BODY(WVA_MODE_PLAN, plan);
 }
 
 // SLO-planning sweep: out arrays are [n_tgt][n_load][n_cells]; in.arrival_rate
@@ -1321,9 +1376,9 @@ __global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
     wva_slo_plan_t(WvaCellsIn in, WvaCellsOut out, int n_blocks, const int *cell_ids, int max_n,
                    int analyzer_mode, float cv2, float *g_inv, double *g_anchor, WvaMemoRec *memo,
                    unsigned *memo_cnt, WvaSloArgs plan) {
-  wva_sweep_body<NT, GMEM, WVA_MODE_SLO>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2,
-                                         g_inv, g_anchor, memo, memo_cnt, plan);
+  WVA_SWEEP_BODY(WVA_MODE_SLO, plan);
 }
+#undef WVA_SWEEP_BODY
 
 // ---------------------------------------------------------------------------
 // K2: segmented argmin per server over the sweep output.
@@ -1391,6 +1446,14 @@ static int wva_optin_lds(const void *func, size_t lds) {
   return 0;
 }
 
+// dynamic LDS of one LDS-resident cell of up to max_n states on nt threads:
+// header(40) + inv_s floats (chunk*nt/2 doubles, rounded up) + anchors
+static size_t wva_cell_lds_bytes(int max_n, int nt) {
+  const int chunk = (max_n + nt - 1) / nt;
+  const int ksub = (chunk + WVA_SUB - 1) / WVA_SUB;
+  return (size_t)(40 + (chunk * nt + 1) / 2 + (size_t)nt * ksub) * sizeof(double);
+}
+
 static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_ids,
                               int analyzer_mode, float cv2, hipStream_t s,
                               const WvaCellsIn &in, const WvaCellsOut &out, float *g_inv,
@@ -1402,12 +1465,8 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
   if (max_n < 1) return -2;
   if (!gmem && max_n > WVA_XL_MAX_N) return -2;
   if (gmem && max_n > WVA_HUGE_MAX_N) return -4;
-  const int chunk = (max_n + nt - 1) / nt;
-  const int ksub = (chunk + 32 - 1) / 32;  // WVA_SUB
-  // header(40) + inv_s floats (chunk*nt/2 doubles, rounded up) + anchors;
   // the spill path keeps only the header in LDS
-  size_t lds = gmem ? (size_t)40 * sizeof(double)
-                    : (size_t)(40 + (chunk * nt + 1) / 2 + (size_t)nt * ksub) * sizeof(double);
+  size_t lds = gmem ? (size_t)40 * sizeof(double) : wva_cell_lds_bytes(max_n, nt);
   if (lds > 160 * 1024) return -5;  // exceeds the CU's LDS
   // the >64 KiB opt-in is per function, so the planning instantiation of a
   // width opts in separately from the reconcile one
@@ -1514,8 +1573,9 @@ __device__ __forceinline__ int wva_winner_record(
     const float *value, const uint8_t *feasible, const uint8_t *zero_empty, const int *cell_acc,
     const int *num_replicas, const int *batch, const float *cost, const float *itl,
     const float *ttft, const float *rho, const float *max_rate, const int *seg_start, int n_srv,
-    size_t base, int srv, float *gf, int *gi, int &acc, int &reps) {
-  const int lane = threadIdx.x;
+    size_t base, int srv, float *gf, int *gi, int &acc, int &reps, const int lane) {
+  // lane: the thread's lane in the wave that runs this (threadIdx.x in the
+  // one-wave blocks of K4 / K4b; threadIdx.x & 63 in the fused tick kernel)
   const int beg = seg_start[srv], end = seg_start[srv + 1];
   float best = INFINITY;
   int best_i = -1;
@@ -1569,7 +1629,7 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_reduce(
   wva_winner_record(value, feasible, zero_empty, cell_acc, num_replicas, batch, cost, itl, ttft,
                     rho, max_rate, seg_start, n_srv, (size_t)sc * (size_t)n_cells, srv,
                     pf + (size_t)sc * 6 * (size_t)n_srv, pi + (size_t)sc * 4 * (size_t)n_srv, acc,
-                    reps);
+                    reps, (int)threadIdx.x);
   if (threadIdx.x != 0) return;
   if (acc >= 0 && acc < n_acc && reps > 0)
     atomicAdd(totals + (size_t)sc * (size_t)n_acc + (size_t)acc, (unsigned long long)reps);
@@ -1592,8 +1652,101 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_winner(
   int acc, reps;
   const int w = wva_winner_record(value, feasible, zero_empty, cell_acc, num_replicas, batch, cost,
                                   itl, ttft, rho, max_rate, seg_start, n_srv, 0, srv,
-                                  (float *)rec, (int *)rec + (size_t)6 * (size_t)n_srv, acc, reps);
+                                  (float *)rec, (int *)rec + (size_t)6 * (size_t)n_srv, acc, reps,
+                                  (int)threadIdx.x);
   if (threadIdx.x == 0) winner[srv] = w;
+}
+
+// ---------------------------------------------------------------------------
+// K6 wva_tick_t: the reconcile tick's sweep AND winner step in one launch.
+// 256 threads; block b takes task tasks[task0 + b] of the context's task table
+// (wva_ctx_set_buckets builds it), four int32 words:
+//   wide   {cell, WVA_TASK_WIDE, -, -}: one cell on the whole block, the
+//          NT = 256 cell function in the whole of dynamic LDS (large, XL);
+//   narrow {c0, c1, c2, c3}: wave w runs the NT = 64 cell function on cell cw
+//          in its own LDS slice (base + w * narrow_stride doubles); -1 = empty
+//          slot, that wave does nothing. The one-wave cell function executes
+//          no barrier (see the reductions, dual_bisect and the geometry
+//          build), so the four waves never wait for each other and may leave
+//          at different times.
+// NT is the bucket kernels' NT for the same cell, so the reduction order, the
+// memo key and every output bit are theirs.
+//
+// Winner step, last-arriver form. Every cell arrives exactly once per tick at
+// done[server of the cell]: after the cell function has returned, by whichever
+// exit, the lane that stored the outputs (the cell's thread 0, the only lane
+// that stores any) drains its stores, releases at agent scope and adds 1 to
+// the counter. The arriver that draws segment length - 1 knows every cell of
+// the server has released its outputs: its wave acquires at agent scope,
+// writes the server's winner record (wva_winner_record, as K4b) and puts the
+// counter back to 0. Nobody polls or waits on a counter, so nothing here
+// depends on which blocks are resident or in what order they run; the
+// counters also work across two launches of this kernel in one tick.
+//
+// The acquire is required even though the arriver has not read these outputs
+// before: sixteen cells share a 64-byte line of every output array, so this
+// CU's L1 can hold a line that a neighbouring server's winner step read
+// earlier in the launch, from before this server's cells stored into it. The
+// winner's loads of the outputs are plain VECTOR loads behind that acquire:
+// the output pointers carry no const __restrict__ here, which would let the
+// compiler move them to the scalar cache that the acquire does not cover.
+//
+// Invariant: after a completed tick every done[] word is 0 (each server's
+// last arriver resets it). The host zeroes the array at creation, whenever the
+// task table changes and after a failed tick, never per tick.
+// ---------------------------------------------------------------------------
+#define WVA_TASK_WIDE (-2)
+#define WVA_TICK_NT 256
+
+__global__ void __launch_bounds__(WVA_TICK_NT, 4)
+    wva_tick_t(WvaCellsIn in, WvaCellsOut out, const int4 *tasks, int task0, int n_tasks,
+               int narrow_stride, int analyzer_mode, float cv2, WvaMemoRec *memo,
+               unsigned *memo_cnt, const int *cell_server, unsigned *done, const int *seg_start,
+               const int *cell_acc, int n_srv, void *rec, int *winner) {
+  extern __shared__ double smem[];
+  if ((int)blockIdx.x >= n_tasks) return;
+  const int4 task = tasks[task0 + (int)blockIdx.x];
+  const int lane = (int)threadIdx.x & (WVA_WAVE - 1);
+  int cell;
+  if (task.y == WVA_TASK_WIDE) {  // block-uniform
+    cell = task.x;
+    wva_cell_body<WVA_TICK_NT, false, WVA_MODE_SWEEP>(in, out, cell, (int)threadIdx.x, smem, 0, 0,
+                                                      analyzer_mode, cv2, nullptr, nullptr, memo,
+                                                      memo_cnt, WvaNoPlan{});
+    // the cell's thread 0 is in wave 0: that wave arrives, the others are done
+    if ((int)threadIdx.x >= WVA_WAVE) return;
+  } else {
+    const int w = (int)threadIdx.x / WVA_WAVE;  // wave-uniform
+    cell = w == 0 ? task.x : w == 1 ? task.y : w == 2 ? task.z : task.w;
+    if (cell < 0) return;
+    wva_cell_body<WVA_WAVE, false, WVA_MODE_SWEEP, true>(in, out, cell, lane, smem + w * narrow_stride,
+                                                   0, 0, analyzer_mode, cv2, nullptr, nullptr,
+                                                   memo, memo_cnt, WvaNoPlan{});
+  }
+  // ---- arrival: one wave per cell from here on, lane 0 stored the outputs
+  const int srv = cell_server[cell];
+  unsigned old = 0u;
+  if (lane == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    // kept, in this order: the fence's own wait is not guaranteed
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    old = __hip_atomic_fetch_add(done + srv, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  old = __shfl(old, 0, WVA_WAVE);
+  const unsigned seg_len = (unsigned)(seg_start[srv + 1] - seg_start[srv]);
+  if (old + 1u != seg_len) return;  // wave-uniform: not the server's last cell
+  // ---- last arriver: the server's winner step
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  int acc, reps;
+  const int win = wva_winner_record(out.value, out.feasible, out.zero_empty, cell_acc,
+                                    out.num_replicas, out.batch, out.cost, out.itl, out.ttft,
+                                    out.rho, out.max_rate, seg_start, n_srv, 0, srv, (float *)rec,
+                                    (int *)rec + (size_t)6 * (size_t)n_srv, acc, reps, lane);
+  if (lane == 0) {
+    winner[srv] = win;
+    __hip_atomic_store(done + srv, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
 }
 
 // ---------------------------------------------------------------------------

@@ -212,6 +212,13 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
         ctypes.POINTER(ctypes.c_uint),  # hits
         ctypes.POINTER(ctypes.c_uint),  # misses
     ]
+    # fused tick diagnostics (engine/native_ctx.py NativeCtx.fused_state)
+    lib.wva_ctx_fused_state.restype = ctypes.c_int
+    lib.wva_ctx_fused_state.argtypes = [
+        ctypes.c_void_p,
+        ctypes.POINTER(ctypes.c_int),  # out: info[6]
+        ctypes.POINTER(ctypes.c_int),  # out: done[] words that are not 0
+    ]
     # scenario planning (engine/fastpath.py FastSweep.plan)
     lib.wva_ctx_plan.restype = ctypes.c_int
     lib.wva_ctx_plan.argtypes = [
