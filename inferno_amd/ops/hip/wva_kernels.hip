@@ -495,23 +495,68 @@ __device__ __forceinline__ Mg1Out mg1_eval(double lam, double mu, int K, double 
   return o;
 }
 
+// The cell's own scalars, loaded once at the top of the cell function. The
+// SLO targets and the arrival rate are not here: they belong to the mode's
+// view of the cell (WvaView below).
+struct WvaCell {
+  int cell;  // index into the per-cell arrays
+  int in_tok, out_tok, N;
+  float alpha, beta, gamma, delta;
+  float t_tps;
+  int min_rep;
+  float acc_cost, cur_cost;
+  int cur_rep;
+  bool cur_same, cur_empty, has_cur;
+};
+
+// The evaluator's model of the cell: what every evaluation after the geometry
+// build reads. Identical on every thread of the cell except tid.
+struct WvaModel {
+  ChainGeom g;
+  double logsN;
+  int Kstates;  // maxQueue (10N) + N  (ref allocation.go:87)
+  int mode;     // analyzer mode: 0 state-dependent chain, 1 closed-form M/G/1/K
+  double cv2d;
+  double mu;  // M/G/1 service rate s(N)
+  double lam_min, lam_max;  // rate range of the bisections (req/msec)
+  double *scratch;  // the cell's LDS header: [0..31] reductions, [32] S_total,
+                    // [33..36] the bisections' result slots
+  int tid;          // the thread's index within the cell's NT threads
+};
+
+// one evaluation at rate lam (req/msec) by the cell's analyzer: throughput
+// (req/msec), wait (msec), effective concurrency, utilization
+struct WvaEval {
+  double tput, wait, eff, rho;
+};
 template <int NT, int PART>
-__device__ double eval_metric(int kind, double lam, const ChainGeom &g, double logsN, int N, int K,
-                              float gamma, float delta, float alpha, float beta, int in_tok,
-                              int out_tok, double *scratch, int mode, double cv2, double mu) {
-  double wait, eff;
-  if (mode == 1) {
-    Mg1Out o = mg1_eval(lam, mu, K, cv2, N);
-    wait = o.wait;
-    eff = o.eff;
+__device__ __forceinline__ WvaEval wva_evaluate(double lam, const WvaCell &c, const WvaModel &m) {
+  WvaEval e;
+  if (m.mode == 1) {
+    Mg1Out o = mg1_eval(lam, m.mu, m.Kstates, m.cv2d, c.N);
+    e.tput = o.throughput;
+    e.wait = o.wait;
+    e.eff = o.eff;
+    e.rho = o.rho;
   } else {
-    ChainOut c = chain_eval<NT, PART>(lam, g, logsN, N, K, scratch);
-    wait = c.wait;
-    eff = effective_concurrency(c.serv, gamma, alpha, delta, beta, in_tok, out_tok, N);
+    ChainOut o = chain_eval<NT, PART>(lam, m.g, m.logsN, c.N, m.Kstates, m.scratch);
+    e.tput = o.throughput;
+    e.wait = o.wait;
+    e.eff = effective_concurrency(o.serv, c.gamma, c.alpha, c.delta, c.beta, c.in_tok, c.out_tok,
+                                  c.N);
+    e.rho = fmin(fmax(o.in_servers / (double)c.N, 0.0), 1.0);
   }
+  return e;
+}
+
+// kind 0: TTFT, kind 1: ITL at rate lam (msec)
+template <int NT, int PART>
+__device__ __forceinline__ double eval_metric(int kind, double lam, const WvaCell &c,
+                                              const WvaModel &m) {
+  const WvaEval e = wva_evaluate<NT, PART>(lam, c, m);
   if (kind == 0)
-    return wait + (double)prefill_time_f(gamma, delta, in_tok, (float)eff);
-  return (double)decode_time_f(alpha, beta, (float)eff);
+    return e.wait + (double)prefill_time_f(c.gamma, c.delta, c.in_tok, (float)e.eff);
+  return (double)decode_time_f(c.alpha, c.beta, (float)e.eff);
 }
 
 __device__ __forceinline__ bool within_tol(double x, double value) {
@@ -529,24 +574,21 @@ __device__ __forceinline__ bool within_tol(double x, double value) {
 // the partial reductions stay uniform; a block-wide vote ends the loop when
 // both halves are done. This halves the sequential depth of the sizing
 // phase vs running the two searches back to back.
-template <int NT, bool SHARED = false>
-__device__ void dual_bisect(double lam_min, double lam_max, float t_ttft, float t_itl,
-                            const ChainGeom &g, double logsN, int N, int K, float gamma,
-                            float delta, float alpha, float beta, int in_tok, int out_tok,
-                            double *scratch, double *res_slot, double lam_star[2],
-                            int ind_out[2], int mode, double cv2, double mu) {
-  // tid: the thread's index within the cell's NT threads. SHARED: the cell is
-  // one wave of a wider block (fused tick, narrow blocks) and its threads are
-  // threadIdx.x & 63; otherwise the cell owns its block.
-  static_assert(!SHARED || NT == WVA_WAVE, "only a one-wave cell shares a block");
+template <int NT>
+__device__ __forceinline__ void dual_bisect(float t_ttft, float t_itl, const WvaCell &c,
+                                            const WvaModel &m, double lam_star[2],
+                                            int ind_out[2]) {
   constexpr int W = NT / 2;
-  const int tid = SHARED ? (int)(threadIdx.x & (WVA_WAVE - 1)) : (int)threadIdx.x;
+  // the cell-relative index: threadIdx.x & 63 when the cell is one wave of a
+  // wider block (fused tick, narrow blocks), threadIdx.x when it owns its block
+  const int tid = m.tid;
+  double *const res_slot = m.scratch + 33;  // 4 doubles
   const int h = tid / W;  // 0 = TTFT, 1 = ITL
   const double target = (h == 0) ? (double)t_ttft : (double)t_itl;
   const bool active = target > 0.0;
 
-  double x_min = lam_min, x_max = lam_max;
-  double x_star = lam_max;
+  double x_min = m.lam_min, x_max = m.lam_max;
+  double x_star = m.lam_max;
   double y_lo = 0.0;
   bool increasing = true;
   int ind = 0;
@@ -563,9 +605,7 @@ __device__ void dual_bisect(double lam_min, double lam_max, float t_ttft, float 
       x_eval = 0.5 * (x_min + x_max);
     else
       x_eval = x_max;  // done: dummy evaluation to keep barriers uniform
-    const double y =
-        eval_metric<NT, 2>(h, x_eval, g, logsN, N, K, gamma, delta, alpha, beta, in_tok,
-                           out_tok, scratch, mode, cv2, mu);
+    const double y = eval_metric<NT, 2>(h, x_eval, c, m);
     if (phase == 0) {
       y_lo = y;
       if (within_tol(y_lo, target)) {
@@ -619,7 +659,7 @@ __device__ void dual_bisect(double lam_min, double lam_max, float t_ttft, float 
     }
   }
 
-  // publish both halves' results (res_slot: 4 doubles in LDS)
+  // publish both halves' results
   if ((tid % W) == 0) {
     res_slot[2 * h] = x_star;
     res_slot[2 * h + 1] = (double)ind;
@@ -696,13 +736,9 @@ __device__ __forceinline__ void memo_store(WvaMemoRec *rec, const WvaMemoKey &k,
 // output slot o: the empty allocation when the server may scale to zero, else
 // min_replicas at the profile's max batch. Called by thread 0 only.
 template <typename SlotT>
-__device__ __forceinline__ void wva_write_zero(const WvaCellsOut &out, SlotT o, int min_rep,
-                                               const int *perf_max_batch, int cell,
-                                               float acc_cost, float alpha, float beta,
-                                               float gamma, float delta, bool has_cur,
-                                               bool cur_same, bool cur_empty, int cur_rep,
-                                               float cur_cost) {
-  if (min_rep == 0) {
+__device__ __forceinline__ void wva_write_zero(const WvaCellsOut &out, SlotT o, const WvaCell &c,
+                                               const int *perf_max_batch) {
+  if (c.min_rep == 0) {
     out.feasible[o] = 1;
     out.zero_empty[o] = 1;
     out.num_replicas[o] = 0;
@@ -713,17 +749,17 @@ __device__ __forceinline__ void wva_write_zero(const WvaCellsOut &out, SlotT o, 
     out.rho[o] = 0.0f;
     out.max_rate[o] = 0.0f;
     float value = 0.0f;
-    if (has_cur) {
-      if (cur_empty)
-        value = (cur_rep == 0) ? 0.0f : (0.0f - cur_cost);
+    if (c.has_cur) {
+      if (c.cur_empty)
+        value = (c.cur_rep == 0) ? 0.0f : (0.0f - c.cur_cost);
       else
-        value = WVA_ACCEL_PENALTY * cur_cost + (0.0f - cur_cost);
+        value = WVA_ACCEL_PENALTY * c.cur_cost + (0.0f - c.cur_cost);
     }
     out.value[o] = value;
   } else {
-    int max_batch = perf_max_batch[cell];
-    float cost = acc_cost * (float)min_rep;
-    float decode1 = alpha + beta;
+    int max_batch = perf_max_batch[c.cell];
+    float cost = c.acc_cost * (float)c.min_rep;
+    float decode1 = c.alpha + c.beta;
     // product rounded before the add in EVERY instantiation: the compiler
     // otherwise fuses it in some (planning) and not in others (it packs this
     // add with decode1's in the single-scenario kernels), and a scenario
@@ -731,13 +767,13 @@ __device__ __forceinline__ void wva_write_zero(const WvaCellsOut &out, SlotT o, 
     float max_decode;
     {
 #pragma clang fp contract(off)
-      max_decode = alpha + beta * (float)max_batch;
+      max_decode = c.alpha + c.beta * (float)max_batch;
     }
-    float prefill1 = gamma + delta;
+    float prefill1 = c.gamma + c.delta;
     float max_serv = prefill1 + max_decode;
     out.feasible[o] = 1;
     out.zero_empty[o] = 0;
-    out.num_replicas[o] = min_rep;
+    out.num_replicas[o] = c.min_rep;
     out.batch[o] = max_batch;
     out.cost[o] = cost;
     out.itl[o] = decode1;
@@ -745,11 +781,11 @@ __device__ __forceinline__ void wva_write_zero(const WvaCellsOut &out, SlotT o, 
     out.rho[o] = 0.0f;
     out.max_rate[o] = (max_serv > 0.0f) ? (float)max_batch / max_serv : 0.0f;
     float value = cost;
-    if (has_cur) {
-      if (cur_same)
-        value = (cur_rep == min_rep) ? 0.0f : (cost - cur_cost);
+    if (c.has_cur) {
+      if (c.cur_same)
+        value = (c.cur_rep == c.min_rep) ? 0.0f : (cost - c.cur_cost);
       else
-        value = WVA_ACCEL_PENALTY * (cur_cost + cost) + (cost - cur_cost);
+        value = WVA_ACCEL_PENALTY * (c.cur_cost + cost) + (cost - c.cur_cost);
     }
     out.value[o] = value;
   }
@@ -760,58 +796,44 @@ __device__ __forceinline__ void wva_write_zero(const WvaCellsOut &out, SlotT o, 
 // rate_star is the sized per-replica rate (req/sec). Every thread of the block
 // calls this with the same arguments.
 template <int NT, typename SlotT>
-__device__ __forceinline__ void wva_eval_scenario(
-    const WvaCellsOut &out, SlotT o, float arr, int tid, float t_tps, int K, double rate_star,
-    int min_rep, float acc_cost, int analyzer_mode, double mu, int Kstates, double cv2d, int N,
-    const ChainGeom &geom, double logsN, double *scratch, float gamma, float delta, float alpha,
-    float beta, int in_tok, int out_tok, bool has_cur, bool cur_same, bool cur_empty,
-    int cur_rep, float cur_cost) {
+__device__ __forceinline__ void wva_eval_scenario(const WvaCellsOut &out, SlotT o, float arr,
+                                                  double rate_star, const WvaCell &c,
+                                                  const WvaModel &m) {
   double total_rate;  // req/sec (ref allocation.go:134-139)
-  if (t_tps == 0.0f)
+  if (c.t_tps == 0.0f)
     total_rate = (double)arr / 60.0;
   else
-    total_rate = (double)t_tps / (double)K;
+    total_rate = (double)c.t_tps / (double)c.out_tok;
   double reps_d = ceil(total_rate / rate_star);
   if (!(reps_d > 0.0)) reps_d = 0.0;
   if (reps_d > 2147483000.0) reps_d = 2147483000.0;
   int num_replicas = (int)reps_d;
-  if (num_replicas < min_rep) num_replicas = min_rep;
+  if (num_replicas < c.min_rep) num_replicas = c.min_rep;
 
-  const float cost = acc_cost * (float)num_replicas;
+  const float cost = c.acc_cost * (float)num_replicas;
 
   // ---- per-replica analyze (ref allocation.go:148-157) ----
   const double rate = total_rate / (double)num_replicas;
-  double wait2, eff, rho;
-  if (analyzer_mode == 1) {
-    Mg1Out o2 = mg1_eval(rate / 1000.0, mu, Kstates, cv2d, N);
-    wait2 = o2.wait;
-    eff = o2.eff;
-    rho = o2.rho;
-  } else {
-    ChainOut c2 = chain_eval<NT, 1>(rate / 1000.0, geom, logsN, N, Kstates, scratch);
-    wait2 = c2.wait;
-    eff = effective_concurrency(c2.serv, gamma, alpha, delta, beta, in_tok, out_tok, N);
-    rho = fmin(fmax(c2.in_servers / (double)N, 0.0), 1.0);
-  }
-  const float prefill_t = prefill_time_f(gamma, delta, in_tok, (float)eff);
-  const float token_t = decode_time_f(alpha, beta, (float)eff);
+  const WvaEval e = wva_evaluate<NT, 1>(rate / 1000.0, c, m);
+  const float prefill_t = prefill_time_f(c.gamma, c.delta, c.in_tok, (float)e.eff);
+  const float token_t = decode_time_f(c.alpha, c.beta, (float)e.eff);
 
-  if (tid == 0) {
+  if (m.tid == 0) {
     out.feasible[o] = 1;
     out.zero_empty[o] = 0;
     out.num_replicas[o] = num_replicas;
-    out.batch[o] = N;
+    out.batch[o] = c.N;
     out.cost[o] = cost;
     out.itl[o] = token_t;
-    out.ttft[o] = (float)wait2 + prefill_t;
-    out.rho[o] = (float)rho;
+    out.ttft[o] = (float)e.wait + prefill_t;
+    out.rho[o] = (float)e.rho;
     out.max_rate[o] = (float)(rate_star / 1000.0);
     float value = cost;
-    if (has_cur) {
-      if (cur_same && !cur_empty)
-        value = (cur_rep == num_replicas) ? 0.0f : (cost - cur_cost);
+    if (c.has_cur) {
+      if (c.cur_same && !c.cur_empty)
+        value = (c.cur_rep == num_replicas) ? 0.0f : (cost - c.cur_cost);
       else
-        value = WVA_ACCEL_PENALTY * (cur_cost + cost) + (cost - cur_cost);
+        value = WVA_ACCEL_PENALTY * (c.cur_cost + cost) + (cost - c.cur_cost);
     }
     out.value[o] = value;
   }
@@ -850,20 +872,13 @@ using WvaPlanParam = typename std::conditional<
 // false when a target cannot be met; else tput is the throughput at the sized
 // rate (req/msec). Every thread of the block calls this with the same
 // arguments and gets the same result.
-template <int NT, bool SHARED = false>
-__device__ __forceinline__ bool wva_size_cell(float t_ttft, float t_itl, float t_tps,
-                                              double lam_min, double lam_max,
-                                              const ChainGeom &geom, double logsN, int N,
-                                              int Kstates, float gamma, float delta, float alpha,
-                                              float beta, int in_tok, int out_tok,
-                                              double *scratch, double *res_slot,
-                                              int analyzer_mode, double cv2d, double mu,
-                                              double &tput) {
+template <int NT>
+__device__ __forceinline__ bool wva_size_cell(float t_ttft, float t_itl, const WvaCell &c,
+                                              const WvaModel &m, double &tput) {
+  const double lam_max = m.lam_max;
   double lam_star[2];
   int inds[2];
-  dual_bisect<NT, SHARED>(lam_min, lam_max, t_ttft, t_itl, geom, logsN, N, Kstates, gamma, delta, alpha,
-                  beta, in_tok, out_tok, scratch, res_slot, lam_star, inds, analyzer_mode, cv2d,
-                  mu);
+  dual_bisect<NT>(t_ttft, t_itl, c, m, lam_star, inds);
   bool feasible = true;
   double lam_ttft = lam_max;
   if (t_ttft > 0.0f) {
@@ -876,230 +891,143 @@ __device__ __forceinline__ bool wva_size_cell(float t_ttft, float t_itl, float t
     if (inds[1] < 0) feasible = false;
   }
   if (!feasible) return false;
-  double lam_tps = (t_tps > 0.0f) ? lam_max * (1.0 - WVA_STABILITY_FRACTION) : lam_max;
+  double lam_tps = (c.t_tps > 0.0f) ? lam_max * (1.0 - WVA_STABILITY_FRACTION) : lam_max;
   double lam = fmin(fmin(lam_ttft, lam_itl), lam_tps);
-  if (analyzer_mode == 1) {
-    tput = mg1_eval(lam, mu, Kstates, cv2d, N).throughput;
-  } else {
-    tput = chain_eval<NT, 1>(lam, geom, logsN, N, Kstates, scratch).throughput;
-  }
+  tput = wva_evaluate<NT, 1>(lam, c, m).tput;
   return true;
 }
 
-// ---------------------------------------------------------------------------
-// K1: allocate-sweep — one block per cell; cell_ids selects this launch's
-// N-bucket (nullptr = identity).
-// dynamic LDS: S[0..maxN] prefix, then scratch[2*NT/64] for reductions.
-// ---------------------------------------------------------------------------
-// GMEM=false: chain geometry in LDS (hot path, N <= WVA_MAX_N).
-// GMEM=true: geometry in a per-block global-memory slab (g_inv/g_anchor,
-// strided by the bucket's max_n) — same algorithm, same arithmetic order,
-// bit-identical results; used for the rare huge-N cells so the sweep stays
-// uncapped like the reference. The slab layout mirrors the LDS layout
-// (chunk-transposed reciprocals), which is also the coalesced global layout.
+// A mode's view of one cell: n_tgt() target sets times n_load() arrival rates,
+// the targets of set t, the arrival rate of load s (req/min), the output slot
+// of slice (t, s), and memo_tgt(), the target set that owns the cell's memo
+// record (-1: none). own_ttft / own_itl are the cell's own targets, which the
+// memo key holds. Everything here is uniform over the cell's threads.
 //
-// PLAN=true is the scenario-planning variant: the cell is sized ONCE (or takes its memo hit) and then every one of n_scen arrival
-// rates (scen_arrival[s * n_cells + cell]) is evaluated against that sizing;
-// outputs are [n_scen][n_cells], scenario-major. Nothing the sizing phase
-// reads depends on the arrival rate (see the memo key), so slice s is bit for
-// bit what a single-scenario launch with that arrival rate writes. Both
-// variants compile from this one body; every difference is an
-// `if constexpr (PLAN)`.
+// A count that is 1 at compile time is returned as the type WvaOne, and
+// wva_each(n, f), which is f(0) .. f(n - 1), is then the plain call f(0). A
+// `for` over a constant 1 would compute the same, but its back edge survives
+// until the loop passes, long after inlining. In the single-scenario kernels
+// the zero-traffic exit then rejoins the main path, six of the cell's uniform
+// loads and the memo record's land behind its stores as vector loads, and
+// scratch grows from 60-68 to 100-128 B/lane (docs/design/kernels.md, "Cell
+// function refactor").
+using WvaOne = std::integral_constant<int, 1>;
+template <typename F>
+__device__ __forceinline__ void wva_each(int n, F &&f) {
+  for (int i = 0; i < n; ++i) f(i);
+}
+template <typename F>
+__device__ __forceinline__ void wva_each(WvaOne, F &&f) {
+  f(0);
+}
+template <int MODE>
+struct WvaView;
+template <>
+struct WvaView<WVA_MODE_SWEEP> {
+  const int cell;
+  const float own_ttft, own_itl, own_arrival;
+  __device__ WvaView(const WvaCellsIn &in, const WvaNoPlan &, int cell)
+      : cell(cell),
+        own_ttft(in.t_ttft[cell]),
+        own_itl(in.t_itl[cell]),
+        own_arrival(in.arrival_rate[cell]) {}
+  __device__ static constexpr WvaOne n_tgt() { return {}; }
+  __device__ static constexpr WvaOne n_load() { return {}; }
+  __device__ float ttft(int) const { return own_ttft; }
+  __device__ float itl(int) const { return own_itl; }
+  __device__ float arrival(int) const { return own_arrival; }
+  __device__ int slot(int, int) const { return cell; }
+  __device__ int memo_tgt() const { return 0; }
+};
+template <>
+struct WvaView<WVA_MODE_PLAN> {
+  const WvaPlanArgs &p;
+  const int cell;
+  const float own_ttft, own_itl;
+  __device__ WvaView(const WvaCellsIn &in, const WvaPlanArgs &p, int cell)
+      : p(p), cell(cell), own_ttft(in.t_ttft[cell]), own_itl(in.t_itl[cell]) {}
+  __device__ static constexpr WvaOne n_tgt() { return {}; }
+  __device__ int n_load() const { return p.n_scen; }
+  __device__ float ttft(int) const { return own_ttft; }
+  __device__ float itl(int) const { return own_itl; }
+  // output slot s * n_cells + cell (up to 256 scenarios of the fleet)
+  __device__ size_t slot(int, int s) const {
+    return (size_t)s * (size_t)p.n_cells + (size_t)cell;
+  }
+  __device__ float arrival(int s) const { return p.scen_arrival[slot(0, s)]; }
+  __device__ int memo_tgt() const { return 0; }
+};
+template <>
+struct WvaView<WVA_MODE_SLO> {
+  const WvaSloArgs &p;
+  const int cell;
+  const float own_ttft, own_itl;
+  __device__ WvaView(const WvaCellsIn &in, const WvaSloArgs &p, int cell)
+      : p(p), cell(cell), own_ttft(in.t_ttft[cell]), own_itl(in.t_itl[cell]) {}
+  __device__ int n_tgt() const { return p.n_tgt; }
+  __device__ int n_load() const { return p.n_load; }
+  __device__ size_t row(int i) const { return (size_t)i * (size_t)p.n_cells + (size_t)cell; }
+  __device__ float ttft(int t) const { return p.scen_ttft[row(t)]; }
+  __device__ float itl(int t) const { return p.scen_itl[row(t)]; }
+  __device__ float arrival(int s) const { return p.scen_arrival[row(s)]; }
+  __device__ size_t slot(int t, int s) const {
+    return ((size_t)t * (size_t)p.n_load + (size_t)s) * (size_t)p.n_cells + (size_t)cell;
+  }
+  // the first target set whose two targets are bit-equal to the cell's own.
+  // Only that one may use the sizing memo, whose record is keyed on the cell's
+  // own targets.
+  __device__ int memo_tgt() const {
+    int base = -1;
+    for (int t = p.n_tgt - 1; t >= 0; --t)
+      if (__float_as_uint(ttft(t)) == __float_as_uint(own_ttft) &&
+          __float_as_uint(itl(t)) == __float_as_uint(own_itl))
+        base = t;
+    return base;
+  }
+};
+
+// (thread 0 only) the "no allocation on this accelerator" verdict of target
+// set t: its n_load slices. Per slice the zero-traffic decision still comes
+// first, exactly as a single-scenario launch orders it.
+template <typename View>
+__device__ __forceinline__ void wva_write_infeasible(const WvaCellsOut &out, const View &v, int t,
+                                                     const WvaCell &c,
+                                                     const int *perf_max_batch) {
+  wva_each(v.n_load(), [&](int s) {
+    const auto o = v.slot(t, s);
+    if (v.arrival(s) == 0.0f) {
+      wva_write_zero(out, o, c, perf_max_batch);
+    } else {
+      out.feasible[o] = 0;
+      out.zero_empty[o] = 0;
+    }
+  });
+}
+
+// The cell's region: a 40-double header in LDS (WvaModel::scratch), then the
+// chain geometry, in LDS (GMEM=false: hot path, N <= WVA_XL_MAX_N) or in slab
+// `slab` of global memory (GMEM=true: g_inv / g_anchor, strided by the
+// bucket's max_n) — same algorithm, same arithmetic order, bit-identical
+// results; used for the rare huge-N cells so the sweep stays uncapped like the
+// reference. The slab layout mirrors the LDS layout (chunk-transposed
+// reciprocals), which is also the coalesced global layout.
 //
-// MODE = WVA_MODE_SLO is the SLO-planning variant: the geometry, which reads
-// no target, is built once; the cell is then sized under each of n_tgt target
-// sets (scen_ttft / scen_itl[t * n_cells + cell]; the TPS target stays the
-// cell's own) and every sizing is evaluated at each of n_load arrival rates
-// into slot (t * n_load + s) * n_cells + cell. Slice (t, s) is bit for bit what
-// a single-scenario launch with those targets and that arrival rate writes.
-// Its differences are `if constexpr (SLO)`.
-//
-// wva_cell_body is the computation of ONE cell by NT threads, separate from
-// the block that runs it: `cell` is the cell, `tid` the thread's index within
-// the cell's NT threads, `smem` the base of the cell's LDS region and `slab`
-// the index of its global-memory slab (GMEM only). The bucket kernels
-// (WVA_SWEEP_BODY below) run one cell per block with tid = threadIdx.x, the
-// base of dynamic LDS and slab = blockIdx.x; the fused tick kernel (wva_tick_t)
-// also runs four one-wave cells side by side in one 256-thread block (SHARED:
-// the few places below the cell function that read threadIdx.x then mask it). It
-// returns at five exits (zero-traffic, memo-infeasible replay, degenerate
-// rate, SLO-infeasible, sized), every one uniform over the cell's threads.
-//
-// Outputs are stored by the cell's thread 0 ONLY, at every exit: each
-// WVA_WRITE_ZERO / WVA_WRITE_INFEASIBLE below sits under `tid == 0`,
-// wva_eval_scenario stores under `tid == 0`, and memo_miss_store does too.
-// The fused tick's hand-off (release by that one lane) depends on it.
-template <int NT, bool GMEM, int MODE, bool SHARED = false>
-__device__ __forceinline__ void wva_cell_body(const WvaCellsIn &in, const WvaCellsOut &out,
-                                              const int cell, const int tid, double *smem,
-                                              const unsigned slab, int max_n, int analyzer_mode,
-                                              float cv2, float *g_inv, double *g_anchor,
-                                              WvaMemoRec *memo, unsigned *memo_cnt,
-                                              const WvaPlanParam<MODE> &plan) {
-  constexpr bool PLAN = MODE == WVA_MODE_PLAN;
-  constexpr bool SLO = MODE == WVA_MODE_SLO;
-  // memo: per-cell sizing records (nullptr = memo off: every cell is sized
-  // from scratch and nothing is recorded); memo_cnt: [0] hits, [1] misses
-  // LDS layout: [0..31] reduction scratch, [32] S_total slot, [40..] chain
-  // geometry (inv_s_t then S_anchor); 40-double header keeps alignment.
+// wva_build_geom fills the geometry: fp32 service rates s(n), the transposed
+// 1/s table and the log-prefix at every anchor (chunk loop, scan of the chunk
+// totals, anchor fix-up), closed by a wait (one wave) or a barrier, so that
+// every thread may read all of it on return. M/G/1 mode builds nothing: its
+// evaluations are closed-form. Returns whether one of THIS lane's rates is
+// degenerate (not positive and finite).
+__device__ __forceinline__ int wva_num_decode(const WvaCell &c) {
+  return (c.in_tok == 0 && c.out_tok == 1) ? 1 : c.out_tok - 1;
+}
+template <int NT, bool GMEM>
+__device__ __forceinline__ bool wva_build_geom(const WvaCell &c, int tid, int analyzer_mode,
+                                               double *smem, unsigned slab, int max_n,
+                                               float *g_inv, double *g_anchor, ChainGeom &geom) {
   double *scratch = smem;
-  double *S = smem + 40;  // geometry base (see setup below)
-
-  const int in_tok = in.in_tok[cell];
-  const int out_tok = in.out_tok[cell];
-  const int N = in.batch_n[cell];
-  const int min_rep = in.min_replicas[cell];
-  const int flags = in.flags[cell];
-  const float alpha = in.alpha[cell];
-  const float beta = in.beta[cell];
-  const float gamma = in.gamma[cell];
-  const float delta = in.delta[cell];
-  const float arrival = in.arrival_rate[cell];
-  const float t_itl = in.t_itl[cell];
-  const float t_ttft = in.t_ttft[cell];
-  const float t_tps = in.t_tps[cell];
-  const float acc_cost = in.acc_cost[cell];
-  const float cur_cost = in.cur_cost[cell];
-  const int cur_rep = in.cur_replicas[cell];
-  const bool cur_same = flags & 1;
-  const bool cur_empty = flags & 2;
-  const bool has_cur = flags & 4;
-
-  // ---- zero-traffic path (ref allocation.go:73-75, 259-288) ----
-  // (thread 0 only) the zero-traffic result into output slot o
-#define WVA_WRITE_ZERO(o)                                                                   \
-  wva_write_zero(out, (o), min_rep, in.perf_max_batch, cell, acc_cost, alpha, beta, gamma,  \
-                 delta, has_cur, cur_same, cur_empty, cur_rep, cur_cost)
-  // (thread 0 only) the "no allocation on this accelerator" verdict. Planning:
-  // per scenario the zero-traffic decision still comes first, exactly as a
-  // single-scenario launch orders it.
-#define WVA_WRITE_INFEASIBLE()                                                              \
-  do {                                                                                      \
-    if constexpr (PLAN) {                                                                   \
-      for (int s = 0; s < plan.n_scen; ++s) {                                               \
-        const size_t o = (size_t)s * (size_t)plan.n_cells + (size_t)cell;                   \
-        if (plan.scen_arrival[o] == 0.0f) {                                                 \
-          WVA_WRITE_ZERO(o);                                                                \
-        } else {                                                                            \
-          out.feasible[o] = 0;                                                              \
-          out.zero_empty[o] = 0;                                                            \
-        }                                                                                   \
-      }                                                                                     \
-    } else if constexpr (SLO) {                                                             \
-      for (int t = 0; t < plan.n_tgt; ++t) WVA_SLO_WRITE_INFEASIBLE(t);                     \
-    } else {                                                                                \
-      out.feasible[cell] = 0;                                                               \
-      out.zero_empty[cell] = 0;                                                             \
-    }                                                                                       \
-  } while (0)
-  // (thread 0 only, SLO planning) the same verdict for target set t alone:
-  // its n_load slices
-#define WVA_SLO_WRITE_INFEASIBLE(t)                                                         \
-  do {                                                                                      \
-    for (int s = 0; s < plan.n_load; ++s) {                                                 \
-      const size_t o = ((size_t)(t) * (size_t)plan.n_load + (size_t)s) *                    \
-                           (size_t)plan.n_cells + (size_t)cell;                             \
-      if (plan.scen_arrival[(size_t)s * (size_t)plan.n_cells + (size_t)cell] == 0.0f) {     \
-        WVA_WRITE_ZERO(o);                                                                  \
-      } else {                                                                              \
-        out.feasible[o] = 0;                                                                \
-        out.zero_empty[o] = 0;                                                              \
-      }                                                                                     \
-    }                                                                                       \
-  } while (0)
-  // SLO planning: the first target set whose two targets are bit-equal to the
-  // cell's own, -1 if none. Only that one may use the sizing memo, whose
-  // record is keyed on the cell's own targets. Block-uniform.
-  int slo_base = -1;
-  if constexpr (SLO) {
-    // zero-traffic in EVERY load scenario, hence in every (t, s) slice: the
-    // decision reads no target (block-uniform: depends on the cell only)
-    bool any_load = false;
-    if (out_tok != 0)
-      for (int s = 0; s < plan.n_load; ++s)
-        any_load = any_load ||
-                   (plan.scen_arrival[(size_t)s * (size_t)plan.n_cells + (size_t)cell] != 0.0f);
-    if (!any_load) {
-      if (tid == 0)
-        for (int o = 0; o < plan.n_tgt * plan.n_load; ++o)
-          WVA_WRITE_ZERO((size_t)o * (size_t)plan.n_cells + (size_t)cell);
-      return;
-    }
-    for (int t = plan.n_tgt - 1; t >= 0; --t) {
-      const size_t k = (size_t)t * (size_t)plan.n_cells + (size_t)cell;
-      if (__float_as_uint(plan.scen_ttft[k]) == __float_as_uint(t_ttft) &&
-          __float_as_uint(plan.scen_itl[k]) == __float_as_uint(t_itl))
-        slo_base = t;
-    }
-  } else if constexpr (PLAN) {
-    // zero-traffic in EVERY scenario (block-uniform: depends on the cell only)
-    bool any_load = false;
-    if (out_tok != 0)
-      for (int s = 0; s < plan.n_scen; ++s)
-        any_load = any_load ||
-                   (plan.scen_arrival[(size_t)s * (size_t)plan.n_cells + (size_t)cell] != 0.0f);
-    if (!any_load) {
-      if (tid == 0)
-        for (int s = 0; s < plan.n_scen; ++s)
-          WVA_WRITE_ZERO((size_t)s * (size_t)plan.n_cells + (size_t)cell);
-      return;
-    }
-  } else {
-    if (arrival == 0.0f || out_tok == 0) {
-      if (tid == 0) WVA_WRITE_ZERO(cell);
-      return;
-    }
-  }
-
-  // ---- sizing memo lookup: every thread loads the cell's record (same
-  // address block-wide) and compares the key, so the verdict is uniform and
-  // every barrier below stays uniform. The only writer is this block's
-  // thread 0 at one of the miss exits, which all lie behind a barrier (or,
-  // for the single-wave block, later in the same wave's program order).
-  // SLO planning: the lookup, its counter and the miss store belong to target
-  // set slo_base; without one the memo is neither read nor written.
-  WvaMemoRec *const rec = (memo && (!SLO || slo_base >= 0)) ? memo + cell : nullptr;
-  unsigned memo_status = WVA_MEMO_EMPTY;
-  double memo_tput = 0.0;
-  if (rec) {
-    const WvaMemoRec r = *rec;
-    const WvaMemoKey k = memo_make_key(in_tok, out_tok, N, alpha, beta, gamma, delta, t_ttft,
-                                       t_itl, t_tps, cv2, analyzer_mode, NT);
-    bool same = r.status == WVA_MEMO_FEASIBLE || r.status == WVA_MEMO_INFEASIBLE;
-#pragma unroll
-    for (int q = 0; q < WVA_MEMO_KEY_WORDS; ++q) same = same && (r.key[q] == k.w[q]);
-    if (same) {
-      memo_status = r.status;
-      memo_tput = r.tput;
-    }
-    if (tid == 0) atomicAdd(memo_cnt + (same ? 0 : 1), 1u);
-    if constexpr (!SLO) {
-      if (memo_status == WVA_MEMO_INFEASIBLE) {
-        // replay of the infeasible verdict: no geometry, no evaluations
-        if (tid == 0) WVA_WRITE_INFEASIBLE();
-        return;
-      }
-    }
-    // (SLO planning replays it for target set slo_base in the loop below: the
-    // other target sets still need the geometry)
-  }
-  // miss exits (degenerate, infeasible, sized) record their outcome; the key
-  // is rebuilt here rather than kept live across the sizing phase
-  auto memo_miss_store = [&](double tput, unsigned status) {
-    // (SLO planning reaches the degenerate exit after a hit too: no store then)
-    if (rec && tid == 0 && (!SLO || memo_status == WVA_MEMO_EMPTY))
-      memo_store(rec,
-                 memo_make_key(in_tok, out_tok, N, alpha, beta, gamma, delta, t_ttft, t_itl,
-                               t_tps, cv2, analyzer_mode, NT),
-                 tput, status);
-  };
-
-  const int K = out_tok;
-  int num_decode = out_tok - 1;
-  if (in_tok == 0 && out_tok == 1) num_decode = 1;
-
-  // ---- build chain geometry: transposed 1/s + anchor log-prefix ----
-  // (skipped entirely in M/G/1 mode — its evaluations are closed-form)
+  const int N = c.N;
+  const int num_decode = wva_num_decode(c);
   const int chunk = (N + NT - 1) / NT;
   const int ksub = (chunk + WVA_SUB - 1) / WVA_SUB;
   float *inv_s_t;
@@ -1111,7 +1039,7 @@ __device__ __forceinline__ void wva_cell_body(const WvaCellsIn &in, const WvaCel
     inv_s_t = g_inv + (size_t)slab * ((size_t)chunk_max * NT);
     S_anchor = g_anchor + (size_t)slab * ((size_t)NT * ksub_max);
   } else {
-    // LDS partition (S points at the dynamic smem base; scratch precedes)
+    double *S = smem + 40;                // LDS partition behind the header
     inv_s_t = (float *)S;                 // chunk*NT floats
     S_anchor = S + (chunk * NT + 1) / 2;  // NT*ksub doubles (8B aligned)
   }
@@ -1123,8 +1051,8 @@ __device__ __forceinline__ void wva_cell_body(const WvaCellsIn &in, const WvaCel
   bool bad_rate = false;
   for (int n = n0; n <= n1; ++n) {
     float nf = (float)n;
-    float prefill = (in_tok == 0) ? 0.0f : (gamma + delta * (float)in_tok * nf);
-    float decode = alpha + beta * nf;
+    float prefill = (c.in_tok == 0) ? 0.0f : (c.gamma + c.delta * (float)c.in_tok * nf);
+    float decode = c.alpha + c.beta * nf;
     float s = nf / (prefill + (float)num_decode * decode);  // fp32 like the reference
     bad_rate = bad_rate || !(s > 0.0f) || !isfinite(s);
     local += log((double)s);
@@ -1142,13 +1070,11 @@ __device__ __forceinline__ void wva_cell_body(const WvaCellsIn &in, const WvaCel
   double offset = incl - local;
   if constexpr (NT != WVA_WAVE) {
     // ...then cross-wave carries via scratch
-    constexpr int NW = NT / WVA_WAVE;
     if ((tid & (WVA_WAVE - 1)) == WVA_WAVE - 1) scratch[tid / WVA_WAVE] = incl;
     __syncthreads();
     double carry = 0.0;
     for (int w = 0; w < tid / WVA_WAVE; ++w) carry += scratch[w];
     offset += carry;
-    static_assert(NW >= 1, "block must be at least one wave");
   }
   for (int k = 0; k < ksub && n0 + k * WVA_SUB <= n1; ++k)
     S_anchor[tid * ksub + k] += offset;
@@ -1160,185 +1086,253 @@ __device__ __forceinline__ void wva_cell_body(const WvaCellsIn &in, const WvaCel
   } else {
     __syncthreads();
   }
-  ChainGeom geom;
   geom.inv_s_t = inv_s_t;
   geom.S_anchor = S_anchor;
   geom.S_total = *total_slot;
   geom.chunk = chunk;
   geom.ksub = ksub;
+  return bad_rate;
+}
 
-  // s(1), s(N) in fp32 (rate-range bounds, ref queueanalyzer.go:117-119)
-  float prefill1 = (in_tok == 0) ? 0.0f : (gamma + delta * (float)in_tok);
-  float s1 = 1.0f / (prefill1 + (float)num_decode * (alpha + beta));
-  float prefillN = (in_tok == 0) ? 0.0f : (gamma + delta * (float)in_tok * (float)N);
-  float sN = (float)N / (prefillN + (float)num_decode * (alpha + beta * (float)N));
+// ---------------------------------------------------------------------------
+// K1: allocate-sweep. wva_cell_body is the computation of ONE cell by NT
+// threads, separate from the block that runs it: `cell` is the cell, `tid` the
+// thread's index within the cell's NT threads, `smem` the base of the cell's
+// LDS region and `slab` the index of its global-memory slab (GMEM only). The
+// bucket kernels (wva_sweep_block below) run one cell per block with tid =
+// threadIdx.x, the base of dynamic LDS and slab = blockIdx.x; the fused tick
+// kernel (wva_tick_t) also runs four one-wave cells side by side in one
+// 256-thread block, each with tid = threadIdx.x & 63.
+//
+// MODE picks the view (WvaView<MODE>) and nothing else; the body is one
+// sequence for all three:
+//   WVA_MODE_SWEEP  one slice: the cell's own targets and arrival rate, into
+//                   output slot `cell`;
+//   WVA_MODE_PLAN   the cell's own targets, sized once, evaluated at n_scen
+//                   arrival rates into slots s * n_cells + cell;
+//   WVA_MODE_SLO    n_tgt target sets (the TPS target stays the cell's own),
+//                   each sized and evaluated at n_load arrival rates into slots
+//                   (t * n_load + s) * n_cells + cell. The geometry, which
+//                   reads no target, is built once.
+// Nothing the sizing reads depends on the arrival rate and nothing the
+// geometry reads depends on a target (see the memo key), so slice (t, s) is
+// bit for bit what a single-scenario launch with those targets and that
+// arrival rate writes.
+//
+// The steps: (1) zero-traffic test over the loads, (2) memo lookup, (3)
+// geometry, (4) degenerate-rate guard, (5) per target set: size it or take
+// the memo's word, (6) per load: zero-traffic result, infeasible verdict or
+// evaluation, in that order of precedence as in a single-scenario launch.
+// It returns after (1), (2: memo-infeasible replay, one target set only),
+// (4) or (6), every exit uniform over the cell's threads: each condition
+// depends on the cell, on (cell, t) or on (cell, s) only, or is a reduction
+// result or a value read back from the shared result slots. So every barrier
+// inside dual_bisect and chain_eval is executed by all threads of a multi-wave
+// cell, and a one-wave cell executes none.
+//
+// Outputs and memo records are stored by the cell's thread 0 ONLY, at every
+// exit: wva_write_zero and wva_write_infeasible are called under `tid == 0`,
+// wva_eval_scenario stores under `tid == 0`, and memo_miss_store does too.
+// The fused tick's hand-off (release by that one lane) depends on it.
+//
+// LDS reuse across the sizings and evaluations of one cell. Blocks wider than
+// one wave: every write to the reduction scratch (red_max_p, red_sum2_p,
+// chain_eval's broadcast) sits behind a barrier that follows the previous
+// reads of it, whichever call made them, so the order of calls does not
+// matter. The bisection result slots are written at the end of dual_bisect and
+// read by all threads right after its closing barrier; the next write to them
+// is at the end of the next dual_bisect, whose loop runs at least one step and
+// every step ends in a barrier (__syncthreads_and), in both analyzer modes —
+// so a barrier separates the reads of target set t from the writes of t + 1,
+// also when t ends early on the infeasible verdict. Single-wave cells use no
+// scratch at all (their reductions are shuffles), and their result slots are
+// written and read by one wave in program order: LDS serves a wave's accesses
+// in issue order, and the s_waitcnt in dual_bisect completes the write before
+// the reads. Nothing else in LDS is written after the geometry build.
+// ---------------------------------------------------------------------------
+template <int NT, bool GMEM, int MODE>
+__device__ __forceinline__ void wva_cell_body(const WvaCellsIn &in, const WvaCellsOut &out,
+                                              const int cell, const int tid, double *smem,
+                                              const unsigned slab, int max_n, int analyzer_mode,
+                                              float cv2, float *g_inv, double *g_anchor,
+                                              WvaMemoRec *memo, unsigned *memo_cnt,
+                                              const WvaPlanParam<MODE> &plan) {
+  // memo: per-cell sizing records (nullptr = memo off: every cell is sized
+  // from scratch and nothing is recorded); memo_cnt: [0] hits, [1] misses
+  const int flags = in.flags[cell];
+  WvaCell c;
+  c.cell = cell;
+  c.in_tok = in.in_tok[cell];
+  c.out_tok = in.out_tok[cell];
+  c.N = in.batch_n[cell];
+  c.alpha = in.alpha[cell];
+  c.beta = in.beta[cell];
+  c.gamma = in.gamma[cell];
+  c.delta = in.delta[cell];
+  c.t_tps = in.t_tps[cell];
+  c.min_rep = in.min_replicas[cell];
+  c.acc_cost = in.acc_cost[cell];
+  c.cur_cost = in.cur_cost[cell];
+  c.cur_rep = in.cur_replicas[cell];
+  c.cur_same = flags & 1;
+  c.cur_empty = flags & 2;
+  c.has_cur = flags & 4;
+  const WvaView<MODE> v(in, plan, cell);
+
+  // ---- (1) zero-traffic in EVERY load, hence in every slice: the decision
+  // reads no target (ref allocation.go:73-75, 259-288)
+  // (two forms of one test. With a single load the test is written as the
+  // per-slice tests below are: the general form costs the single-scenario
+  // kernels their scalar loads, see wva_each. With several loads, written on
+  // `== 0.0f` like that, wva_plan_t reloads about twice as many spilled SGPRs
+  // and measured 4-6 % slower; docs/design/kernels.md, "Cell function refactor")
+  bool no_load;
+  if constexpr (std::is_same<decltype(v.n_load()), WvaOne>::value) {
+    no_load = v.arrival(0) == 0.0f || c.out_tok == 0;
+  } else {
+    bool any_load = false;
+    if (c.out_tok != 0)
+      wva_each(v.n_load(), [&](int s) { any_load = any_load || (v.arrival(s) != 0.0f); });
+    no_load = !any_load;
+  }
+  if (no_load) {
+    if (tid == 0)
+      wva_each(v.n_tgt(), [&](int t) {
+        wva_each(v.n_load(),
+                 [&](int s) { wva_write_zero(out, v.slot(t, s), c, in.perf_max_batch); });
+      });
+    return;
+  }
+
+  // ---- (2) sizing memo lookup: every thread loads the cell's record (same
+  // address cell-wide) and compares the key, so the verdict is uniform and
+  // every barrier below stays uniform. The only writer is this cell's
+  // thread 0 at one of the miss exits, which all lie behind a barrier (or,
+  // for the single-wave cell, later in the same wave's program order).
+  // The lookup, its counter and the miss store belong to target set memo_t;
+  // without one (SLO planning only) the memo is neither read nor written.
+  const int memo_t = v.memo_tgt();
+  WvaMemoRec *const rec = (memo && memo_t >= 0) ? memo + cell : nullptr;
+  const auto memo_key = [&]() {
+    return memo_make_key(c.in_tok, c.out_tok, c.N, c.alpha, c.beta, c.gamma, c.delta, v.own_ttft,
+                         v.own_itl, c.t_tps, cv2, analyzer_mode, NT);
+  };
+  unsigned memo_status = WVA_MEMO_EMPTY;
+  double memo_tput = 0.0;
+  if (rec) {
+    const WvaMemoRec r = *rec;
+    const WvaMemoKey k = memo_key();
+    bool same = r.status == WVA_MEMO_FEASIBLE || r.status == WVA_MEMO_INFEASIBLE;
+#pragma unroll
+    for (int q = 0; q < WVA_MEMO_KEY_WORDS; ++q) same = same && (r.key[q] == k.w[q]);
+    if (same) {
+      memo_status = r.status;
+      memo_tput = r.tput;
+    }
+    if (tid == 0) atomicAdd(memo_cnt + (same ? 0 : 1), 1u);
+    if constexpr (MODE != WVA_MODE_SLO) {
+      if (memo_status == WVA_MEMO_INFEASIBLE) {
+        // replay of the infeasible verdict: no geometry, no evaluations
+        if (tid == 0) wva_write_infeasible(out, v, 0, c, in.perf_max_batch);
+        return;
+      }
+    }
+    // (SLO planning replays it for target set memo_t in the loop below: the
+    // other target sets still need the geometry)
+  }
+  // miss exits (degenerate, infeasible, sized) record their outcome; the key
+  // is rebuilt here rather than kept live across the sizing phase.
+  // (SLO planning reaches the degenerate exit after a hit too: no store then.
+  // The other modes reach a miss exit only on a miss, since the key covers all
+  // the geometry reads, so the test is always true there. It is not limited to
+  // SLO mode as it once was: that form drops wva_plan_t<256> and <512> to 168
+  // VGPRs and occupancy 3, and planning measured 3-6 % slower; this form
+  // leaves the override-only wva_plan_t<128> at 164 VGPRs against 162.
+  // docs/design/kernels.md, "Cell function refactor")
+  auto memo_miss_store = [&](double tput, unsigned status) {
+    if (rec && tid == 0 && memo_status == WVA_MEMO_EMPTY)
+      memo_store(rec, memo_key(), tput, status);
+  };
+
+  // ---- (3) chain geometry
+  WvaModel m;
+  const bool bad_rate =
+      wva_build_geom<NT, GMEM>(c, tid, analyzer_mode, smem, slab, max_n, g_inv, g_anchor, m.g);
+
+  // ---- (4) s(1), s(N) in fp32 (rate-range bounds, ref queueanalyzer.go:117-119)
+  const int num_decode = wva_num_decode(c);
+  float prefill1 = (c.in_tok == 0) ? 0.0f : (c.gamma + c.delta * (float)c.in_tok);
+  float s1 = 1.0f / (prefill1 + (float)num_decode * (c.alpha + c.beta));
+  float prefillN = (c.in_tok == 0) ? 0.0f : (c.gamma + c.delta * (float)c.in_tok * (float)c.N);
+  float sN = (float)c.N / (prefillN + (float)num_decode * (c.alpha + c.beta * (float)c.N));
   // degenerate perf parameters (zero/negative service times) -> infeasible
   // cell rather than propagating inf/nan through the chain (matches the CPU
   // golden's AnalyzerError guard)
-  const double any_bad = red_max_p<NT, 1>(bad_rate ? 1.0 : 0.0, scratch);
+  const double any_bad = red_max_p<NT, 1>(bad_rate ? 1.0 : 0.0, smem);
   if (any_bad > 0.0 || !(s1 > 0.0f) || !(sN > 0.0f) || !isfinite(s1) || !isfinite(sN)) {
-    if (tid == 0) WVA_WRITE_INFEASIBLE();
+    if (tid == 0)
+      wva_each(v.n_tgt(),
+               [&](int t) { wva_write_infeasible(out, v, t, c, in.perf_max_batch); });
     memo_miss_store(0.0, WVA_MEMO_INFEASIBLE);
     return;
   }
-  const double logsN = log((double)sN);
+  m.logsN = log((double)sN);
+  m.Kstates = 11 * c.N;
+  m.mode = analyzer_mode;
+  m.cv2d = (double)cv2;
+  m.mu = (double)sN;
+  m.lam_min = (double)s1 * WVA_EPSILON;
+  m.lam_max = (double)sN * (1.0 - WVA_EPSILON);
+  m.scratch = smem;
+  m.tid = tid;
 
-  const double lam_min = (double)s1 * WVA_EPSILON;
-  const double lam_max = (double)sN * (1.0 - WVA_EPSILON);
-  const double mu = (double)sN;  // M/G/1 service rate (analyzer mode 1)
-  const double cv2d = (double)cv2;
-  const int Kstates = 11 * N;  // maxQueue (10N) + N  (ref allocation.go:87)
-
-  if constexpr (SLO) {
-    // ---- per target set: size (or, for slo_base, take the memo's word), then
-    // per load scenario the single-scenario tail. Per slice the order is the
-    // single-scenario kernel's: zero-traffic decision, infeasible verdict,
-    // evaluation.
-    //
-    // Block-uniform: the targets depend on (cell, t) only and the verdict comes
-    // from the shared result slots, so every barrier inside dual_bisect and
-    // chain_eval stays uniform.
-    //
-    // Consecutive sizings reuse the reduction scratch and the four bisection
-    // result slots behind total_slot. Blocks wider than one wave: every write
-    // to the scratch (red_max_p, red_sum2_p, chain_eval's broadcast) sits
-    // behind a barrier that follows the previous reads of it, whichever call
-    // made them, so the order of calls does not matter. The result slots are
-    // written at the end of dual_bisect and read by all threads right after
-    // its closing barrier; the next write to them is at the end of the next
-    // dual_bisect, whose loop runs at least one step and every step ends in a
-    // barrier (__syncthreads_and), in both analyzer modes — so a barrier
-    // separates the reads of iteration t from the writes of iteration t + 1,
-    // also when iteration t ends early on the infeasible verdict. Single-wave
-    // blocks use no scratch at all (their reductions are shuffles), and their
-    // result slots are written and read by one wave in program order: LDS
-    // serves a wave's accesses in issue order, and the s_waitcnt in
-    // dual_bisect completes the write before the reads. Nothing else in LDS is
-    // written after the geometry build.
-    for (int t = 0; t < plan.n_tgt; ++t) {
-      const size_t kt = (size_t)t * (size_t)plan.n_cells + (size_t)cell;
-      const bool base = (t == slo_base);
-      double tput_at_lam = 0.0;
-      bool feasible;
-      if (base && memo_status == WVA_MEMO_FEASIBLE) {
-        tput_at_lam = memo_tput;  // memo hit
-        feasible = true;
-      } else if (base && memo_status == WVA_MEMO_INFEASIBLE) {
-        feasible = false;  // replay of the infeasible verdict, for this t only
-      } else {
-        feasible = wva_size_cell<NT, SHARED>(plan.scen_ttft[kt], plan.scen_itl[kt], t_tps, lam_min,
-                                     lam_max, geom, logsN, N, Kstates, gamma, delta, alpha, beta,
-                                     in_tok, out_tok, scratch, total_slot + 1, analyzer_mode,
-                                     cv2d, mu, tput_at_lam);
-        // only slo_base records its outcome (rec is null without one)
-        if (base) memo_miss_store(tput_at_lam, feasible ? WVA_MEMO_FEASIBLE : WVA_MEMO_INFEASIBLE);
-      }
-      if (!feasible) {
-        if (tid == 0) WVA_SLO_WRITE_INFEASIBLE(t);
-        continue;
-      }
+  wva_each(v.n_tgt(), [&](int t) {
+    // ---- (5) size target set t, or take the memo's word for memo_t
+    const bool owns_memo = (t == memo_t);
+    double tput_at_lam = 0.0;
+    bool feasible;
+    if (owns_memo && memo_status == WVA_MEMO_FEASIBLE) {
+      tput_at_lam = memo_tput;  // memo hit: the sizing would reproduce this value
+      feasible = true;
+    } else if (owns_memo && memo_status == WVA_MEMO_INFEASIBLE) {
+      feasible = false;  // replay of the infeasible verdict, for this t only
+    } else {
+      feasible = wva_size_cell<NT>(v.ttft(t), v.itl(t), c, m, tput_at_lam);
+      if (owns_memo)
+        memo_miss_store(tput_at_lam, feasible ? WVA_MEMO_FEASIBLE : WVA_MEMO_INFEASIBLE);
+    }
+    // ---- (6) per load: zero-traffic result, infeasible verdict or evaluation
+    if (!feasible) {
+      if (tid == 0) wva_write_infeasible(out, v, t, c, in.perf_max_batch);
+    } else {
       const double rate_star = tput_at_lam * 1000.0;  // req/sec
-      for (int s = 0; s < plan.n_load; ++s) {
-        const float arr = plan.scen_arrival[(size_t)s * (size_t)plan.n_cells + (size_t)cell];
-        const size_t o = ((size_t)t * (size_t)plan.n_load + (size_t)s) * (size_t)plan.n_cells +
-                         (size_t)cell;
+      wva_each(v.n_load(), [&](int s) {
+        const float arr = v.arrival(s);
         if (arr == 0.0f) {
-          if (tid == 0) WVA_WRITE_ZERO(o);
-          continue;
+          if (tid == 0) wva_write_zero(out, v.slot(t, s), c, in.perf_max_batch);
+        } else {
+          wva_eval_scenario<NT>(out, v.slot(t, s), arr, rate_star, c, m);
         }
-        wva_eval_scenario<NT>(out, o, arr, tid, t_tps, K, rate_star, min_rep, acc_cost,
-                              analyzer_mode, mu, Kstates, cv2d, N, geom, logsN, scratch, gamma,
-                              delta, alpha, beta, in_tok, out_tok, has_cur, cur_same, cur_empty,
-                              cur_rep, cur_cost);
-      }
+      });
     }
-  } else {
-    double tput_at_lam;
-    if (memo_status == WVA_MEMO_FEASIBLE) {
-      // memo hit (block-uniform): the sizing below would reproduce this value
-      tput_at_lam = memo_tput;
-    } else {
-      // ---- SLO sizing: concurrent TTFT+ITL bisections (queueanalyzer.go:185-255)
-      // (kept inline: the same steps as wva_size_cell, but routing these two
-      // modes through it moves their register allocation)
-      double lam_star[2];
-      int inds[2];
-      dual_bisect<NT, SHARED>(lam_min, lam_max, t_ttft, t_itl, geom, logsN, N, Kstates, gamma, delta,
-                      alpha, beta, in_tok, out_tok, scratch, total_slot + 1, lam_star, inds,
-                      analyzer_mode, cv2d, mu);
-      bool feasible = true;
-      double lam_ttft = lam_max;
-      if (t_ttft > 0.0f) {
-        lam_ttft = lam_star[0];
-        if (inds[0] < 0) feasible = false;
-      }
-      double lam_itl = lam_max;
-      if (feasible && t_itl > 0.0f) {
-        lam_itl = lam_star[1];
-        if (inds[1] < 0) feasible = false;
-      }
-      if (!feasible) {
-        if (tid == 0) WVA_WRITE_INFEASIBLE();
-        memo_miss_store(0.0, WVA_MEMO_INFEASIBLE);
-        return;
-      }
-      double lam_tps = (t_tps > 0.0f) ? lam_max * (1.0 - WVA_STABILITY_FRACTION) : lam_max;
-      double lam = fmin(fmin(lam_ttft, lam_itl), lam_tps);
-
-      // ---- analyze at sized rate -> rate* (ref allocation.go:126-131) ----
-      if (analyzer_mode == 1) {
-        tput_at_lam = mg1_eval(lam, mu, Kstates, cv2d, N).throughput;
-      } else {
-        tput_at_lam = chain_eval<NT, 1>(lam, geom, logsN, N, Kstates, scratch).throughput;
-      }
-      memo_miss_store(tput_at_lam, WVA_MEMO_FEASIBLE);
-    }
-    const double rate_star = tput_at_lam * 1000.0;  // req/sec
-
-    // ---- per scenario: replicas, cost and the per-replica analysis (the
-    // single-scenario instantiations evaluate the cell's own arrival rate).
-    // Block-uniform: the arrival rate depends only on (cell, scenario), so every
-    // barrier inside chain_eval stays uniform; consecutive chain_eval calls are
-    // ordered as the sized-rate and per-replica evaluations always were (single-
-    // wave blocks only READ LDS there, wider blocks enter each reduction through
-    // a barrier).
-    if constexpr (PLAN) {
-      for (int s = 0; s < plan.n_scen; ++s) {
-        // output slot s * n_cells + cell (up to 256 scenarios of the fleet)
-        const size_t o = (size_t)s * (size_t)plan.n_cells + (size_t)cell;
-        const float arr = plan.scen_arrival[o];
-        if (arr == 0.0f) {
-          if (tid == 0) WVA_WRITE_ZERO(o);
-          continue;
-        }
-        wva_eval_scenario<NT>(out, o, arr, tid, t_tps, K, rate_star, min_rep, acc_cost,
-                              analyzer_mode, mu, Kstates, cv2d, N, geom, logsN, scratch, gamma,
-                              delta, alpha, beta, in_tok, out_tok, has_cur, cur_same, cur_empty,
-                              cur_rep, cur_cost);
-      }
-    } else {
-      wva_eval_scenario<NT>(out, cell, arrival, tid, t_tps, K, rate_star, min_rep, acc_cost,
-                            analyzer_mode, mu, Kstates, cv2d, N, geom, logsN, scratch, gamma, delta,
-                            alpha, beta, in_tok, out_tok, has_cur, cur_same, cur_empty, cur_rep,
-                            cur_cost);
-    }
-  }
-#undef WVA_SLO_WRITE_INFEASIBLE
-#undef WVA_WRITE_INFEASIBLE
-#undef WVA_WRITE_ZERO
+  });
 }
 
 // One cell per block: block blockIdx.x of a bucket launch computes cell
 // cell_ids[blockIdx.x] with all its threads in the whole of dynamic LDS.
-// (a macro, not one more function: the bucket kernels call the cell function
-// at the inlining depth the sweep body always had)
-#define WVA_SWEEP_BODY(MODE, plan)                                                          \
-  extern __shared__ double smem[];                                                          \
-  if ((int)blockIdx.x >= n_blocks) return;                                                  \
-  const int cell = cell_ids ? cell_ids[blockIdx.x] : (int)blockIdx.x;                       \
-  wva_cell_body<NT, GMEM, MODE>(in, out, cell, (int)threadIdx.x, smem, blockIdx.x,          \
-                                max_n, analyzer_mode, cv2, g_inv, g_anchor, memo, memo_cnt, \
-                                plan)
+template <int NT, bool GMEM, int MODE>
+__device__ __forceinline__ void wva_sweep_block(const WvaCellsIn &in, const WvaCellsOut &out,
+                                                int n_blocks, const int *cell_ids, int max_n,
+                                                int analyzer_mode, float cv2, float *g_inv,
+                                                double *g_anchor, WvaMemoRec *memo,
+                                                unsigned *memo_cnt,
+                                                const WvaPlanParam<MODE> &plan) {
+  extern __shared__ double smem[];
+  if ((int)blockIdx.x >= n_blocks) return;
+  const int cell = cell_ids ? cell_ids[blockIdx.x] : (int)blockIdx.x;
+  wva_cell_body<NT, GMEM, MODE>(in, out, cell, (int)threadIdx.x, smem, blockIdx.x, max_n,
+                                analyzer_mode, cv2, g_inv, g_anchor, memo, memo_cnt, plan);
+}
 
 template <int NT, bool GMEM>
 __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut out, int n_blocks,
@@ -1346,7 +1340,8 @@ __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut 
                                                   int analyzer_mode, float cv2,
                                                   float *g_inv, double *g_anchor,
                                                   WvaMemoRec *memo, unsigned *memo_cnt) {
-  WVA_SWEEP_BODY(WVA_MODE_SWEEP, WvaNoPlan{});
+  wva_sweep_block<NT, GMEM, WVA_MODE_SWEEP>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2,
+                                            g_inv, g_anchor, memo, memo_cnt, WvaNoPlan{});
 }
 
 // scenario-planning sweep: out arrays are [n_scen][n_cells]; in.arrival_rate
@@ -1359,12 +1354,12 @@ __global__ void __launch_bounds__(NT, 4) wva_sweep_t(WvaCellsIn in, WvaCellsOut 
 #define WVA_PLAN_MIN_WAVES 2
 #endif
 template <int NT, bool GMEM>
-__global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES) wva_plan_t(WvaCellsIn in, WvaCellsOut out, int n_blocks,
-                                                 const int *cell_ids, int max_n,
-                                                 int analyzer_mode, float cv2, float *g_inv,
-                                                 double *g_anchor, WvaMemoRec *memo,
-                                                 unsigned *memo_cnt, WvaPlanArgs plan) {
-  WVA_SWEEP_BODY(WVA_MODE_PLAN, plan);
+__global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
+    wva_plan_t(WvaCellsIn in, WvaCellsOut out, int n_blocks, const int *cell_ids, int max_n,
+               int analyzer_mode, float cv2, float *g_inv, double *g_anchor, WvaMemoRec *memo,
+               unsigned *memo_cnt, WvaPlanArgs plan) {
+  wva_sweep_block<NT, GMEM, WVA_MODE_PLAN>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2,
+                                           g_inv, g_anchor, memo, memo_cnt, plan);
 }
 
 // SLO-planning sweep: out arrays are [n_tgt][n_load][n_cells]; in.arrival_rate
@@ -1376,9 +1371,9 @@ __global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
     wva_slo_plan_t(WvaCellsIn in, WvaCellsOut out, int n_blocks, const int *cell_ids, int max_n,
                    int analyzer_mode, float cv2, float *g_inv, double *g_anchor, WvaMemoRec *memo,
                    unsigned *memo_cnt, WvaSloArgs plan) {
-  WVA_SWEEP_BODY(WVA_MODE_SLO, plan);
+  wva_sweep_block<NT, GMEM, WVA_MODE_SLO>(in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2,
+                                          g_inv, g_anchor, memo, memo_cnt, plan);
 }
-#undef WVA_SWEEP_BODY
 
 // ---------------------------------------------------------------------------
 // K2: segmented argmin per server over the sweep output.
@@ -1468,34 +1463,22 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
   // the spill path keeps only the header in LDS
   size_t lds = gmem ? (size_t)40 * sizeof(double) : wva_cell_lds_bytes(max_n, nt);
   if (lds > 160 * 1024) return -5;  // exceeds the CU's LDS
-  // the >64 KiB opt-in is per function, so the planning instantiation of a
-  // width opts in separately from the reconcile one
-#define WVA_LAUNCH(NTV, GM)                                                                 \
-  do {                                                                                      \
-    if (slo != nullptr) {                                                                   \
-      int src =                                                                             \
-          wva_optin_lds(reinterpret_cast<const void *>(&wva_slo_plan_t<NTV, GM>), lds);     \
-      if (src != 0) return src;                                                             \
-      hipLaunchKernelGGL((wva_slo_plan_t<NTV, GM>), dim3(n_blocks), dim3(NTV), lds, s, in,  \
-                         out, n_blocks, cell_ids, max_n, analyzer_mode, cv2, g_inv,         \
-                         g_anchor, memo, memo_cnt, *slo);                                   \
-      break;                                                                                \
-    }                                                                                       \
-    if (plan != nullptr) {                                                                  \
-      int prc =                                                                             \
-          wva_optin_lds(reinterpret_cast<const void *>(&wva_plan_t<NTV, GM>), lds);  \
-      if (prc != 0) return prc;                                                             \
-      hipLaunchKernelGGL((wva_plan_t<NTV, GM>), dim3(n_blocks), dim3(NTV), lds, s,   \
-                         in, out, n_blocks, cell_ids, max_n, analyzer_mode, cv2, g_inv,     \
-                         g_anchor, memo, memo_cnt, *plan);                                  \
-      break;                                                                                \
-    }                                                                                       \
-    int orc = wva_optin_lds(reinterpret_cast<const void *>(&wva_sweep_t<NTV, GM>), lds);    \
-    if (orc != 0) return orc;                                                               \
-    hipLaunchKernelGGL((wva_sweep_t<NTV, GM>), dim3(n_blocks), dim3(NTV), lds, s, in, out,  \
-                       n_blocks, cell_ids, max_n, analyzer_mode, cv2, g_inv, g_anchor,      \
-                       memo, memo_cnt);                                                     \
-  } while (0)
+  // opt in to the dynamic LDS, then launch; `tail` is the mode's argument
+  // struct, if any. The >64 KiB opt-in is per function, so the planning
+  // instantiations of a width opt in separately from the reconcile one.
+  // (block size nt: WVA_LAUNCH below picks the instantiation with NT == nt)
+  auto launch = [&](auto kernel, auto... tail) -> int {
+    int rc = wva_optin_lds(reinterpret_cast<const void *>(kernel), lds);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(nt), lds, s, in, out, n_blocks, cell_ids,
+                       max_n, analyzer_mode, cv2, g_inv, g_anchor, memo, memo_cnt, tail...);
+    return 0;
+  };
+  int rc = -3;
+#define WVA_LAUNCH(NTV, GM)                                        \
+  rc = slo != nullptr    ? launch(&wva_slo_plan_t<NTV, GM>, *slo)  \
+       : plan != nullptr ? launch(&wva_plan_t<NTV, GM>, *plan)     \
+                         : launch(&wva_sweep_t<NTV, GM>)
   if (gmem) {
     switch (nt) {
       case 256: WVA_LAUNCH(256, true); break;
@@ -1513,6 +1496,7 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
     }
   }
 #undef WVA_LAUNCH
+  if (rc != 0) return rc;
   return (int)hipGetLastError();
 }
 
@@ -1719,9 +1703,9 @@ __global__ void __launch_bounds__(WVA_TICK_NT, 4)
     const int w = (int)threadIdx.x / WVA_WAVE;  // wave-uniform
     cell = w == 0 ? task.x : w == 1 ? task.y : w == 2 ? task.z : task.w;
     if (cell < 0) return;
-    wva_cell_body<WVA_WAVE, false, WVA_MODE_SWEEP, true>(in, out, cell, lane, smem + w * narrow_stride,
-                                                   0, 0, analyzer_mode, cv2, nullptr, nullptr,
-                                                   memo, memo_cnt, WvaNoPlan{});
+    wva_cell_body<WVA_WAVE, false, WVA_MODE_SWEEP>(in, out, cell, lane, smem + w * narrow_stride, 0,
+                                                   0, analyzer_mode, cv2, nullptr, nullptr, memo,
+                                                   memo_cnt, WvaNoPlan{});
   }
   // ---- arrival: one wave per cell from here on, lane 0 stored the outputs
   const int srv = cell_server[cell];
