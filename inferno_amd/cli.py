@@ -6,6 +6,7 @@ pkg/config wire format) and print the allocation solution.
   python -m inferno_amd.cli plan system.json --scales 0.5,1,1.5,2 [--backend ...] [--json]
       [--limited] [--capacity TYPE=N,...] [--saturation-policy P] [--delayed-best-effort]
   python -m inferno_amd.cli plan system.json --slo-scales 0.5,1,2 [--scales ...] [--json]
+  python -m inferno_amd.cli plan system.json --rollout --scales 0.5,1,2,1,0.5 [--json]
 """
 from __future__ import annotations
 
@@ -99,6 +100,11 @@ def cmd_plan(args) -> int:
     from .engine import FastSweep, SweepEngine
 
     limited = args.limited or args.capacity is not None
+    if args.rollout:
+        if limited or args.slo_scales is not None:
+            raise SystemExit("plan: --rollout replays consecutive unlimited-mode reconciles; it "
+                             "does not combine with --slo-scales, --limited or --capacity")
+        return _cmd_plan_rollout(args)
     if args.slo_scales is not None:
         if limited:
             raise SystemExit("plan: --slo-scales is an unlimited-mode plan; it does not "
@@ -224,6 +230,48 @@ def _cmd_plan_slo(args) -> int:
     return 0
 
 
+def _cmd_plan_rollout(args) -> int:
+    """Forecast rollout: the scales are consecutive ticks, each reconciled
+    against the allocation the tick before it left behind."""
+    from .engine import FastSweep, SweepEngine
+
+    if args.scales is None:
+        raise SystemExit("plan: --rollout needs --scales (one factor per step)")
+    scales = _parse_scales(args.scales)
+    system, _ = _load_system(args.spec)
+    backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
+    fs = FastSweep(system, backend=backend)
+    try:
+        res = fs.rollout(scales=scales)
+    except ValueError as e:
+        print(f"plan: {e}", file=sys.stderr)
+        return 2
+    rows = [{
+        "step": s,
+        "scale": scale,
+        "totalCost": round(float(res.cost_total[s]), 2),
+        "replicas": {
+            name: int(res.replicas_by_acc[s, j]) for j, name in enumerate(fs.acc_names)
+        },
+        "infeasibleServers": int(res.infeasible_servers[s]),
+        "acceleratorChanges": int(res.acc_changes[s]),
+    } for s, scale in enumerate(scales)]
+    if args.json:
+        print(json.dumps({"backend": backend, "servers": len(fs.server_names), "rollout": rows,
+                          "acceleratorChangesTotal": int(res.acc_changes.sum())}, indent=2))
+        return 0
+    names = fs.acc_names
+    print(f"{'step':>5} {'scale':>8} {'cost':>12} " + " ".join(f"{n:>10}" for n in names)
+          + f" {'infeasible':>10} {'acc-changes':>11}")
+    for r in rows:
+        print(f"{r['step']:>5} {r['scale']:>8g} {r['totalCost']:>12.2f} "
+              + " ".join(f"{r['replicas'][n]:>10}" for n in names)
+              + f" {r['infeasibleServers']:>10} {r['acceleratorChanges']:>11}")
+    print(f"({len(fs.server_names)} servers, backend {backend}; consecutive steps, acc-changes "
+          f"are relative to the step before; {int(res.acc_changes.sum())} in all)")
+    return 0
+
+
 def cmd_analyze(args) -> int:
     from .api import v1alpha1 as api
     from .controller.modelanalyzer import ModelAnalyzer
@@ -270,6 +318,9 @@ def main() -> None:
     pp.add_argument("--saturation-policy", default=None,
                     choices=["None", "PriorityExhaustive", "PriorityRoundRobin", "RoundRobin"])
     pp.add_argument("--delayed-best-effort", action="store_true")
+    pp.add_argument("--rollout", action="store_true",
+                    help="forecast rollout: --scales are consecutive steps, each reconciled "
+                         "against the allocation the step before it left behind")
     pp.set_defaults(fn=cmd_plan)
     pa = sub.add_parser("analyze", help="per-variant candidate allocations")
     pa.add_argument("spec")

@@ -93,6 +93,33 @@ class SloPlanResult:
     cells: Optional[dict] = None  # reconcile_cells() layout, arrays [T, S, n_cells]
 
 
+@dataclass
+class RolloutResult:
+    """Forecast rollout: what the controller does over S consecutive ticks of
+    an arrival-rate forecast, every tick judged against the allocation the
+    tick before it left behind (FastSweep.rollout)."""
+
+    winners: WinnerRecord  # every array [S, n_servers]; row s = tick s
+    replicas_by_acc: np.ndarray  # int64 [S, n_acc], columns = FastSweep.acc_names
+    cost_total: np.ndarray  # float64 [S]: fp64 sum of the winners' fp32 cost
+    infeasible_servers: np.ndarray  # int64 [S]: servers with acc_idx == -1
+    arrival: np.ndarray  # float32 [S, n_servers]: the forecast evaluated
+    # int64 [S]: servers whose current accelerator after the tick differs from
+    # the one before it (empty is an accelerator of its own; from no current
+    # allocation to any counts)
+    acc_changes: np.ndarray
+    # (cur_acc i32, cur_rep i32, cur_cost f32) after the last tick, in the form
+    # of FastSweep.cur_override
+    final_cur: tuple
+    cells: Optional[dict] = None  # reconcile_cells() layout, arrays [S, n_cells]
+
+
+# Longest forecast one rollout() takes, and the steps one device pass of it
+# holds (at most PLAN_MAX_S): longer forecasts run as consecutive passes, each
+# starting from the allocation the one before it ended with.
+ROLLOUT_MAX_STEPS = 4096
+ROLLOUT_CHUNK = PLAN_MAX_S
+
 _WINNER_FIELDS = ("acc_idx", "num_replicas", "batch", "cost", "value", "itl", "ttft", "rho",
                   "max_rate")
 
@@ -379,7 +406,8 @@ class FastSweep:
     # batch_n differs from the one it was chosen for; outputs preallocated;
     # winner records selected and gathered ON-DEVICE in one launch and
     # downloaded in a single D2H copy.
-    def _tick(self, plan_arrival: Optional[np.ndarray] = None, launch: bool = True) -> None:
+    def _tick(self, plan_arrival: Optional[np.ndarray] = None, launch: bool = True,
+              cur=None) -> None:
         """One native tick (wva_ctx_tick): the library expands the six
         per-server arrays into the pinned dynamic block — what
         _refresh_dynamic() computes, byte for byte — and, with ``launch``,
@@ -389,8 +417,9 @@ class FastSweep:
         before and the already staged tick resumed (wva_reconcile).
 
         ``plan_arrival`` as in _refresh_dynamic; the planning passes stage
-        with ``launch=False`` and run their own pipeline afterwards. The
-        device state is set up on the first call."""
+        with ``launch=False`` and run their own pipeline afterwards; ``cur``
+        (a rollout pass) replaces _base_cur()'s triple. The device state is
+        set up on the first call."""
         g = getattr(self, "_gpu", None)
         if g is None:
             g = self._gpu = NativeCtx(len(self.server_names), self._stat, self.cell_server,
@@ -400,7 +429,7 @@ class FastSweep:
         if plan_arrival is not None:
             arrival = plan_arrival.max(axis=0).astype(np.float32)
             zero = arrival
-        cur_acc, cur_rep, cur_cost = self._base_cur()
+        cur_acc, cur_rep, cur_cost = cur if cur is not None else self._base_cur()
         n_srv = len(self.server_names)
         f32, i32 = np.float32, np.int32
         srv = (
@@ -531,10 +560,13 @@ class FastSweep:
         )
         return totals, cost_total, (~has).sum(axis=1).astype(np.int64)
 
-    def _plan_scenarios(self, scales, arrival) -> np.ndarray:
-        """Validate plan()'s input and return the [S, n_servers] fp32 rates."""
+    def _plan_scenarios(self, scales, arrival, limit: int = PLAN_MAX_S,
+                        who: str = "plan()", rows: str = "scenarios") -> np.ndarray:
+        """Validate plan()'s input (at most ``limit`` rows; ``who`` and ``rows``
+        name the caller in the messages) and return the [S, n_servers] fp32
+        rates."""
         if (scales is None) == (arrival is None):
-            raise ValueError("plan() takes exactly one of scales and arrival")
+            raise ValueError(f"{who} takes exactly one of scales and arrival")
         n_srv = len(self.server_names)
         if scales is not None:
             try:
@@ -555,8 +587,8 @@ class FastSweep:
                 )
             vals, what = arr, "arrival"
         n_scen = vals.shape[0]
-        if not 1 <= n_scen <= PLAN_MAX_S:
-            raise ValueError(f"plan() takes 1..{PLAN_MAX_S} scenarios, got {n_scen}")
+        if not 1 <= n_scen <= limit:
+            raise ValueError(f"{who} takes 1..{limit} {rows}, got {n_scen}")
         if not np.isfinite(vals).all() or (vals < 0).any():
             raise ValueError(f"{what} must be finite and non-negative")
         if scales is not None:
@@ -583,6 +615,112 @@ class FastSweep:
     def _plan_cells_gpu(self, n_scen: int) -> dict:
         """Per-cell outputs of the planning pass that just ran."""
         return self._with_cell_meta(self._gpu.plan_cells(n_scen))
+
+    # ------------------------------------------------------------------
+    # Forecast rollout
+    # ------------------------------------------------------------------
+    def rollout(self, scales=None, arrival=None, return_cells: bool = False) -> RolloutResult:
+        """Replay S consecutive reconciles of an arrival-rate forecast.
+
+        Input as for plan(): exactly one of ``scales`` (S step factors on the
+        base arrival rates) and ``arrival`` ([S, n_servers] req/min); 1 <= S
+        <= ROLLOUT_MAX_STEPS. The rows are consecutive ticks, not
+        alternatives. Tick 0 runs against the current allocation (the
+        current-allocation override when set, else the server objects); tick
+        s >= 1 against what tick s - 1 left behind: unchanged where it found
+        no feasible cell (acc_idx -1), empty after a zero-load empty winner
+        (-2), else the winner's accelerator, replicas and cost. Tick s of the
+        result is what reconcile() returns with row s as the load and that
+        allocation as the current one; with ``return_cells`` the per-cell
+        arrays of reconcile_cells() come with it.
+
+        On the GPU the per-cell work is plan()'s pass (each cell sized once,
+        the sizing memo shared: one hit or miss per loaded cell and pass) and
+        the per-server chain over the ticks runs in one kernel; forecasts
+        longer than ROLLOUT_CHUNK ticks run as consecutive passes. A rollout
+        changes nothing a following reconcile(), plan() or plan_slo()
+        returns, and leaves the server objects as they were."""
+        scen = self._plan_scenarios(scales, arrival, ROLLOUT_MAX_STEPS, "rollout()", "steps")
+        start = tuple(np.array(a) for a in self._base_cur())
+        if self.backend == "gpu":
+            winners, totals, cells, final_cur = self._rollout_gpu(scen, start, return_cells)
+        else:
+            winners, final_cur = self._rollout_cpu(scen, start)
+            totals = cells = None
+        totals, cost_total, infeasible = self._plan_totals(winners, totals)
+        return RolloutResult(
+            winners=winners,
+            replicas_by_acc=totals,
+            cost_total=cost_total,
+            infeasible_servers=infeasible,
+            arrival=scen,
+            acc_changes=_acc_changes(start[0], winners.acc_idx),
+            final_cur=final_cur,
+            cells=cells,
+        )
+
+    def _rollout_gpu(self, scen: np.ndarray, cur, return_cells: bool):
+        n_steps, n_srv = scen.shape
+        n_acc = len(self.acc_names)
+        if self.n_cells == 0 or n_acc == 0:
+            return (_empty_winners(n_steps, n_srv), np.zeros((n_steps, n_acc), dtype=np.int64),
+                    None, cur)
+        chunk = max(1, min(int(ROLLOUT_CHUNK), PLAN_MAX_S))
+        pf, pi, tot, cells = [], [], [], []
+        for lo in range(0, n_steps, chunk):
+            rows = scen[lo:lo + chunk]
+            # stage with the allocation the pass starts from; a stale bucket
+            # layout (the pass's own zero-load cells) is resynchronised there
+            self._tick(plan_arrival=rows, launch=False, cur=cur)
+            cell_scen = np.ascontiguousarray(rows[:, self.cell_server], dtype=np.float32)
+            of, oi, totals, cur = self._gpu.rollout(cell_scen, n_acc, cur)
+            pf.append(of)
+            pi.append(oi)
+            tot.append(totals)
+            if return_cells:
+                cells.append(self._gpu.plan_cells(rows.shape[0]))
+        all_cells = None
+        if return_cells:
+            all_cells = self._with_cell_meta(
+                {k: np.concatenate([c[k] for c in cells]) for k in CELL_KEYS})
+        return (_winner_record(np.concatenate(pf), np.concatenate(pi)), np.concatenate(tot),
+                all_cells, cur)
+
+    def _rollout_cpu(self, scen: np.ndarray, cur):
+        """Golden path: one _reconcile_cpu per step with the step's arrival
+        rates and the fed-back current allocation put on the server objects,
+        which are restored afterwards in any case. Step 0 runs against the
+        objects' own current allocations unless the override is set."""
+        from ..core.allocation import Allocation
+
+        saved = [srv.cur_allocation for srv in self._srv_objs]
+
+        def put_cur(which):
+            for i in np.nonzero(which)[0]:
+                acc = int(cur[0][i])
+                self._srv_objs[i].cur_allocation = None if acc == -3 else Allocation(
+                    accelerator=self.acc_names[acc] if acc >= 0 else "",
+                    num_replicas=int(cur[1][i]), cost=float(cur[2][i]),
+                )
+
+        rows = []
+        try:
+            with self._scenario_loads() as set_loads:
+                if self.cur_override is not None:
+                    put_cur(np.ones(len(self._srv_objs), dtype=bool))
+                for row in scen:
+                    set_loads(row)
+                    w = self._reconcile_cpu()
+                    rows.append(w)
+                    cur = feed_back(cur, w)
+                    put_cur(w.acc_idx != -1)  # the others keep what they had
+        finally:
+            for srv, old in zip(self._srv_objs, saved):
+                srv.cur_allocation = old
+        winners = WinnerRecord(**{
+            f: np.stack([getattr(r, f) for r in rows]) for f in _WINNER_FIELDS
+        })
+        return winners, cur
 
     # ------------------------------------------------------------------
     # What-if SLO planning
@@ -1011,6 +1149,37 @@ class FastSweep:
             _set_winner(rec, seg, best,
                         -2 if best.accelerator == "" else self._acc_index[best.accelerator])
         return rec
+
+
+def feed_back(cur, w: WinnerRecord):
+    """Desired -> current between two ticks: the (cur_acc, cur_rep, cur_cost)
+    triple after a tick that started from ``cur`` and returned the winners
+    ``w`` ([n_servers]). A server without a feasible cell (acc_idx -1) keeps
+    what it had; a zero-load empty winner (-2) leaves it empty (-1)."""
+    pa, pr, pc = cur
+    ok = w.acc_idx != -1
+    return (
+        np.where(ok, np.where(w.acc_idx == -2, -1, w.acc_idx), pa).astype(np.int32),
+        np.where(ok, w.num_replicas, pr).astype(np.int32),
+        np.where(ok, w.cost, pc).astype(np.float32),
+    )
+
+
+def _acc_changes(start_acc: np.ndarray, acc_idx: np.ndarray) -> np.ndarray:
+    """Per step of a rollout, the servers whose current accelerator (-3 none,
+    -1 empty, >= 0 index) after the step differs from the one before it;
+    ``acc_idx`` is the winners' [S, n_servers], ``start_acc`` the current
+    accelerator before step 0."""
+    n_steps = acc_idx.shape[0]
+    ok = acc_idx != -1
+    # the step each server's current accelerator was last set at (-1: never)
+    last = np.maximum.accumulate(
+        np.where(ok, np.arange(n_steps)[:, None], -1), axis=0)
+    new = np.where(acc_idx == -2, -1, acc_idx)
+    after = np.where(last >= 0, np.take_along_axis(new, np.maximum(last, 0), axis=0),
+                     start_acc[None, :])
+    before = np.concatenate([start_acc[None, :], after[:-1]])
+    return (after != before).sum(axis=1).astype(np.int64)
 
 
 def _empty_winner(n: int) -> WinnerRecord:

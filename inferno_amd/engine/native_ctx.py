@@ -307,6 +307,36 @@ class NativeCtx:
             _copy_out(out[2], ctypes.c_uint64, (n_scen, n_acc)).astype(np.int64),
         )
 
+    def rollout(self, cell_scen: np.ndarray, n_acc: int, cur):
+        """wva_ctx_rollout on [S, n_cells] fp32 arrivals, the rows being
+        consecutive ticks, starting from the per-server current allocation
+        ``cur`` = (cur_acc i32, cur_rep i32, cur_cost f32), which the tick was
+        staged with: plan()'s three arrays, then the allocation after the last
+        step as a (cur_acc, cur_rep, cur_cost) triple."""
+        n_steps = cell_scen.shape[0]
+        cur = (np.ascontiguousarray(cur[0], dtype=np.int32),
+               np.ascontiguousarray(cur[1], dtype=np.int32),
+               np.ascontiguousarray(cur[2], dtype=np.float32))
+        for a in cur:
+            if a.shape != (self.n_srv,):
+                raise ValueError(
+                    f"per-server override has shape {a.shape}, expected ({self.n_srv},)"
+                )
+        out = [ctypes.c_void_p() for _ in range(4)]
+        rc = self._lib.wva_ctx_rollout(
+            self.ctx, n_steps, n_acc, cell_scen.ctypes.data, cur[0].ctypes.data,
+            cur[1].ctypes.data, cur[2].ctypes.data, *[ctypes.byref(p) for p in out],
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_rollout failed: {rc}")
+        end = _copy_out(out[3], ctypes.c_int32, (3, self.n_srv))
+        return (
+            _copy_out(out[0], ctypes.c_float, (n_steps, 6, self.n_srv)),
+            _copy_out(out[1], ctypes.c_int32, (n_steps, 4, self.n_srv)),
+            _copy_out(out[2], ctypes.c_uint64, (n_steps, n_acc)).astype(np.int64),
+            (end[0], end[1], end[2].view(np.float32)),
+        )
+
     def plan_cells(self, n_scen: int) -> dict:
         """Per-cell outputs [S, n_cells] of the planning pass that just ran."""
         cells = {k: np.empty((n_scen, self.n_cells), dtype=d)

@@ -120,6 +120,12 @@ struct WvaCtx {
   float *slo_itl;    // device [T][n_cells]
   float *slo_pin_ttft;  // pinned mirrors
   float *slo_pin_itl;
+  // forecast rollout (wva_ctx_rollout): the per-server current allocation the
+  // chain starts from and ends with, three rows of n_srv words (cur_acc,
+  // cur_rep, cur_cost). Allocated on first use, freed in destroy.
+  int roll_group = 1;  // lanes per server in wva_rollout (wva_ctx_set_topology)
+  void *roll_dev;      // device [3][n_srv]
+  void *roll_pin;      // its pinned source and mirror
   // capacity-limited planning (wva_ctx_plan_limited): the static greedy
   // inputs (wva_ctx_set_greedy_static) and the per-scenario workspace, both
   // allocated on first use and freed in destroy
@@ -382,6 +388,19 @@ extern "C" int wva_ctx_set_topology(void *ctx, const int *cell_server, const int
   c->topo_override = c->topo + 4 * n;
   c->bucket_batch_n = c->topo + 5 * n;
   c->bucket_batch_valid = 0;
+  // wva_rollout's lanes per server: the smallest power of two that holds the
+  // longest segment, at most a wave (longer segments are strided)
+  {
+    std::vector<int> per_srv((size_t)c->n_srv, 0);
+    int longest = 1;
+    for (size_t k = 0; k < n; ++k) {
+      const int len = ++per_srv[cell_server[k]];
+      if (len > longest) longest = len;
+    }
+    int g = 1;
+    while (g < longest && g < WVA_WAVE) g <<= 1;
+    c->roll_group = g;
+  }
   // the fused tick kernel finds a cell's server on the device. Synchronous
   // upload, off the hot path; the next set_buckets rebuilds the task table.
   c->fused_path = 0;
@@ -903,6 +922,15 @@ static int wva_slo_reserve(WvaCtx *c, int n_tgt) {
   return 0;
 }
 
+// the rollout's current-allocation rows; on failure nothing is held and
+// reconciles and plans keep working
+static int wva_roll_reserve(WvaCtx *c) {
+  if (c->roll_dev != nullptr) return 0;
+  const size_t bytes = (size_t)3 * (size_t)c->n_srv * sizeof(int);
+  if (!wva_arena_alloc(c, bytes, bytes, false, &c->roll_dev, &c->roll_pin)) return -37;
+  return 0;
+}
+
 static void wva_lim_release(WvaCtx *c) {
   wva_arena_free(c->lim_dev, c->lim_pin);
   c->lim_cap = c->lim_types_cap = 0;
@@ -988,6 +1016,9 @@ extern "C" int wva_ctx_set_greedy_static(void *ctx, const int *cell_type, const 
 // itl, ttft, rho, max_rate), pi [n_scen][4][n_srv] i32 (acc code, replicas,
 // batch, winner cell), totals [n_scen][n_acc] u64.
 //
+// With roll (wva_ctx_rollout) the scenarios are consecutive ticks and step 3
+// is wva_rollout; everything else is the same pass.
+//
 // lim == nullptr is the unlimited plan (wva_ctx_plan). With lim, step 3 is
 // wva_plan_greedy instead of wva_plan_reduce and the capacity rows go up and
 // come back (wva_ctx_plan_limited); everything else is the same pass.
@@ -1007,10 +1038,16 @@ struct WvaSloTargets {
   const float *scen_ttft;  // host [n_tgt][n_cells]
   const float *scen_itl;   // host [n_tgt][n_cells]
 };
+struct WvaRollArgs {
+  const int *cur_acc;     // host [n_srv]: -3 none, -1 empty, >= 0 accelerator index
+  const int *cur_rep;     // host [n_srv]
+  const float *cur_cost;  // host [n_srv]
+};
 
 static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arrival,
                         const WvaLimArgs *lim, const void **out_pf, const void **out_pi,
-                        const void **out_totals, const WvaSloTargets *slo = nullptr) {
+                        const void **out_totals, const WvaSloTargets *slo = nullptr,
+                        const WvaRollArgs *roll = nullptr) {
   if (c == nullptr || scen_arrival == nullptr) return -31;
   if (n_scen < 1 || n_scen > WVA_PLAN_MAX_S || n_acc < 1) return -32;
   if (slo != nullptr && (slo->n_tgt < 1 || n_scen % slo->n_tgt != 0)) return -32;
@@ -1024,6 +1061,10 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   }
   if (lim != nullptr) {
     rc = wva_lim_reserve(c, n_scen, lim->n_types);
+    if (rc != 0) return rc;
+  }
+  if (roll != nullptr) {
+    rc = wva_roll_reserve(c);
     if (rc != 0) return rc;
   }
   // arrival-rate scenarios: all n_scen slices, or one SLO plan's load axis
@@ -1056,6 +1097,17 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   err = hipMemsetAsync(c->plan_tot, 0, (size_t)n_scen * n_acc * sizeof(unsigned long long),
                        c->s0);
   if (err != hipSuccess) return (int)err;
+  const size_t b_cur = (size_t)3 * (size_t)c->n_srv * sizeof(int);
+  if (roll != nullptr) {
+    int *pc = (int *)c->roll_pin;
+    for (int i = 0; i < c->n_srv; ++i) {
+      pc[i] = roll->cur_acc[i];
+      pc[c->n_srv + i] = roll->cur_rep[i];
+      memcpy(pc + 2 * (size_t)c->n_srv + i, roll->cur_cost + i, sizeof(float));
+    }
+    err = hipMemcpyAsync(c->roll_dev, c->roll_pin, b_cur, hipMemcpyHostToDevice, c->s0);
+    if (err != hipSuccess) return (int)err;
+  }
   const size_t n_capacity = lim != nullptr ? (size_t)n_scen * (size_t)lim->n_types : 0;
   if (lim != nullptr) {
     for (size_t i = 0; i < n_capacity; ++i) c->lim_pin_capacity[i] = lim->capacity[i];
@@ -1075,8 +1127,17 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   }
   if (rc != 0) return rc;
 
-  // 3. winners, records and totals for all (server, scenario) pairs
-  if (lim == nullptr) {
+  // 3. winners, records and totals for all (server, scenario) pairs; a
+  // rollout's scenarios are consecutive steps, chained per server
+  if (roll != nullptr) {
+    const int per_block = WVA_WAVE / c->roll_group;
+    hipLaunchKernelGGL(wva_rollout, dim3((c->n_srv + per_block - 1) / per_block), dim3(WVA_WAVE),
+                       0, c->s0, c->plan_out.value, c->plan_out.feasible, c->plan_out.zero_empty,
+                       c->cell_acc, c->plan_out.num_replicas, c->plan_out.batch, c->plan_out.cost,
+                       c->plan_out.itl, c->plan_out.ttft, c->plan_out.rho, c->plan_out.max_rate,
+                       c->seg_start, c->n_srv, c->n_cells, n_scen, n_acc, c->roll_group,
+                       c->plan_pf, c->plan_pi, c->plan_tot, (int *)c->roll_dev);
+  } else if (lim == nullptr) {
     hipLaunchKernelGGL(wva_plan_reduce, dim3(c->n_srv, n_scen), dim3(WVA_WAVE), 0, c->s0,
                        c->plan_out.value, c->plan_out.feasible, c->plan_out.zero_empty,
                        c->cell_acc, c->plan_out.num_replicas, c->plan_out.batch, c->plan_out.cost,
@@ -1111,6 +1172,10 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   }
 
   // 4. downloads
+  if (roll != nullptr) {
+    err = hipMemcpyAsync(c->roll_pin, c->roll_dev, b_cur, hipMemcpyDeviceToHost, c->s0);
+    if (err != hipSuccess) return (int)err;
+  }
   err = hipMemcpyAsync(c->plan_pin_pf, c->plan_pf, (size_t)n_scen * 6 * c->n_srv * sizeof(float),
                        hipMemcpyDeviceToHost, c->s0);
   if (err != hipSuccess) return (int)err;
@@ -1181,6 +1246,31 @@ extern "C" int wva_ctx_plan_slo(void *ctx, int n_tgt, int n_scen, int n_acc,
                       out_totals, &slo);
 }
 
+// One forecast-rollout pass: the n_steps rows of scen_arrival ([n_steps]
+// [n_cells] fp32, req/min) are consecutive ticks. wva_ctx_plan's staging,
+// uploads and buckets, then wva_rollout instead of wva_plan_reduce: step 0 is
+// judged against the per-server current allocation cur_acc / cur_rep / cur_cost
+// (host [n_srv]; the caller staged the tick with the same three arrays), step
+// s >= 1 against what step s - 1 left behind. pf, pi and totals are as for
+// wva_ctx_plan; out_cur names a pinned i32 [3][n_srv] block (cur_acc, cur_rep,
+// the bits of cur_cost) holding the allocation after the last step.
+// wva_ctx_plan_cells works on the result and returns every step's value
+// against that step's own current allocation. -37: the current-allocation
+// rows could not be allocated (the context is intact).
+extern "C" int wva_ctx_rollout(void *ctx, int n_steps, int n_acc, const float *scen_arrival,
+                               const int *cur_acc, const int *cur_rep, const float *cur_cost,
+                               const void **out_pf, const void **out_pi, const void **out_totals,
+                               const void **out_cur) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || cur_acc == nullptr || cur_rep == nullptr || cur_cost == nullptr) return -31;
+  const WvaRollArgs roll = {cur_acc, cur_rep, cur_cost};
+  const int rc = wva_plan_run(c, n_steps, n_acc, scen_arrival, nullptr, out_pf, out_pi,
+                              out_totals, nullptr, &roll);
+  if (rc != 0) return rc;
+  if (out_cur) *out_cur = c->roll_pin;
+  return 0;
+}
+
 // Per-cell outputs of the last successful wva_ctx_plan, copied into ten host
 // arrays of plan_s * n_cells elements each, in WvaCellsOut order (feasible,
 // zero_empty: u8; num_replicas, batch: i32; cost, value, itl, ttft, rho,
@@ -1218,6 +1308,7 @@ extern "C" void wva_ctx_destroy(void *ctx) {
   wva_plan_release(c);
   wva_slo_release(c);
   wva_lim_release(c);
+  wva_arena_free(c->roll_dev, c->roll_pin);
   if (c->lim_static != nullptr) (void)hipFree(c->lim_static);
   free(c->topo);
   delete c;

@@ -1620,6 +1620,142 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_reduce(
 }
 
 // ---------------------------------------------------------------------------
+// K4c wva_rollout: the winner step of a forecast rollout. The n_steps slices of
+// a planning sweep are consecutive ticks: step s is judged against the
+// allocation step s - 1 left behind (winner none: unchanged; zero-load empty:
+// empty; else the winner's accelerator, replicas and cost). That chain is per
+// server and lives in registers: cur_acc (-3 none, -1 empty, >= 0 accelerator
+// index), cur_rep, cur_cost, starting from cur[3][n_srv] and written back there
+// after the last step.
+//
+// `group` lanes (a power of two, 1..64) serve one server, 64 / group servers
+// share a one-wave block; lane `sub` of a group takes cells beg + sub,
+// beg + sub + group, ... of the server's segment. Per step every lane reads its
+// cells' slice outputs (none of them depends on the chain), recomputes `value`
+// against the chain's current allocation and stores it, the group selects the
+// winner by wva_winner_record's rule (minimum value over feasible cells, lowest
+// cell index on ties; same shuffle order), the lane that owns the winner writes
+// the record into pf[n_steps][6][n_srv] / pi[n_steps][4][n_srv] and adds its
+// replicas to totals[n_steps][n_acc] (zero on entry), and all lanes of the
+// group take the winner as the new current allocation. No barrier, no LDS.
+//
+// The value expression is the reconcile kernels' one (wva_sweep_t, wva_tick_t)
+// as their machine code has it: cost is the rounded fp32 product the slice
+// holds, the sum and the difference are rounded, and only the penalty multiply
+// is fused into the final add. It is computed for every step, step 0 included,
+// so that no step depends on how the planning kernel happened to contract the
+// same source expression.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float wva_rollout_value(bool zero_empty, int reps, float cost,
+                                                   int acc, int cur_acc, int cur_rep,
+                                                   float cur_cost) {
+#pragma clang fp contract(off)
+  if (cur_acc == -3) return zero_empty ? 0.0f : cost;
+  if (zero_empty) {
+    if (cur_acc == -1) return (cur_rep == 0) ? 0.0f : (0.0f - cur_cost);
+    return __fmaf_rn(cur_cost, WVA_ACCEL_PENALTY, 0.0f - cur_cost);
+  }
+  if (cur_acc >= 0 && cur_acc == acc) return (cur_rep == reps) ? 0.0f : (cost - cur_cost);
+  return __fmaf_rn(cur_cost + cost, WVA_ACCEL_PENALTY, cost - cur_cost);
+}
+
+extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_rollout(
+    float *value, const uint8_t *feasible, const uint8_t *zero_empty, const int *cell_acc,
+    const int *num_replicas, const int *batch, const float *cost, const float *itl,
+    const float *ttft, const float *rho, const float *max_rate, const int *seg_start, int n_srv,
+    int n_cells, int n_steps, int n_acc, int group, float *pf, int *pi,
+    unsigned long long *totals, int *cur) {
+  const int lane = (int)threadIdx.x;
+  const int sub = lane & (group - 1);
+  const int srv = (int)blockIdx.x * (WVA_WAVE / group) + lane / group;
+  // lanes past the last server keep an empty segment and store nothing, but
+  // stay in the loop: the shuffles below are executed by the whole wave
+  const bool live = srv < n_srv;
+  const int beg = live ? seg_start[srv] : 0;
+  const int end = live ? seg_start[srv + 1] : 0;
+  int cur_acc = live ? cur[0 * n_srv + srv] : -3;
+  int cur_rep = live ? cur[1 * n_srv + srv] : 0;
+  float cur_cost = live ? __int_as_float(cur[2 * n_srv + srv]) : 0.0f;
+
+  for (int s = 0; s < n_steps; ++s) {
+    const size_t base = (size_t)s * (size_t)n_cells;
+    // this lane's best candidate and the fields its record and the chain need
+    float best = INFINITY;
+    int best_i = -1;
+    int b_acc = -1, b_reps = 0, b_batch = 0;
+    float b_cost = 0.0f, b_itl = 0.0f, b_ttft = 0.0f, b_rho = 0.0f, b_rate = 0.0f;
+    for (int i = beg + sub; i < end; i += group) {
+      const size_t o = base + (size_t)i;
+      if (!feasible[o]) continue;
+      const bool ze = zero_empty[o] != 0;
+      const int reps = num_replicas[o];
+      const float c = cost[o];
+      const int acc = cell_acc[i];
+      const float v = wva_rollout_value(ze, reps, c, acc, cur_acc, cur_rep, cur_cost);
+      value[o] = v;
+      if (best_i == -1 || v < best) {
+        best = v;
+        best_i = i;
+        b_acc = ze ? -2 : acc;
+        b_reps = reps;
+        b_cost = c;
+        b_batch = batch[o];
+        b_itl = itl[o];
+        b_ttft = ttft[o];
+        b_rho = rho[o];
+        b_rate = max_rate[o];
+      }
+    }
+    // the group's winner on its lane 0 (wva_winner_record's reduction), then
+    // on every lane of the group
+    float win = best;
+    int w = best_i;
+    for (int off = group >> 1; off > 0; off >>= 1) {
+      const float ov = __shfl_down(win, off, group);
+      const int oi = __shfl_down(w, off, group);
+      if (oi != -1 && (w == -1 || ov < win || (ov == win && oi < w))) {
+        win = ov;
+        w = oi;
+      }
+    }
+    w = __shfl(w, 0, group);
+    // the lane whose candidate won holds the winner's fields
+    const bool owner = live && w >= 0 && w == best_i;
+    if (owner || (live && w < 0 && sub == 0)) {
+      float *gf = pf + (size_t)s * 6 * (size_t)n_srv;
+      int *gi = pi + (size_t)s * 4 * (size_t)n_srv;
+      gf[0 * n_srv + srv] = b_cost;
+      gf[1 * n_srv + srv] = owner ? best : 0.0f;
+      gf[2 * n_srv + srv] = b_itl;
+      gf[3 * n_srv + srv] = b_ttft;
+      gf[4 * n_srv + srv] = b_rho;
+      gf[5 * n_srv + srv] = b_rate;
+      gi[0 * n_srv + srv] = b_acc;
+      gi[1 * n_srv + srv] = b_reps;
+      gi[2 * n_srv + srv] = b_batch;
+      gi[3 * n_srv + srv] = w;
+      if (b_acc >= 0 && b_acc < n_acc && b_reps > 0)
+        atomicAdd(totals + (size_t)s * (size_t)n_acc + (size_t)b_acc, (unsigned long long)b_reps);
+    }
+    // desired -> current, on every lane of the group
+    const int src = (w >= 0) ? ((w - beg) & (group - 1)) : 0;
+    const int n_acc_code = __shfl(b_acc, src, group);
+    const int n_reps = __shfl(b_reps, src, group);
+    const float n_cost = __shfl(b_cost, src, group);
+    if (w >= 0) {
+      cur_acc = (n_acc_code == -2) ? -1 : n_acc_code;
+      cur_rep = n_reps;
+      cur_cost = n_cost;
+    }
+  }
+  if (live && sub == 0) {
+    cur[0 * n_srv + srv] = cur_acc;
+    cur[1 * n_srv + srv] = cur_rep;
+    cur[2 * n_srv + srv] = __float_as_int(cur_cost);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // K4b wva_winner: the reconcile tick's winner step in one launch, one wave
 // per server: wva_argmin's selection followed by the winner record, i.e.
 // wva_plan_reduce on a single scenario without the totals. rec is the

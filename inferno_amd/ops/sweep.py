@@ -244,6 +244,21 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_scen][4][n_srv]
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][n_acc]
     ]
+    # forecast rollout (engine/fastpath.py FastSweep.rollout)
+    lib.wva_ctx_rollout.restype = ctypes.c_int
+    lib.wva_ctx_rollout.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_int,  # n_steps (1..PLAN_MAX_S)
+        ctypes.c_int,  # n_acc
+        ctypes.c_void_p,  # host fp32 [n_steps][n_cells] arrival rates
+        ctypes.c_void_p,  # host i32 [n_srv] cur_acc the chain starts from
+        ctypes.c_void_p,  # host i32 [n_srv] cur_rep
+        ctypes.c_void_p,  # host fp32 [n_srv] cur_cost
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned fp32 [n_steps][6][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_steps][4][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_steps][n_acc]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [3][n_srv] final allocation
+    ]
     lib.wva_ctx_plan_cells.restype = ctypes.c_int
     lib.wva_ctx_plan_cells.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
     # capacity-limited planning (FastSweep.plan(capacity=...))
