@@ -77,6 +77,23 @@ def _parse_scales(text: str, flag: str = "--scales") -> list[float]:
     return scales
 
 
+def _parse_token_scales(text: str) -> list[tuple[float, float]]:
+    pairs = []
+    for item in text.split(","):
+        if not item.strip():
+            continue
+        f_in, sep, f_out = item.partition(":")
+        try:
+            pairs.append((float(f_in), float(f_out)))
+        except ValueError:
+            sep = ""
+        if not sep:
+            raise SystemExit(f"--token-scales: expected IN:OUT[,IN:OUT...], got {item!r}")
+    if not pairs:
+        raise SystemExit("--token-scales: at least one IN:OUT pair is required")
+    return pairs
+
+
 def _parse_capacity(text: str) -> dict:
     cap = {}
     for item in text.split(","):
@@ -100,6 +117,11 @@ def cmd_plan(args) -> int:
     from .engine import FastSweep, SweepEngine
 
     limited = args.limited or args.capacity is not None
+    if args.token_scales is not None:
+        if limited or args.slo_scales is not None or args.rollout:
+            raise SystemExit("plan: --token-scales is an unlimited-mode plan; it does not "
+                             "combine with --slo-scales, --rollout, --limited or --capacity")
+        return _cmd_plan_tokens(args)
     if args.rollout:
         if limited or args.slo_scales is not None:
             raise SystemExit("plan: --rollout replays consecutive unlimited-mode reconciles; it "
@@ -111,7 +133,7 @@ def cmd_plan(args) -> int:
                              "combine with --limited or --capacity")
         return _cmd_plan_slo(args)
     if args.scales is None:
-        raise SystemExit("plan: one of --scales and --slo-scales is required")
+        raise SystemExit("plan: one of --scales, --slo-scales and --token-scales is required")
     scales = _parse_scales(args.scales)
     system, opt = _load_system(args.spec)
     backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
@@ -230,6 +252,62 @@ def _cmd_plan_slo(args) -> int:
     return 0
 
 
+def _cmd_plan_tokens(args) -> int:
+    """What-if token-mix plan: the unlimited-mode solution at each pair of
+    factors on the average input and output tokens and each load scale."""
+    import numpy as np
+
+    from .engine import FastSweep, SweepEngine
+
+    token_scales = _parse_token_scales(args.token_scales)
+    scales = _parse_scales(args.scales) if args.scales is not None else [1.0]
+    system, _ = _load_system(args.spec)
+    backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
+    fs = FastSweep(system, backend=backend)
+    try:
+        res = fs.plan_tokens(token_scales=token_scales, scales=scales)
+    except ValueError as e:
+        print(f"plan: {e}", file=sys.stderr)
+        return 2
+    # accelerator changes are relative to token scales 1:1 at load scale 1.0
+    # (the first of either when that one is not among them)
+    wref = token_scales.index((1.0, 1.0)) if (1.0, 1.0) in token_scales else 0
+    sref = scales.index(1.0) if 1.0 in scales else 0
+    acc = res.winners.acc_idx
+    blocks = []
+    for w, (f_in, f_out) in enumerate(token_scales):
+        rows = [{
+            "scale": scale,
+            "totalCost": round(float(res.cost_total[w, s]), 2),
+            "replicas": {
+                name: int(res.replicas_by_acc[w, s, j]) for j, name in enumerate(fs.acc_names)
+            },
+            "infeasibleServers": int(res.infeasible_servers[w, s]),
+            "acceleratorChanges": int(np.count_nonzero(acc[w, s] != acc[wref, sref])),
+        } for s, scale in enumerate(scales)]
+        blocks.append({"inTokenScale": f_in, "outTokenScale": f_out, "scenarios": rows})
+    if args.json:
+        print(json.dumps({"backend": backend,
+                          "referenceTokenScales": list(token_scales[wref]),
+                          "referenceScale": scales[sref], "servers": len(fs.server_names),
+                          "tokenScenarios": blocks}, indent=2))
+        return 0
+    names = fs.acc_names
+    for b in blocks:
+        print(f"token scales {b['inTokenScale']:g}:{b['outTokenScale']:g} (average input "
+              f"tokens x {b['inTokenScale']:g}, output tokens x {b['outTokenScale']:g})")
+        print(f"{'scale':>8} {'cost':>12} " + " ".join(f"{n:>10}" for n in names)
+              + f" {'infeasible':>10} {'acc-changes':>11}")
+        for r in b["scenarios"]:
+            print(f"{r['scale']:>8g} {r['totalCost']:>12.2f} "
+                  + " ".join(f"{r['replicas'][n]:>10}" for n in names)
+                  + f" {r['infeasibleServers']:>10} {r['acceleratorChanges']:>11}")
+    ref_in, ref_out = token_scales[wref]
+    print(f"({len(fs.server_names)} servers, backend {backend}; acc-changes are relative to "
+          f"token scales {ref_in:g}:{ref_out:g} at load scale {scales[sref]:g})")
+    return 0
+
+
 def _cmd_plan_rollout(args) -> int:
     """Forecast rollout: the scales are consecutive ticks, each reconciled
     against the allocation the tick before it left behind."""
@@ -308,6 +386,10 @@ def main() -> None:
     pp.add_argument("--slo-scales", default=None,
                     help="comma-separated factors on every TTFT and ITL target, e.g. 0.5,1,2: "
                          "one block per SLO scale (load scale 1 unless --scales is given)")
+    pp.add_argument("--token-scales", default=None,
+                    help="comma-separated IN:OUT factors on every server's average input and "
+                         "output tokens, e.g. 1:1,4:1,1:0.5: one block per pair (load scale 1 "
+                         "unless --scales is given)")
     pp.add_argument("--backend", choices=["auto", "gpu", "cpu"], default="auto")
     pp.add_argument("--json", action="store_true")
     pp.add_argument("--limited", action="store_true",

@@ -5,6 +5,7 @@ from .fastpath import (  # noqa: F401
     PlanResult,
     RolloutResult,
     SloPlanResult,
+    TokenPlanResult,
     WinnerRecord,
     feed_back,
 )

@@ -94,6 +94,22 @@ class SloPlanResult:
 
 
 @dataclass
+class TokenPlanResult:
+    """What-if token-mix plan: the unlimited-mode solution of W sets of
+    per-server average input / output token counts times S arrival-rate
+    scenarios of one fleet (FastSweep.plan_tokens)."""
+
+    winners: WinnerRecord  # every array [W, S, n_servers]
+    replicas_by_acc: np.ndarray  # int64 [W, S, n_acc], columns = FastSweep.acc_names
+    cost_total: np.ndarray  # float64 [W, S]: fp64 sum of the winners' fp32 cost
+    infeasible_servers: np.ndarray  # int64 [W, S]: servers with acc_idx == -1
+    arrival: np.ndarray  # float32 [S, n_servers]: the load scenarios evaluated
+    in_tok: np.ndarray  # int32 [W, n_servers]: the average input tokens evaluated
+    out_tok: np.ndarray  # int32 [W, n_servers]: the average output tokens evaluated
+    cells: Optional[dict] = None  # reconcile_cells() layout, arrays [W, S, n_cells]
+
+
+@dataclass
 class RolloutResult:
     """Forecast rollout: what the controller does over S consecutive ticks of
     an arrival-rate forecast, every tick judged against the allocation the
@@ -856,6 +872,176 @@ class FastSweep:
             t_itl=t_itl,
             cells=cells,
         )
+
+    # ------------------------------------------------------------------
+    # What-if token-mix planning
+    # ------------------------------------------------------------------
+    def plan_tokens(self, tokens=None, token_scales=None, scales=None, arrival=None,
+                    return_cells: bool = False) -> TokenPlanResult:
+        """Solve W sets of average token counts times S arrival-rate scenarios
+        of the fleet in one pass: what a change of the request shape costs
+        (longer prompts, longer or shorter outputs), at each load.
+
+        Token axis, exactly one of: ``tokens=(in_tok, out_tok)`` (two
+        [W, n_servers] integer arrays, every value >= 0 and within int32) and
+        ``token_scales`` (W pairs ``(f_in, f_out)`` of finite factors > 0; set
+        w is ``floor(float64(base) * f)`` of every server's average input and
+        output tokens, where a positive base never drops below 1, so that a
+        scale cannot switch a server's load off). Load axis: ``scales`` or
+        ``arrival`` as in plan(); with neither, the base load alone (S = 1).
+        1 <= W * S <= 256.
+
+        Slice (w, s) of the result is what reconcile() returns on a fresh
+        FastSweep of an identical system whose load is ``(arrival[s],
+        in_tok[w], out_tok[w])``, with the same current allocation.
+
+        On the GPU nothing of a cell is shared between two token sets: the
+        batch size N moves with the output tokens, and with it the chain
+        geometry and the block width. Every (set, cell) pair is a block of
+        its own, in the bucket and at the width a reconcile under that set
+        gives it, and every set is evaluated at every load. The pass brings
+        its own bucket layout and stays off the sizing memo, so a following
+        reconcile() is neither changed nor slowed and memo_stats() does not
+        move. Unlimited mode only."""
+        n_srv = len(self.server_names)
+        if (tokens is None) == (token_scales is None):
+            raise ValueError("plan_tokens() takes exactly one of tokens and token_scales")
+        i32 = np.iinfo(np.int32)
+        if token_scales is not None:
+            try:
+                sc = np.asarray(token_scales, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"token_scales is not numeric: {e}") from None
+            if sc.ndim != 2 or sc.shape[1] != 2:
+                raise ValueError(
+                    f"token_scales must be W pairs (f_in, f_out), got shape {sc.shape}")
+            if not np.isfinite(sc).all() or (sc <= 0).any():
+                raise ValueError("token_scales must be finite and positive")
+            _, base_in, base_out = self._base_load()
+            sets = []
+            for base, f in ((base_in, sc[:, 0]), (base_out, sc[:, 1])):
+                base = base.astype(np.float64)
+                with np.errstate(over="ignore"):
+                    v = np.floor(base[None, :] * f[:, None])
+                sets.append(np.where(base[None, :] > 0, np.maximum(v, 1.0), v))
+        else:
+            try:
+                t_in, t_out = tokens
+                raw = [np.asarray(t_in), np.asarray(t_out)]
+                sets = [a.astype(np.float64) for a in raw]
+            except (TypeError, ValueError) as e:
+                raise ValueError(
+                    f"tokens is not an (in_tok, out_tok) pair of integer arrays: {e}") from None
+            for a, r, what in zip(sets, raw, ("in_tok", "out_tok")):
+                if a.ndim != 2 or a.shape[1] != n_srv:
+                    raise ValueError(
+                        f"tokens {what} must have shape [W, {n_srv}], got {a.shape}")
+                if r.dtype.kind not in "iu" and not (
+                        np.isfinite(a).all() and (a == np.floor(a)).all()):
+                    raise ValueError(f"tokens {what} must hold integers")
+            if sets[0].shape != sets[1].shape:
+                raise ValueError("tokens in_tok and out_tok differ in shape")
+        for a, what in zip(sets, ("in_tok", "out_tok")):
+            if not np.isfinite(a).all() or (a < 0).any() or (a > i32.max).any():
+                raise ValueError(f"{what} must be non-negative and fit int32")
+        in_tok = np.ascontiguousarray(sets[0], dtype=np.int32)
+        out_tok = np.ascontiguousarray(sets[1], dtype=np.int32)
+        n_tok = in_tok.shape[0]
+        if scales is None and arrival is None:
+            scen = np.ascontiguousarray(self._base_load()[0][None, :], dtype=np.float32)
+        else:
+            scen = self._plan_scenarios(scales, arrival, who="plan_tokens()")
+        n_load = scen.shape[0]
+        if not 1 <= n_tok * n_load <= PLAN_MAX_S:
+            raise ValueError(
+                f"plan_tokens() takes 1..{PLAN_MAX_S} (token set, load) pairs, "
+                f"got {n_tok} x {n_load}"
+            )
+
+        n_acc = len(self.acc_names)
+        cells = totals = None
+        if self.backend != "gpu":
+            rows = []
+            with self._scenario_tokens() as set_tokens:
+                for w in range(n_tok):
+                    set_tokens(in_tok[w], out_tok[w])
+                    rows.append(self._plan_cpu(scen))
+            flat = WinnerRecord(**{
+                f: np.concatenate([getattr(r, f) for r in rows]) for f in _WINNER_FIELDS
+            })
+        elif self.n_cells == 0 or n_acc == 0:
+            flat = _empty_winners(n_tok * n_load, n_srv)
+        else:
+            self._tick(plan_arrival=scen, launch=False)  # stage the rest of the cell state
+            cs = self.cell_server
+            of, oi, totals = self._gpu.plan_tokens(
+                np.ascontiguousarray(scen[:, cs], dtype=np.float32),
+                np.ascontiguousarray(in_tok[:, cs]), np.ascontiguousarray(out_tok[:, cs]),
+                self._token_batch_n(scen, out_tok), n_acc,
+            )
+            flat = _winner_record(of, oi)
+            if return_cells:
+                cells = self._plan_cells_gpu(n_tok * n_load)
+                for k in CELL_KEYS:
+                    cells[k] = cells[k].reshape(n_tok, n_load, self.n_cells)
+        totals, cost_total, infeasible = self._plan_totals(flat, totals)
+        grid = (n_tok, n_load)
+        return TokenPlanResult(
+            winners=WinnerRecord(**{
+                f: getattr(flat, f).reshape(grid + (n_srv,)) for f in _WINNER_FIELDS
+            }),
+            replicas_by_acc=totals.reshape(grid + (n_acc,)),
+            cost_total=cost_total.reshape(grid),
+            infeasible_servers=infeasible.reshape(grid),
+            arrival=scen,
+            in_tok=in_tok,
+            out_tok=out_tok,
+            cells=cells,
+        )
+
+    def _token_batch_n(self, scen: np.ndarray, out_tok: np.ndarray) -> np.ndarray:
+        """int32 [W, n_cells]: the batch size N of every cell under every token
+        set, by _refresh_dynamic's rule with the plan's zero-load decision: 1
+        where no scenario loads the cell or the set's out_tok is 0, else the
+        server's override or max(maxBatchSize * atTokens // out_tok, 1)."""
+        cs = self.cell_server
+        st = self._stat
+        c_out = out_tok[:, cs]
+        prod = st["perf_max_batch_cfg"].astype(np.int64) * st["at_tokens"].astype(np.int64)
+        n_scaled = np.maximum(prod[None, :] // np.maximum(c_out, 1).astype(np.int64), 1)
+        base = np.where(st["override"][None, :] > 0, st["override"][None, :],
+                        n_scaled).astype(np.int32)
+        zero_load = (scen.max(axis=0)[cs] == 0)[None, :] | (c_out == 0)
+        return np.ascontiguousarray(np.where(zero_load, 1, base), dtype=np.int32)
+
+    @contextlib.contextmanager
+    def _scenario_tokens(self):
+        """For the CPU golden path: yields set_tokens(in_row, out_row), which
+        puts one token set on the server objects (and into the load override,
+        when set, which _scenario_loads copies the tokens from); both are
+        restored afterwards in any case."""
+        saved_override = self.load_override
+        saved = [
+            None if srv.load is None else (srv.load.avgInTokens, srv.load.avgOutTokens)
+            for srv in self._srv_objs
+        ]
+
+        def set_tokens(in_row, out_row):
+            for i, srv in enumerate(self._srv_objs):
+                if srv.load is not None:
+                    srv.load.avgInTokens = int(in_row[i])
+                    srv.load.avgOutTokens = int(out_row[i])
+            if saved_override is not None:
+                self.load_override = (saved_override[0], np.array(in_row, dtype=np.int32),
+                                      np.array(out_row, dtype=np.int32))
+
+        try:
+            yield set_tokens
+        finally:
+            self.load_override = saved_override
+            for srv, old in zip(self._srv_objs, saved):
+                if old is not None:
+                    srv.load.avgInTokens, srv.load.avgOutTokens = old
 
     def _server_targets(self):
         """(targets, owner), cached per fleet topology: the Target object each

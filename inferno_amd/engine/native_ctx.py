@@ -10,6 +10,7 @@ handle, and the handle is destroyed first (close()).
 from __future__ import annotations
 
 import ctypes
+import os
 from typing import Optional
 
 import numpy as np
@@ -21,8 +22,16 @@ from ..ops.sweep import (
     HipKernelError,
     alloc_gmem_slabs,
     choose_buckets,
+    gmem_slab_bytes,
     load_library,
 )
+
+# Most bytes of global-memory geometry slabs one huge-tier bucket of a
+# token-mix plan may hold (NativeCtx.plan_tokens): the tier's tasks grow with
+# the number of token sets, so a bucket that needs more runs in consecutive
+# slices which share one allocation of at most this size.
+# INFERNO_PLAN_TOKENS_SLAB_BYTES replaces it, read when a context is created.
+PLAN_TOKENS_SLAB_BYTES = 1 << 30
 
 # The dynamic block (4-byte words, int32 rows then fp32 rows) in row order.
 DYN_INT = ("in_tok", "out_tok", "batch_n", "perf_max_batch", "cur_replicas", "flags")
@@ -92,6 +101,19 @@ class NativeCtx:
         self.bucket_key = None  # batch_n bytes `buckets` was chosen for
         self.buckets: list = []
         self.greedy_static_key = None  # static greedy inputs last pushed
+        # token-mix planning's own bucket cache: the task batch_n bytes
+        # `tok_buckets` was chosen for. Apart from bucket_key / buckets, which
+        # describe the layout the context holds for its reconciles.
+        self.tok_bucket_key = None
+        self.tok_buckets: list = []
+        env = os.environ.get("INFERNO_PLAN_TOKENS_SLAB_BYTES")
+        try:
+            self.tok_slab_budget = int(env) if env else PLAN_TOKENS_SLAB_BYTES
+        except ValueError:
+            raise ValueError(
+                f"INFERNO_PLAN_TOKENS_SLAB_BYTES must be an integer, got {env!r}") from None
+        if self.tok_slab_budget < 1:
+            raise ValueError("INFERNO_PLAN_TOKENS_SLAB_BYTES must be positive")
         self._create_ctx()
 
     def _create_ctx(self) -> None:
@@ -301,6 +323,76 @@ class NativeCtx:
         )
         if rc != 0:
             raise HipKernelError(f"wva_ctx_plan_slo failed: {rc}")
+        return (
+            _copy_out(out[0], ctypes.c_float, (n_scen, 6, self.n_srv)),
+            _copy_out(out[1], ctypes.c_int32, (n_scen, 4, self.n_srv)),
+            _copy_out(out[2], ctypes.c_uint64, (n_scen, n_acc)).astype(np.int64),
+        )
+
+    def tok_buckets_for(self, task_n: np.ndarray):
+        """Task buckets of a token-mix plan, chosen over the flattened
+        [W * n_cells] task batch sizes and cached on their bytes: [(nt, device
+        task ids or None, max N, tasks, slabs, tasks per launch)]. A huge-tier
+        bucket whose slabs would exceed the budget gets slabs for as many
+        tasks as fit and runs in slices of that many (0 = one launch)."""
+        import torch
+
+        key = task_n.tobytes()
+        if self.tok_bucket_key == key:
+            return self.tok_buckets
+        self.tok_bucket_key, self.tok_buckets = None, []  # drop the old slabs first
+        buckets = []
+        for nt, ids, bmax, count, gmem in choose_buckets(task_n):
+            slabs, per_launch = (None, None), 0
+            if gmem:
+                per_task = gmem_slab_bytes(bmax, nt)
+                fit = self.tok_slab_budget // per_task
+                if fit < 1:
+                    raise HipKernelError(
+                        f"one token-mix task of batch size {bmax} needs {per_task} bytes of "
+                        f"geometry slabs, above the budget of {self.tok_slab_budget} "
+                        "(INFERNO_PLAN_TOKENS_SLAB_BYTES)"
+                    )
+                if fit < count:
+                    per_launch = int(fit)
+                    if ids is None:  # a slice names its tasks
+                        ids = np.arange(count, dtype=np.int32)
+                slabs = alloc_gmem_slabs(min(count, fit), bmax, nt, self.device)
+            ids_t = torch.from_numpy(ids).to(self.device) if ids is not None else None
+            buckets.append((nt, ids_t, bmax, count, slabs, per_launch))
+        self.tok_bucket_key, self.tok_buckets = key, buckets
+        return buckets
+
+    def plan_tokens(self, cell_scen: np.ndarray, cell_in: np.ndarray, cell_out: np.ndarray,
+                    cell_n: np.ndarray, n_acc: int):
+        """wva_ctx_plan_tokens on [S, n_cells] fp32 arrivals and [W, n_cells]
+        int32 in_tok / out_tok / batch_n (the tick is staged): plan()'s first
+        three arrays with W * S leading, slice w * S + s being token set w at
+        arrival rates s. The pass runs on task buckets of its own
+        (tok_buckets_for); the context's reconcile layout is not touched."""
+        n_load, n_tok = cell_scen.shape[0], cell_n.shape[0]
+        n_scen = n_tok * n_load
+        buckets = self.tok_buckets_for(cell_n.reshape(-1))
+
+        def ptrs(tensors):
+            return (ctypes.c_void_p * len(tensors))(
+                *[ctypes.c_void_p(t.data_ptr()) if t is not None else None for t in tensors]
+            )
+
+        def ints(values):
+            return (ctypes.c_int * len(values))(*values)
+
+        out = [ctypes.c_void_p() for _ in range(3)]
+        rc = self._lib.wva_ctx_plan_tokens(
+            self.ctx, n_tok, n_scen, n_acc, cell_scen.ctypes.data, cell_in.ctypes.data,
+            cell_out.ctypes.data, cell_n.ctypes.data, len(buckets),
+            ints([b[0] for b in buckets]), ptrs([b[1] for b in buckets]),
+            ints([b[3] for b in buckets]), ints([b[2] for b in buckets]),
+            ptrs([b[4][0] for b in buckets]), ptrs([b[4][1] for b in buckets]),
+            ints([b[5] for b in buckets]), *[ctypes.byref(p) for p in out],
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_plan_tokens failed: {rc}")
         return (
             _copy_out(out[0], ctypes.c_float, (n_scen, 6, self.n_srv)),
             _copy_out(out[1], ctypes.c_int32, (n_scen, 4, self.n_srv)),

@@ -5,7 +5,8 @@
 // it does not cover, regime-bucketed sweep launches overlapped via events on
 // side streams and the winner kernel —, one D2H copy, sync):
 // wva_ctx_tick(ctx, ...); wva_reconcile(ctx) runs an already
-// staged tick; the planning passes share the context's arrays and buckets.
+// staged tick; the planning passes share the context's arrays and buckets
+// (token-mix planning brings a bucket list of its own, over tasks).
 #include <vector>
 
 #include "../native/wva_arena.h"  // 256-aligned arena layout (host only)
@@ -20,6 +21,10 @@ struct WvaBucket {
   int max_n;
   float *g_inv;      // non-null: global-memory geometry slab (huge-N spill)
   double *g_anchor;
+  // blocks per launch: 0 = all n_blocks in one launch; else the bucket runs as
+  // consecutive launches of at most this many blocks on its stream, which
+  // reuse the first `slice` slabs (token-mix planning's huge tier)
+  int slice;
 };
 
 // Created with `new WvaCtx()`: every member without an initialiser below
@@ -120,6 +125,17 @@ struct WvaCtx {
   float *slo_itl;    // device [T][n_cells]
   float *slo_pin_ttft;  // pinned mirrors
   float *slo_pin_itl;
+  // token-mix planning (wva_ctx_plan_tokens): the per-cell token sets,
+  // allocated on first use, grown to the largest count seen, freed in destroy
+  int tok_cap;       // token sets the buffers hold (0 = not allocated)
+  void *tok_dev;     // one device allocation, carved up below
+  void *tok_pin;     // one pinned host allocation, carved up below
+  int *tok_in;       // device [W][n_cells]
+  int *tok_out;      // device [W][n_cells]
+  int *tok_n;        // device [W][n_cells]: the batch size N under set w
+  int *tok_pin_in;   // pinned mirrors
+  int *tok_pin_out;
+  int *tok_pin_n;
   // forecast rollout (wva_ctx_rollout): the per-server current allocation the
   // chain starts from and ends with, three rows of n_srv words (cur_acc,
   // cur_rep, cur_cost). Allocated on first use, freed in destroy.
@@ -615,6 +631,7 @@ extern "C" int wva_ctx_set_buckets(void *ctx, int n_buckets, const int *nts,
     c->buckets[i].max_n = max_ns[i];
     c->buckets[i].g_inv = g_invs ? (float *)g_invs[i] : nullptr;
     c->buckets[i].g_anchor = g_anchors ? (double *)g_anchors[i] : nullptr;
+    c->buckets[i].slice = 0;
   }
   c->analyzer_mode = analyzer_mode;
   c->cv2 = cv2;
@@ -627,26 +644,39 @@ extern "C" int wva_ctx_set_buckets(void *ctx, int n_buckets, const int *nts,
 }
 
 // The bucket sweeps of one pass, after the uploads queued on s0: record the
-// upload event, launch bucket 0 on s0 and the others on the side streams
-// behind that event, then join them back onto s0. `out` receives the per-cell
-// results; `plan` (may be null) selects the planning kernels, `slo` (may be
-// null) the SLO-planning ones. Enqueues only —
+// upload event, launch bucket 0 of `buckets` on s0 and the others on the side
+// streams behind that event, then join them back onto s0. `out` receives the
+// per-cell results; `plan` (may be null) selects the planning kernels, `slo`
+// (may be null) the SLO-planning ones. With `tok` (token-mix planning) the
+// buckets hold tasks, `in` is the view with the [W][n_cells] token rows, and
+// the sizing memo stays out of it. Enqueues only —
 // no synchronising call, since the reconcile pipeline runs under stream
 // capture.
-static int wva_run_buckets(WvaCtx *c, const WvaCellsOut &out, const WvaPlanArgs *plan,
-                           const WvaSloArgs *slo = nullptr) {
+static int wva_run_buckets(WvaCtx *c, const WvaBucket *buckets, int n_buckets,
+                           const WvaCellsIn &in, const WvaCellsOut &out, const WvaPlanArgs *plan,
+                           const WvaSloArgs *slo = nullptr, const WvaTokArgs *tok = nullptr) {
+  if (n_buckets < 0 || n_buckets > WVA_MAX_BUCKETS) return -1;
+  WvaMemoRec *memo = tok != nullptr ? nullptr : c->memo;
+  unsigned *memo_cnt = tok != nullptr ? nullptr : c->memo_cnt;
   if (hipEventRecord(c->e_up, c->s0) != hipSuccess) return -10;
-  for (int i = 0; i < c->n_buckets; ++i) {
+  for (int i = 0; i < n_buckets; ++i) {
     hipStream_t s = (i == 0) ? c->s0 : c->side[i - 1];
     if (i > 0 && hipStreamWaitEvent(s, c->e_up, 0) != hipSuccess) return -11;
-    const WvaBucket &b = c->buckets[i];
-    const int rc =
-        wva_sweep_dispatch(b.n_blocks, b.max_n, b.nt, b.cell_ids, c->analyzer_mode, c->cv2, s,
-                           c->in, out, b.g_inv, b.g_anchor, c->memo, c->memo_cnt, plan, slo);
-    if (rc != 0) return rc;
+    const WvaBucket &b = buckets[i];
+    // one launch, or consecutive slices on this stream (stream order keeps a
+    // slice off the slabs until the one before it is done with them)
+    const int step = (b.slice > 0 && b.slice < b.n_blocks) ? b.slice : b.n_blocks;
+    if (step < b.n_blocks && b.cell_ids == nullptr) return -2;  // a slice needs its ids
+    for (int at = 0; at < b.n_blocks; at += step) {
+      const int n = b.n_blocks - at < step ? b.n_blocks - at : step;
+      const int rc = wva_sweep_dispatch(n, b.max_n, b.nt, b.cell_ids ? b.cell_ids + at : nullptr,
+                                        c->analyzer_mode, c->cv2, s, in, out, b.g_inv,
+                                        b.g_anchor, memo, memo_cnt, plan, slo, tok);
+      if (rc != 0) return rc;
+    }
     if (i > 0 && hipEventRecord(c->e_b[i - 1], s) != hipSuccess) return -12;
   }
-  for (int i = 1; i < c->n_buckets; ++i)
+  for (int i = 1; i < n_buckets; ++i)
     if (hipStreamWaitEvent(c->s0, c->e_b[i - 1], 0) != hipSuccess) return -14;
   return 0;
 }
@@ -686,7 +716,7 @@ static int wva_enqueue_pipeline(WvaCtx *c) {
     if (err != hipSuccess) return (int)err;
   } else {
     // 2. bucket launches, overlapped on the side streams
-    const int rc = wva_run_buckets(c, c->out, nullptr);
+    const int rc = wva_run_buckets(c, c->buckets, c->n_buckets, c->in, c->out, nullptr);
     if (rc != 0) return rc;
 
     // 3. winner selection + winner records on s0, one launch
@@ -922,6 +952,33 @@ static int wva_slo_reserve(WvaCtx *c, int n_tgt) {
   return 0;
 }
 
+static void wva_tok_release(WvaCtx *c) {
+  wva_arena_free(c->tok_dev, c->tok_pin);
+  c->tok_cap = 0;
+}
+
+// (re)allocate the token-mix planning arrays for n_tok token sets; on failure
+// nothing is held and reconciles and the other plans keep working
+static int wva_tok_reserve(WvaCtx *c, int n_tok) {
+  if (n_tok <= c->tok_cap) return 0;
+  wva_tok_release(c);
+  const size_t b_t = (size_t)n_tok * (size_t)c->n_cells * sizeof(int);
+  enum { A_IN, A_OUT, A_N, A_COUNT };  // the same three arrays on the device and pinned
+  const size_t size[A_COUNT] = {b_t, b_t, b_t};
+  size_t off[A_COUNT];
+  const size_t bytes = wva_arena_layout(size, A_COUNT, off);
+  if (!wva_arena_alloc(c, bytes, bytes, false, &c->tok_dev, &c->tok_pin)) return -38;
+  c->tok_cap = n_tok;
+  char *d = (char *)c->tok_dev, *h = (char *)c->tok_pin;
+  c->tok_in = (int *)(d + off[A_IN]);
+  c->tok_out = (int *)(d + off[A_OUT]);
+  c->tok_n = (int *)(d + off[A_N]);
+  c->tok_pin_in = (int *)(h + off[A_IN]);
+  c->tok_pin_out = (int *)(h + off[A_OUT]);
+  c->tok_pin_n = (int *)(h + off[A_N]);
+  return 0;
+}
+
 // the rollout's current-allocation rows; on failure nothing is held and
 // reconciles and plans keep working
 static int wva_roll_reserve(WvaCtx *c) {
@@ -1027,6 +1084,11 @@ extern "C" int wva_ctx_set_greedy_static(void *ctx, const int *cell_type, const 
 // n_scen / n_tgt arrival-rate scenarios, target-major: scen_arrival holds the
 // arrival-rate scenarios only, the target sets go up next to it, and step 2
 // launches the SLO-planning kernels; everything else is the same pass.
+//
+// With tok (wva_ctx_plan_tokens) the n_scen slices are n_tok token sets times
+// n_scen / n_tok arrival-rate scenarios, set-major: the token sets go up next
+// to the arrivals and step 2 launches the token-mix kernels over the pass's
+// own bucket list of tasks; the context's buckets are not read or changed.
 struct WvaLimArgs {
   int n_types;
   const int *capacity;  // host [n_scen][n_types]
@@ -1043,20 +1105,34 @@ struct WvaRollArgs {
   const int *cur_rep;     // host [n_srv]
   const float *cur_cost;  // host [n_srv]
 };
+struct WvaTokSets {
+  int n_tok;
+  const int *in_tok;   // host [n_tok][n_cells]
+  const int *out_tok;  // host [n_tok][n_cells]
+  const int *batch_n;  // host [n_tok][n_cells]
+  const WvaBucket *buckets;  // the pass's task buckets
+  int n_buckets;
+};
 
 static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arrival,
                         const WvaLimArgs *lim, const void **out_pf, const void **out_pi,
                         const void **out_totals, const WvaSloTargets *slo = nullptr,
-                        const WvaRollArgs *roll = nullptr) {
+                        const WvaRollArgs *roll = nullptr, const WvaTokSets *tok = nullptr) {
   if (c == nullptr || scen_arrival == nullptr) return -31;
   if (n_scen < 1 || n_scen > WVA_PLAN_MAX_S || n_acc < 1) return -32;
   if (slo != nullptr && (slo->n_tgt < 1 || n_scen % slo->n_tgt != 0)) return -32;
+  if (tok != nullptr && (slo != nullptr || tok->n_tok < 1 || n_scen % tok->n_tok != 0))
+    return -32;
   if (c->n_cells <= 0 || c->n_srv <= 0) return -33;
   c->plan_s = 0;
   int rc = wva_plan_reserve(c, n_scen, n_acc);
   if (rc != 0) return rc;
   if (slo != nullptr) {
     rc = wva_slo_reserve(c, slo->n_tgt);
+    if (rc != 0) return rc;
+  }
+  if (tok != nullptr) {
+    rc = wva_tok_reserve(c, tok->n_tok);
     if (rc != 0) return rc;
   }
   if (lim != nullptr) {
@@ -1067,8 +1143,11 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
     rc = wva_roll_reserve(c);
     if (rc != 0) return rc;
   }
-  // arrival-rate scenarios: all n_scen slices, or one SLO plan's load axis
-  const int n_load = slo != nullptr ? n_scen / slo->n_tgt : n_scen;
+  // arrival-rate scenarios: all n_scen slices, or the load axis of an SLO or
+  // token-mix plan
+  const int n_load = slo != nullptr   ? n_scen / slo->n_tgt
+                     : tok != nullptr ? n_scen / tok->n_tok
+                                      : n_scen;
   const size_t cells = (size_t)n_load * (size_t)c->n_cells;
   hipError_t err;
 
@@ -1090,6 +1169,19 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
     err = hipMemcpyAsync(c->slo_itl, c->slo_pin_itl, tcells * sizeof(float),
                          hipMemcpyHostToDevice, c->s0);
     if (err != hipSuccess) return (int)err;
+  }
+  if (tok != nullptr) {
+    // (one copy per array: the arena pads each to its alignment)
+    const size_t tcells = (size_t)tok->n_tok * (size_t)c->n_cells;
+    memcpy(c->tok_pin_in, tok->in_tok, tcells * sizeof(int));
+    memcpy(c->tok_pin_out, tok->out_tok, tcells * sizeof(int));
+    memcpy(c->tok_pin_n, tok->batch_n, tcells * sizeof(int));
+    int *const dst[3] = {c->tok_in, c->tok_out, c->tok_n};
+    const int *const src[3] = {c->tok_pin_in, c->tok_pin_out, c->tok_pin_n};
+    for (int r = 0; r < 3; ++r) {
+      err = hipMemcpyAsync(dst[r], src[r], tcells * sizeof(int), hipMemcpyHostToDevice, c->s0);
+      if (err != hipSuccess) return (int)err;
+    }
   }
   err = hipMemcpyAsync(c->dev_dyn, c->pin_dyn, (size_t)WVA_DYN_ROWS * c->n_cells * 4,
                        hipMemcpyHostToDevice, c->s0);
@@ -1117,13 +1209,23 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   }
 
   // 2. planning buckets: same streams, fork/join and order as the reconcile
-  if (slo != nullptr) {
+  if (tok != nullptr) {
+    // the pass's own task buckets on a view of the inputs whose token rows
+    // are the [W][n_cells] arrays; the context's layout is left alone
+    WvaCellsIn tin = c->in;
+    tin.in_tok = c->tok_in;
+    tin.out_tok = c->tok_out;
+    tin.batch_n = c->tok_n;
+    const WvaTokArgs ta = {c->n_cells, n_load, c->plan_scen, tok->n_tok};
+    rc = wva_run_buckets(c, tok->buckets, tok->n_buckets, tin, c->plan_out, nullptr, nullptr,
+                         &ta);
+  } else if (slo != nullptr) {
     const WvaSloArgs sa = {c->n_cells, n_load,       c->plan_scen,
                            slo->n_tgt, c->slo_ttft, c->slo_itl};
-    rc = wva_run_buckets(c, c->plan_out, nullptr, &sa);
+    rc = wva_run_buckets(c, c->buckets, c->n_buckets, c->in, c->plan_out, nullptr, &sa);
   } else {
     const WvaPlanArgs pa = {c->n_cells, n_scen, c->plan_scen};
-    rc = wva_run_buckets(c, c->plan_out, &pa);
+    rc = wva_run_buckets(c, c->buckets, c->n_buckets, c->in, c->plan_out, &pa);
   }
   if (rc != 0) return rc;
 
@@ -1271,6 +1373,58 @@ extern "C" int wva_ctx_rollout(void *ctx, int n_steps, int n_acc, const float *s
   return 0;
 }
 
+// One token-mix planning pass: n_tok sets of per-cell token averages times
+// n_load = n_scen / n_tok arrival-rate scenarios, n_scen slices in all
+// (1..WVA_PLAN_MAX_S), slice w * n_load + s being token set w at arrival rates
+// s. scen_arrival: host [n_load][n_cells] fp32 (req/min); in_tok, out_tok,
+// batch_n: host [n_tok][n_cells] int32, batch_n being the batch size N the
+// single-scenario path stages for the cell under set w. The tick is staged as
+// for wva_ctx_plan (its token rows are not read). The pass brings its own
+// bucket list over the tasks w * n_cells + cell, chosen from batch_n: per
+// bucket the block width, the device int32 task ids (null: every task, in
+// order), the task count, the largest N, the slabs of a global-memory bucket
+// and the tasks per launch (0: all; else the bucket runs in consecutive slices
+// of that many tasks, which share slabs for that many blocks). Nothing of the
+// context's reconcile layout is read or changed, and the sizing memo is left
+// out. The three out pointers ([n_scen] leading) are as for wva_ctx_plan;
+// wva_ctx_plan_cells works on the result. -38: the token arrays could not be
+// allocated (the context is intact).
+extern "C" int wva_ctx_plan_tokens(void *ctx, int n_tok, int n_scen, int n_acc,
+                                   const float *scen_arrival, const int *in_tok,
+                                   const int *out_tok, const int *batch_n, int n_buckets,
+                                   const int *nts, const void **task_ids, const int *n_blocks,
+                                   const int *max_ns, const void **g_invs,
+                                   const void **g_anchors, const int *slices,
+                                   const void **out_pf, const void **out_pi,
+                                   const void **out_totals) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || in_tok == nullptr || out_tok == nullptr || batch_n == nullptr) return -31;
+  if (n_buckets < 0 || n_buckets > WVA_MAX_BUCKETS) return -32;
+  if (n_buckets > 0 && (nts == nullptr || task_ids == nullptr || n_blocks == nullptr ||
+                        max_ns == nullptr))
+    return -31;
+  if (n_tok < 1 || n_tok > WVA_PLAN_MAX_S) return -32;
+  const long n_tasks = (long)n_tok * (long)c->n_cells;
+  if (n_tasks > 0x7fffffffL) return -32;
+  WvaBucket buckets[WVA_MAX_BUCKETS];
+  for (int i = 0; i < n_buckets; ++i) {
+    WvaBucket &b = buckets[i];
+    b.nt = nts[i];
+    b.cell_ids = (const int *)task_ids[i];
+    b.n_blocks = n_blocks[i];
+    b.max_n = max_ns[i];
+    b.g_inv = g_invs ? (float *)g_invs[i] : nullptr;
+    b.g_anchor = g_anchors ? (double *)g_anchors[i] : nullptr;
+    b.slice = slices ? slices[i] : 0;
+    if (b.n_blocks < 0 || (long)b.n_blocks > n_tasks || b.slice < 0) return -32;
+    // the identity list names every task; a partial bucket brings its ids
+    if (b.cell_ids == nullptr && (long)b.n_blocks != n_tasks) return -32;
+  }
+  const WvaTokSets tok = {n_tok, in_tok, out_tok, batch_n, buckets, n_buckets};
+  return wva_plan_run(c, n_scen, n_acc, scen_arrival, nullptr, out_pf, out_pi, out_totals,
+                      nullptr, nullptr, &tok);
+}
+
 // Per-cell outputs of the last successful wva_ctx_plan, copied into ten host
 // arrays of plan_s * n_cells elements each, in WvaCellsOut order (feasible,
 // zero_empty: u8; num_replicas, batch: i32; cost, value, itl, ttft, rho,
@@ -1307,6 +1461,7 @@ extern "C" void wva_ctx_destroy(void *ctx) {
   if (c->tasks != nullptr) (void)hipFree(c->tasks);
   wva_plan_release(c);
   wva_slo_release(c);
+  wva_tok_release(c);
   wva_lim_release(c);
   wva_arena_free(c->roll_dev, c->roll_pin);
   if (c->lim_static != nullptr) (void)hipFree(c->lim_static);

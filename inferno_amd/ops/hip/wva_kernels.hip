@@ -48,6 +48,10 @@
 //       scenarios per cell (planning), and as wva_slo_plan_t<NT>: T SLO-target
 //       sets times S arrival-rate scenarios per cell (SLO planning).
 //
+//       And as wva_tok_plan_t<NT>: W sets of token averages times S scenarios
+//       (token-mix planning), one block per (set, cell) at the width the cell
+//       has under that set.
+//
 //   K4 wva_plan_reduce: per (server, scenario) K2's selection, the winner
 //       record and the per-accelerator replica totals, in one launch.
 //
@@ -1375,6 +1379,66 @@ __global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
                                           g_inv, g_anchor, memo, memo_cnt, plan);
 }
 
+// Token-mix planning sweep: n_tok sets of per-cell (in_tok, out_tok, batch_n)
+// times n_scen arrival-rate scenarios. Nothing of a cell survives a change of
+// tokens (the geometry, N and with N the block width all move), so a set is
+// not a loop inside the block: task w * n_cells + cell is a block of its own,
+// in the bucket and at the width the single-scenario path gives that cell under
+// set w. Block b runs task task_ids[b] (null: task b) as wva_plan_t runs a
+// cell, on a view of the arrays shifted to the set: in.in_tok / out_tok /
+// batch_n are [n_tok][n_cells] and the block reads row w, the ten outputs are
+// [n_tok][n_scen][n_cells] and the block writes slab w of them, the arrivals
+// [n_scen][n_cells] are shared, and everything else is the cell's own. The
+// cell function runs unchanged on that view.
+//
+// No sizing memo: the n_tok blocks of one cell would race on its single
+// record, and another set's sizing in it would cost the next reconcile a miss.
+// The memo arguments are there for the launcher's sake and are not read.
+//
+// A task outside the grid, or one whose N does not fit the bucket it was put
+// in, is skipped (uniformly, before any barrier): the host chose the buckets
+// from the same batch_n it uploaded, so this only keeps a broken caller from
+// running past the bucket's LDS or slab.
+struct WvaTokArgs {
+  int n_cells;
+  int n_scen;
+  const float *scen_arrival;  // device, [n_scen][n_cells]
+  int n_tok;
+};
+template <int NT, bool GMEM>
+__global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
+    wva_tok_plan_t(WvaCellsIn in, WvaCellsOut out, int n_blocks, const int *task_ids, int max_n,
+                   int analyzer_mode, float cv2, float *g_inv, double *g_anchor, WvaMemoRec *,
+                   unsigned *, WvaTokArgs tok) {
+  extern __shared__ double smem[];
+  if ((int)blockIdx.x >= n_blocks) return;
+  const int task = task_ids ? task_ids[blockIdx.x] : (int)blockIdx.x;
+  if (task < 0 || tok.n_cells < 1 || task / tok.n_cells >= tok.n_tok) return;
+  const int w = task / tok.n_cells;
+  const int cell = task - w * tok.n_cells;
+  const size_t row = (size_t)w * (size_t)tok.n_cells;
+  const size_t slab = row * (size_t)tok.n_scen;
+  in.in_tok += row;
+  in.out_tok += row;
+  in.batch_n += row;
+  const int n = in.batch_n[cell];
+  if (n < 1 || n > max_n) return;
+  out.feasible += slab;
+  out.zero_empty += slab;
+  out.num_replicas += slab;
+  out.batch += slab;
+  out.cost += slab;
+  out.value += slab;
+  out.itl += slab;
+  out.ttft += slab;
+  out.rho += slab;
+  out.max_rate += slab;
+  const WvaPlanArgs plan = {tok.n_cells, tok.n_scen, tok.scen_arrival};
+  wva_cell_body<NT, GMEM, WVA_MODE_PLAN>(in, out, cell, (int)threadIdx.x, smem, blockIdx.x, max_n,
+                                         analyzer_mode, cv2, g_inv, g_anchor, nullptr, nullptr,
+                                         plan);
+}
+
 // ---------------------------------------------------------------------------
 // K2: segmented argmin per server over the sweep output.
 // ---------------------------------------------------------------------------
@@ -1454,7 +1518,8 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
                               const WvaCellsIn &in, const WvaCellsOut &out, float *g_inv,
                               double *g_anchor, WvaMemoRec *memo, unsigned *memo_cnt,
                               const WvaPlanArgs *plan = nullptr,
-                              const WvaSloArgs *slo = nullptr) {
+                              const WvaSloArgs *slo = nullptr,
+                              const WvaTokArgs *tok = nullptr) {
   if (n_blocks <= 0) return 0;
   const bool gmem = g_inv != nullptr && g_anchor != nullptr;
   if (max_n < 1) return -2;
@@ -1476,7 +1541,8 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
   };
   int rc = -3;
 #define WVA_LAUNCH(NTV, GM)                                        \
-  rc = slo != nullptr    ? launch(&wva_slo_plan_t<NTV, GM>, *slo)  \
+  rc = tok != nullptr    ? launch(&wva_tok_plan_t<NTV, GM>, *tok)  \
+       : slo != nullptr  ? launch(&wva_slo_plan_t<NTV, GM>, *slo)  \
        : plan != nullptr ? launch(&wva_plan_t<NTV, GM>, *plan)     \
                          : launch(&wva_sweep_t<NTV, GM>)
   if (gmem) {

@@ -139,6 +139,13 @@ def alloc_gmem_slabs(n_blocks: int, max_n: int, nt: int, device: str):
     g_anchor = torch.empty((n_blocks, nt * ksub), dtype=torch.float64, device=device)
     return g_inv, g_anchor
 
+def gmem_slab_bytes(max_n: int, nt: int) -> int:
+    """Bytes of one block's slabs as alloc_gmem_slabs lays them out."""
+    chunk = (max_n + nt - 1) // nt
+    ksub = (chunk + 31) // 32
+    return chunk * nt * 4 + nt * ksub * 8
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -240,6 +247,29 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
         ctypes.c_void_p,  # host fp32 [n_load][n_cells] arrival rates
         ctypes.c_void_p,  # host fp32 [n_tgt][n_cells] TTFT targets
         ctypes.c_void_p,  # host fp32 [n_tgt][n_cells] ITL targets
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned fp32 [n_scen][6][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_scen][4][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][n_acc]
+    ]
+    # token-mix planning (engine/fastpath.py FastSweep.plan_tokens)
+    lib.wva_ctx_plan_tokens.restype = ctypes.c_int
+    lib.wva_ctx_plan_tokens.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_int,  # n_tok
+        ctypes.c_int,  # n_scen = n_tok * n_load (1..PLAN_MAX_S)
+        ctypes.c_int,  # n_acc
+        ctypes.c_void_p,  # host fp32 [n_load][n_cells] arrival rates
+        ctypes.c_void_p,  # host i32 [n_tok][n_cells] in_tok
+        ctypes.c_void_p,  # host i32 [n_tok][n_cells] out_tok
+        ctypes.c_void_p,  # host i32 [n_tok][n_cells] batch_n
+        ctypes.c_int,  # task buckets of the pass
+        ctypes.POINTER(ctypes.c_int),  # per bucket: block width
+        ctypes.POINTER(ctypes.c_void_p),  # device i32 task ids (null: every task)
+        ctypes.POINTER(ctypes.c_int),  # tasks
+        ctypes.POINTER(ctypes.c_int),  # largest N
+        ctypes.POINTER(ctypes.c_void_p),  # g_inv slabs (huge-N)
+        ctypes.POINTER(ctypes.c_void_p),  # g_anchor slabs
+        ctypes.POINTER(ctypes.c_int),  # tasks per launch (0: all)
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned fp32 [n_scen][6][n_srv]
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_scen][4][n_srv]
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][n_acc]
