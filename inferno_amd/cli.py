@@ -7,6 +7,7 @@ pkg/config wire format) and print the allocation solution.
       [--limited] [--capacity TYPE=N,...] [--saturation-policy P] [--delayed-best-effort]
   python -m inferno_amd.cli plan system.json --slo-scales 0.5,1,2 [--scales ...] [--json]
   python -m inferno_amd.cli plan system.json --rollout --scales 0.5,1,2,1,0.5 [--json]
+  python -m inferno_amd.cli plan system.json --hold --scales 0.5,1,2,4 [--json]
 """
 from __future__ import annotations
 
@@ -117,6 +118,13 @@ def cmd_plan(args) -> int:
     from .engine import FastSweep, SweepEngine
 
     limited = args.limited or args.capacity is not None
+    if args.hold:
+        if (limited or args.slo_scales is not None or args.token_scales is not None
+                or args.rollout):
+            raise SystemExit("plan: --hold evaluates the current allocation as it is; it does "
+                             "not combine with --slo-scales, --token-scales, --rollout, "
+                             "--limited or --capacity")
+        return _cmd_plan_hold(args)
     if args.token_scales is not None:
         if limited or args.slo_scales is not None or args.rollout:
             raise SystemExit("plan: --token-scales is an unlimited-mode plan; it does not "
@@ -350,6 +358,57 @@ def _cmd_plan_rollout(args) -> int:
     return 0
 
 
+def _cmd_plan_hold(args) -> int:
+    """Hold analysis: the current allocation, unchanged, at each load scale."""
+    from .engine import HOLD_OK, HOLD_STATUS_NAMES, FastSweep, SweepEngine
+
+    if args.scales is None:
+        raise SystemExit("plan: --hold needs --scales")
+    scales = _parse_scales(args.scales)
+    system, _ = _load_system(args.spec)
+    backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
+    fs = FastSweep(system, backend=backend)
+    try:
+        res = fs.hold(scales=scales)
+    except ValueError as e:
+        print(f"plan: {e}", file=sys.stderr)
+        return 2
+    rows = []
+    for s, scale in enumerate(scales):
+        rows.append({
+            "scale": scale,
+            "status": {n: int(res.counts[s, j]) for j, n in enumerate(HOLD_STATUS_NAMES)},
+            "deficit": {n: int(res.deficit_by_acc[s, j]) for j, n in enumerate(fs.acc_names)},
+            "notOk": [{
+                "server": fs.server_names[i],
+                "status": HOLD_STATUS_NAMES[res.status[s, i]],
+                "accelerator": fs.acc_names[res.acc_idx[s, i]] if res.acc_idx[s, i] >= 0 else "",
+                "heldReplicas": int(res.held_replicas[s, i]),
+                "neededReplicas": int(res.needed_replicas[s, i]),
+                # +inf (an overloaded server) has no JSON number
+                "itl": float(res.itl[s, i]) if res.itl[s, i] != float("inf") else None,
+                "ttft": float(res.ttft[s, i]) if res.ttft[s, i] != float("inf") else None,
+            } for i in range(len(fs.server_names)) if res.status[s, i] != HOLD_OK],
+        })
+    if args.json:
+        print(json.dumps({"backend": backend, "servers": len(fs.server_names), "hold": rows},
+                         indent=2))
+        return 0
+    for r in rows:
+        print(f"load scale {r['scale']:g}: "
+              + ", ".join(f"{n} {c}" for n, c in r["status"].items() if c)
+              + "; replicas short: "
+              + (", ".join(f"{n} {d}" for n, d in r["deficit"].items() if d) or "none"))
+        for b in r["notOk"]:
+            lat = ("" if b["itl"] is None
+                   else f" itl {b['itl']:.2f} ms ttft {b['ttft']:.2f} ms")
+            print(f"  {b['server']:<24} {b['status']:<12} {b['accelerator'] or '-':<12} "
+                  f"held {b['heldReplicas']} needed {b['neededReplicas']}{lat}")
+    print(f"({len(fs.server_names)} servers, backend {backend}; the current allocation is held "
+          "at every load scale)")
+    return 0
+
+
 def cmd_analyze(args) -> int:
     from .api import v1alpha1 as api
     from .controller.modelanalyzer import ModelAnalyzer
@@ -403,6 +462,9 @@ def main() -> None:
     pp.add_argument("--rollout", action="store_true",
                     help="forecast rollout: --scales are consecutive steps, each reconciled "
                          "against the allocation the step before it left behind")
+    pp.add_argument("--hold", action="store_true",
+                    help="hold analysis: the current allocation is not resized; per load scale "
+                         "the SLO verdict of every server, the replicas short by accelerator")
     pp.set_defaults(fn=cmd_plan)
     pa = sub.add_parser("analyze", help="per-variant candidate allocations")
     pa.add_argument("spec")

@@ -130,6 +130,47 @@ class RolloutResult:
     cells: Optional[dict] = None  # reconcile_cells() layout, arrays [S, n_cells]
 
 
+# Verdict of one (scenario, server) slice of a hold analysis (FastSweep.hold),
+# as ops/hip/wva_kernels.hip numbers them (WVA_HOLD_*), in order of precedence
+# NOT_HELD, IDLE, INVALID, OVERLOADED, then OK or SLO_VIOLATED.
+HOLD_OK = 0  # evaluated; the sizing is feasible and held >= needed replicas
+HOLD_SLO_VIOLATED = 1  # evaluated; fewer replicas than the SLO needs, or unreachable SLO
+HOLD_OVERLOADED = 2  # no replicas, or the per-replica rate is above the analyzer's range
+HOLD_NOT_HELD = 3  # the allocation names no accelerator the server has a cell on
+HOLD_IDLE = 4  # no arrivals or no output tokens
+HOLD_INVALID = 5  # degenerate service rates: no model of the cell
+HOLD_STATUS_NAMES = ("OK", "SLO_VIOLATED", "OVERLOADED", "NOT_HELD", "IDLE", "INVALID")
+_HOLD_FLOATS = ("itl", "ttft", "rho", "rate", "slo_rate", "cost")  # device row order
+_HOLD_INTS = ("status", "acc_idx", "held_replicas", "needed_replicas")
+# wva_ctx_plan_cells' ten arrays under the names a hold pass gives them
+_HOLD_CELL_KEYS = ("status", "held", "held_replicas", "needed_replicas", "cost", "slo_rate",
+                   "itl", "ttft", "rho", "rate")
+
+
+@dataclass
+class HoldResult:
+    """Hold analysis: what users see under S loads when the allocation does
+    not move (FastSweep.hold). Arrays are [S, n_servers] unless noted."""
+
+    status: np.ndarray  # int32, one of HOLD_*
+    acc_idx: np.ndarray  # int32: the held accelerator, -1 where NOT_HELD
+    held_replicas: np.ndarray  # int32: 0 where NOT_HELD
+    # int32: ceil(total rate / sized per-replica rate), not raised to
+    # min_replicas; 0 where IDLE; -1 where the SLO is unreachable on the held
+    # accelerator, and where NOT_HELD or INVALID
+    needed_replicas: np.ndarray
+    itl: np.ndarray  # float32 msec; +inf where OVERLOADED
+    ttft: np.ndarray  # float32 msec; +inf where OVERLOADED
+    rho: np.ndarray  # float32; 1 where OVERLOADED
+    rate: np.ndarray  # float32 req/s per held replica
+    slo_rate: np.ndarray  # float32 req/min the held replicas carry within the SLO
+    cost: np.ndarray  # float32: accelerator cost x held replicas
+    arrival: np.ndarray  # float32: the loads evaluated
+    counts: np.ndarray  # int64 [S, 6]: servers per status
+    deficit_by_acc: np.ndarray  # int64 [S, n_acc]: sum of max(needed - held, 0), needed >= 0
+    cells: Optional[dict] = None  # per-cell arrays [S, n_cells] of the same, plus cell metadata
+
+
 # Longest forecast one rollout() takes, and the steps one device pass of it
 # holds (at most PLAN_MAX_S): longer forecasts run as consecutive passes, each
 # starting from the allocation the one before it ended with.
@@ -737,6 +778,222 @@ class FastSweep:
             f: np.stack([getattr(r, f) for r in rows]) for f in _WINNER_FIELDS
         })
         return winners, cur
+
+    # ------------------------------------------------------------------
+    # Hold analysis
+    # ------------------------------------------------------------------
+    def hold(self, scales=None, arrival=None, allocation=None,
+             return_cells: bool = False) -> HoldResult:
+        """Evaluate a FIXED allocation under S arrival-rate scenarios in one
+        pass: the latency users see when the replicas do not follow the load
+        (a capped deployment, an autoscaler that lags a ramp, the headroom of
+        today's fleet). Every other pass resizes the fleet per scenario; this
+        one pins the replicas.
+
+        Load axis as for plan(): exactly one of ``scales`` and ``arrival``,
+        1 <= S <= 256. ``allocation`` None holds the current allocation (the
+        current-allocation override when set, else the server objects) in
+        every scenario; else it is ``(acc_idx, num_replicas)``, two integer
+        arrays of shape [n_servers] or [S, n_servers]. ``acc_idx`` >= 0 indexes
+        ``acc_names``; any negative value means "holds nothing", so a
+        WinnerRecord's -1 / -2 and a rollout's final_cur -1 / -3 pass straight
+        in. ``num_replicas`` >= 0 where an accelerator is named.
+
+        Per (scenario, server) the verdict is, in this order: HOLD_NOT_HELD
+        (no accelerator named, or the server has no cell on it), HOLD_IDLE
+        (zero arrival or no output tokens; latencies as the zero-load
+        allocation reports them), HOLD_INVALID (degenerate service rates),
+        HOLD_OVERLOADED (no replicas, or a per-replica rate the analyzer
+        refuses: latencies +inf, rho 1), else one analysis at total rate /
+        held replicas: HOLD_OK iff the SLO is reachable on the held
+        accelerator and held >= needed_replicas, else HOLD_SLO_VIOLATED. The
+        verdict compares integers, never latencies with targets.
+        ``rollout()`` says what the controller will do over a forecast f;
+        ``hold(arrival=f[1:], allocation=(r.winners.acc_idx[:-1],
+        r.winners.num_replicas[:-1]))`` says whether the SLO holds while it
+        catches up, under one tick of actuation lag.
+
+        On the GPU only the held cell of a server is evaluated, once per
+        scenario against one sizing (or its sizing-memo hit: the memo is shared
+        with reconcile(), one lookup per held and loaded cell and call). A
+        hold changes nothing a following reconcile() or plan returns and
+        leaves the server objects as they were."""
+        scen = self._plan_scenarios(scales, arrival, who="hold()")
+        acc, rep = self._hold_allocation(allocation, scen.shape[0])
+        n_scen, n_srv = scen.shape
+        n_acc = len(self.acc_names)
+        cells = None
+        if self.n_cells == 0 or n_acc == 0:
+            rec = _empty_hold(n_scen, n_srv)
+            counts = deficit = None
+        elif self.backend == "gpu":
+            self._tick(plan_arrival=scen, launch=False)  # stage + bucket layout
+            cs = self.cell_server
+            cell_scen = np.ascontiguousarray(scen[:, cs], dtype=np.float32)
+            cell_held = np.ascontiguousarray(
+                np.where(acc[:, cs] == self.cell_acc_idx[None, :], rep[:, cs], -1), dtype=np.int32)
+            hf, hi, counts, deficit = self._gpu.hold(cell_scen, cell_held, n_acc)
+            rec = {k: np.ascontiguousarray(hf[:, r]) for r, k in enumerate(_HOLD_FLOATS)}
+            rec.update({k: np.ascontiguousarray(hi[:, r]) for r, k in enumerate(_HOLD_INTS)})
+            if return_cells:
+                raw = self._gpu.plan_cells(n_scen)
+                cells = self._with_cell_meta(
+                    {new: raw[old] for new, old in zip(_HOLD_CELL_KEYS, CELL_KEYS)})
+        else:
+            rec = self._hold_cpu(scen, acc, rep)
+            counts = deficit = None
+        if counts is None:
+            counts, deficit = _hold_sums(rec, n_acc)
+        return HoldResult(arrival=scen, counts=counts, deficit_by_acc=deficit, cells=cells, **rec)
+
+    def _hold_allocation(self, allocation, n_scen: int):
+        """Validate hold()'s allocation and return (acc_idx, num_replicas) as
+        int32 [S, n_servers]: acc_idx -1 wherever nothing is held (replicas 0
+        there)."""
+        n_srv = len(self.server_names)
+        if allocation is None:
+            cur_acc, cur_rep, _ = self._base_cur()
+            raw = [np.asarray(cur_acc), np.asarray(cur_rep)]
+        else:
+            try:
+                a, r = allocation
+                raw = [np.asarray(a), np.asarray(r)]
+                [x.astype(np.float64) for x in raw]
+            except (TypeError, ValueError) as e:
+                raise ValueError(
+                    "allocation is not an (acc_idx, num_replicas) pair of integer arrays: "
+                    f"{e}") from None
+        vals = []
+        for x, what in zip(raw, ("acc_idx", "num_replicas")):
+            v = x.astype(np.float64)
+            if v.shape not in ((n_srv,), (n_scen, n_srv)):
+                raise ValueError(
+                    f"allocation {what} must have shape [{n_srv}] or [{n_scen}, {n_srv}], "
+                    f"got {v.shape}")
+            if x.dtype.kind not in "iu" and not (np.isfinite(v).all() and (v == np.floor(v)).all()):
+                raise ValueError(f"allocation {what} must hold integers")
+            vals.append(np.broadcast_to(v, (n_scen, n_srv)))
+        acc, rep = vals
+        if (acc >= len(self.acc_names)).any():
+            raise ValueError(
+                f"allocation acc_idx must be below {len(self.acc_names)} (acc_names), "
+                f"got {int(acc.max())}")
+        on = acc >= 0
+        if (rep[on] < 0).any():
+            raise ValueError("allocation num_replicas must be non-negative where acc_idx >= 0")
+        if (rep[on] > np.iinfo(np.int32).max).any():
+            raise ValueError("allocation num_replicas must fit int32")
+        return (np.ascontiguousarray(np.where(on, acc, -1), dtype=np.int32),
+                np.ascontiguousarray(np.where(on, rep, 0), dtype=np.int32))
+
+    def _hold_cpu(self, scen: np.ndarray, acc: np.ndarray, rep: np.ndarray) -> dict:
+        """Golden path: per (scenario, server) the held cell's analyzer built
+        as core/allocation.py builds it (M/G/1 mode included), size() for the
+        sized rate and the needed replicas, analyze() at total rate / held
+        replicas for the latencies, its refusal of the rate mapped to
+        OVERLOADED. Reads the server objects and changes none."""
+        from ..analyzer import (AnalyzerError, Configuration, DecodeParms, PrefillParms,
+                                QueueAnalyzer, RequestSize, ServiceParms, TargetPerf)
+        from ..config import MAX_QUEUE_TO_BATCH_RATIO
+
+        system = self.system
+        n_scen, n_srv = scen.shape
+        rec = _empty_hold(n_scen, n_srv)
+        _, in_tok, out_tok = self._base_load()
+        targets, _ = self._server_targets()
+        cell_of = {(int(self.cell_server[k]), int(self.cell_acc_idx[k])): k
+                   for k in range(self.n_cells)}
+        st = self._stat
+        f32 = np.float32
+        sized = {}  # cell -> (analyzer or None, sized rate req/s or None)
+
+        def analyzer(k, i):
+            if k in sized:
+                return sized[k]
+            server = self._srv_objs[i]
+            acc_name = self.acc_names[self.cell_acc_idx[k]]
+            perf = system.models[server.model_name].get_perf_data(acc_name)
+            K = int(out_tok[i])
+            N = server.max_batch_size if server.max_batch_size > 0 else max(
+                perf.maxBatchSize * perf.atTokens // K, 1)
+            cfg = Configuration(
+                max_batch_size=N, max_queue_size=N * MAX_QUEUE_TO_BATCH_RATIO,
+                service_parms=ServiceParms(
+                    prefill=PrefillParms(gamma=perf.prefillParms.gamma,
+                                         delta=perf.prefillParms.delta),
+                    decode=DecodeParms(alpha=perf.decodeParms.alpha, beta=perf.decodeParms.beta)),
+            )
+            req = RequestSize(avg_input_tokens=int(in_tok[i]), avg_output_tokens=K)
+            qa = rate_star = None
+            try:
+                if getattr(system, "analyzer_mode", "mm1k") == "mg1":
+                    from ..analyzer.mg1 import MG1QueueEvaluator
+
+                    qa = MG1QueueEvaluator(cfg, req, cv2=getattr(system, "analyzer_cv2", 1.0))
+                else:
+                    qa = QueueAnalyzer(cfg, req)
+            except AnalyzerError:
+                pass
+            if qa is not None:
+                t = targets[i]
+                try:
+                    _, metrics, _ = qa.size(TargetPerf(target_ttft=t.ttft, target_itl=t.itl,
+                                                       target_tps=t.tps))
+                    rate_star = metrics.throughput
+                except AnalyzerError:
+                    pass
+            sized[k] = (qa, rate_star)
+            return sized[k]
+
+        for s in range(n_scen):
+            for i in range(n_srv):
+                k = cell_of.get((i, int(acc[s, i]))) if acc[s, i] >= 0 else None
+                if k is None:
+                    continue  # NOT_HELD
+                at = (s, i)
+                held = int(rep[s, i])
+                rec["acc_idx"][at] = acc[s, i]
+                rec["held_replicas"][at] = held
+                rec["cost"][at] = f32(st["acc_cost"][k]) * f32(held)
+                arr, K = float(scen[s, i]), int(out_tok[i])
+                if arr == 0 or K == 0:
+                    rec["status"][at] = HOLD_IDLE
+                    rec["needed_replicas"][at] = 0
+                    if st["min_replicas"][k] != 0:
+                        rec["itl"][at] = f32(st["alpha"][k]) + f32(st["beta"][k])
+                        rec["ttft"][at] = f32(st["gamma"][k]) + f32(st["delta"][k])
+                    continue
+                qa, rate_star = analyzer(k, i)
+                if qa is None:
+                    rec["status"][at] = HOLD_INVALID
+                    continue
+                tps = targets[i].tps
+                total_rate = arr / 60.0 if tps == 0 else tps / float(K)
+                if rate_star is not None:
+                    with np.errstate(all="ignore"):
+                        reps_d = np.ceil(np.float64(total_rate) / np.float64(rate_star))
+                    reps_d = float(reps_d) if reps_d > 0.0 else 0.0
+                    rec["needed_replicas"][at] = int(min(reps_d, 2147483000.0))
+                    rec["slo_rate"][at] = f32(rate_star * float(held) * 60.0)
+                metrics = None
+                if held > 0 and total_rate / float(held) <= qa.rate_max:
+                    try:
+                        metrics = qa.analyze(total_rate / float(held))
+                    except AnalyzerError:
+                        pass
+                if held > 0:
+                    rec["rate"][at] = f32(total_rate / float(held))
+                if metrics is None:
+                    rec["status"][at] = HOLD_OVERLOADED
+                    rec["itl"][at] = rec["ttft"][at] = np.inf
+                    rec["rho"][at] = 1.0
+                    continue
+                rec["itl"][at] = metrics.avg_token_time
+                rec["ttft"][at] = metrics.avg_wait_time + metrics.avg_prefill_time
+                rec["rho"][at] = metrics.rho
+                ok = rate_star is not None and held >= rec["needed_replicas"][at]
+                rec["status"][at] = HOLD_OK if ok else HOLD_SLO_VIOLATED
+        return rec
 
     # ------------------------------------------------------------------
     # What-if SLO planning
@@ -1366,6 +1623,32 @@ def _acc_changes(start_acc: np.ndarray, acc_idx: np.ndarray) -> np.ndarray:
                      start_acc[None, :])
     before = np.concatenate([start_acc[None, :], after[:-1]])
     return (after != before).sum(axis=1).astype(np.int64)
+
+
+def _empty_hold(n_scen: int, n_srv: int) -> dict:
+    """The per-server arrays of a HoldResult with every slice NOT_HELD."""
+    shape = (n_scen, n_srv)
+    rec = {k: np.zeros(shape, dtype=np.float32) for k in _HOLD_FLOATS}
+    rec["status"] = np.full(shape, HOLD_NOT_HELD, dtype=np.int32)
+    rec["acc_idx"] = np.full(shape, -1, dtype=np.int32)
+    rec["held_replicas"] = np.zeros(shape, dtype=np.int32)
+    rec["needed_replicas"] = np.full(shape, -1, dtype=np.int32)
+    return rec
+
+
+def _hold_sums(rec: dict, n_acc: int):
+    """(counts int64 [S, 6], deficit_by_acc int64 [S, n_acc]) of the per-server
+    arrays of a hold analysis."""
+    n_scen = rec["status"].shape[0]
+    counts = np.stack([np.bincount(rec["status"][s], minlength=len(HOLD_STATUS_NAMES))
+                       for s in range(n_scen)]).astype(np.int64)
+    deficit = np.zeros((n_scen, n_acc), dtype=np.int64)
+    need = rec["needed_replicas"].astype(np.int64)
+    short = np.maximum(need - rec["held_replicas"].astype(np.int64), 0)
+    on = (rec["status"] != HOLD_NOT_HELD) & (need >= 0) & (rec["acc_idx"] >= 0)
+    for s in range(n_scen):
+        np.add.at(deficit[s], rec["acc_idx"][s][on[s]], short[s][on[s]])
+    return counts, deficit
 
 
 def _empty_winner(n: int) -> WinnerRecord:

@@ -429,6 +429,29 @@ class NativeCtx:
             (end[0], end[1], end[2].view(np.float32)),
         )
 
+    def hold(self, cell_scen: np.ndarray, cell_held: np.ndarray, n_acc: int):
+        """wva_ctx_hold on [S, n_cells] fp32 arrivals and int32 held replicas
+        (-1: the scenario's allocation is not on the cell; the tick is staged
+        and the buckets are set): fp32 [S, 6, n_srv] (itl, ttft, rho, rate,
+        slo_rate, cost), int32 [S, 4, n_srv] (status, accelerator, held,
+        needed), int64 status counts [S, 6] and int64 deficits [S, n_acc]."""
+        n_scen = cell_scen.shape[0]
+        if cell_held.shape != cell_scen.shape or cell_held.dtype != np.int32:
+            raise ValueError("held replicas must be int32 of the arrivals' shape")
+        out = [ctypes.c_void_p() for _ in range(4)]
+        rc = self._lib.wva_ctx_hold(
+            self.ctx, n_scen, n_acc, cell_scen.ctypes.data, cell_held.ctypes.data,
+            *[ctypes.byref(p) for p in out],
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_hold failed: {rc}")
+        return (
+            _copy_out(out[0], ctypes.c_float, (n_scen, 6, self.n_srv)),
+            _copy_out(out[1], ctypes.c_int32, (n_scen, 4, self.n_srv)),
+            _copy_out(out[2], ctypes.c_uint64, (n_scen, 6)).astype(np.int64),
+            _copy_out(out[3], ctypes.c_uint64, (n_scen, n_acc)).astype(np.int64),
+        )
+
     def plan_cells(self, n_scen: int) -> dict:
         """Per-cell outputs [S, n_cells] of the planning pass that just ran."""
         cells = {k: np.empty((n_scen, self.n_cells), dtype=d)

@@ -136,6 +136,12 @@ struct WvaCtx {
   int *tok_pin_in;   // pinned mirrors
   int *tok_pin_out;
   int *tok_pin_n;
+  // hold analysis (wva_ctx_hold): the per-cell held replicas of every
+  // scenario, allocated on first use, grown to the largest scenario count
+  // seen, freed in destroy
+  int hold_cap;      // scenarios the buffers hold (0 = not allocated)
+  void *hold_dev;    // device i32 [S][n_cells]: -1 not held, >= 0 held replicas
+  void *hold_pin;    // its pinned source
   // forecast rollout (wva_ctx_rollout): the per-server current allocation the
   // chain starts from and ends with, three rows of n_srv words (cur_acc,
   // cur_rep, cur_cost). Allocated on first use, freed in destroy.
@@ -649,12 +655,14 @@ extern "C" int wva_ctx_set_buckets(void *ctx, int n_buckets, const int *nts,
 // per-cell results; `plan` (may be null) selects the planning kernels, `slo`
 // (may be null) the SLO-planning ones. With `tok` (token-mix planning) the
 // buckets hold tasks, `in` is the view with the [W][n_cells] token rows, and
-// the sizing memo stays out of it. Enqueues only —
+// the sizing memo stays out of it. `hold` (may be null) selects the hold
+// kernels on the context's buckets, sizing memo included. Enqueues only —
 // no synchronising call, since the reconcile pipeline runs under stream
 // capture.
 static int wva_run_buckets(WvaCtx *c, const WvaBucket *buckets, int n_buckets,
                            const WvaCellsIn &in, const WvaCellsOut &out, const WvaPlanArgs *plan,
-                           const WvaSloArgs *slo = nullptr, const WvaTokArgs *tok = nullptr) {
+                           const WvaSloArgs *slo = nullptr, const WvaTokArgs *tok = nullptr,
+                           const WvaHoldArgs *hold = nullptr) {
   if (n_buckets < 0 || n_buckets > WVA_MAX_BUCKETS) return -1;
   WvaMemoRec *memo = tok != nullptr ? nullptr : c->memo;
   unsigned *memo_cnt = tok != nullptr ? nullptr : c->memo_cnt;
@@ -671,7 +679,7 @@ static int wva_run_buckets(WvaCtx *c, const WvaBucket *buckets, int n_buckets,
       const int n = b.n_blocks - at < step ? b.n_blocks - at : step;
       const int rc = wva_sweep_dispatch(n, b.max_n, b.nt, b.cell_ids ? b.cell_ids + at : nullptr,
                                         c->analyzer_mode, c->cv2, s, in, out, b.g_inv,
-                                        b.g_anchor, memo, memo_cnt, plan, slo, tok);
+                                        b.g_anchor, memo, memo_cnt, plan, slo, tok, hold);
       if (rc != 0) return rc;
     }
     if (i > 0 && hipEventRecord(c->e_b[i - 1], s) != hipSuccess) return -12;
@@ -979,6 +987,22 @@ static int wva_tok_reserve(WvaCtx *c, int n_tok) {
   return 0;
 }
 
+static void wva_hold_release(WvaCtx *c) {
+  wva_arena_free(c->hold_dev, c->hold_pin);
+  c->hold_cap = 0;
+}
+
+// (re)allocate the hold analysis' held-replica array for n_scen scenarios; on
+// failure nothing is held and reconciles and the other plans keep working
+static int wva_hold_reserve(WvaCtx *c, int n_scen) {
+  if (n_scen <= c->hold_cap) return 0;
+  wva_hold_release(c);
+  const size_t bytes = (size_t)n_scen * (size_t)c->n_cells * sizeof(int);
+  if (!wva_arena_alloc(c, bytes, bytes, false, &c->hold_dev, &c->hold_pin)) return -39;
+  c->hold_cap = n_scen;
+  return 0;
+}
+
 // the rollout's current-allocation rows; on failure nothing is held and
 // reconciles and plans keep working
 static int wva_roll_reserve(WvaCtx *c) {
@@ -1089,6 +1113,10 @@ extern "C" int wva_ctx_set_greedy_static(void *ctx, const int *cell_type, const 
 // n_scen / n_tok arrival-rate scenarios, set-major: the token sets go up next
 // to the arrivals and step 2 launches the token-mix kernels over the pass's
 // own bucket list of tasks; the context's buckets are not read or changed.
+//
+// With hold (wva_ctx_hold) the held replicas go up next to the arrivals, step
+// 2 launches the hold kernels, step 3 is wva_hold_reduce, and the totals block
+// holds the status counts and the deficits; everything else is the same pass.
 struct WvaLimArgs {
   int n_types;
   const int *capacity;  // host [n_scen][n_types]
@@ -1113,20 +1141,33 @@ struct WvaTokSets {
   const WvaBucket *buckets;  // the pass's task buckets
   int n_buckets;
 };
+struct WvaHoldIn {
+  const int *scen_held;  // host [n_scen][n_cells]: -1 not held, >= 0 held replicas
+};
 
 static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arrival,
                         const WvaLimArgs *lim, const void **out_pf, const void **out_pi,
                         const void **out_totals, const WvaSloTargets *slo = nullptr,
-                        const WvaRollArgs *roll = nullptr, const WvaTokSets *tok = nullptr) {
+                        const WvaRollArgs *roll = nullptr, const WvaTokSets *tok = nullptr,
+                        const WvaHoldIn *hold = nullptr) {
   if (c == nullptr || scen_arrival == nullptr) return -31;
   if (n_scen < 1 || n_scen > WVA_PLAN_MAX_S || n_acc < 1) return -32;
+  if (hold != nullptr && (lim != nullptr || slo != nullptr || roll != nullptr || tok != nullptr))
+    return -32;
+  // words per scenario of the totals block: the replica totals, or a hold's
+  // status counts followed (after all scenarios' counts) by its deficits
+  const int n_tot = hold != nullptr ? n_acc + WVA_HOLD_STATUSES : n_acc;
   if (slo != nullptr && (slo->n_tgt < 1 || n_scen % slo->n_tgt != 0)) return -32;
   if (tok != nullptr && (slo != nullptr || tok->n_tok < 1 || n_scen % tok->n_tok != 0))
     return -32;
   if (c->n_cells <= 0 || c->n_srv <= 0) return -33;
   c->plan_s = 0;
-  int rc = wva_plan_reserve(c, n_scen, n_acc);
+  int rc = wva_plan_reserve(c, n_scen, n_tot);
   if (rc != 0) return rc;
+  if (hold != nullptr) {
+    rc = wva_hold_reserve(c, n_scen);
+    if (rc != 0) return rc;
+  }
   if (slo != nullptr) {
     rc = wva_slo_reserve(c, slo->n_tgt);
     if (rc != 0) return rc;
@@ -1157,6 +1198,12 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   err = hipMemcpyAsync(c->plan_scen, c->plan_pin_scen, cells * sizeof(float),
                        hipMemcpyHostToDevice, c->s0);
   if (err != hipSuccess) return (int)err;
+  if (hold != nullptr) {
+    memcpy(c->hold_pin, hold->scen_held, cells * sizeof(int));
+    err = hipMemcpyAsync(c->hold_dev, c->hold_pin, cells * sizeof(int), hipMemcpyHostToDevice,
+                         c->s0);
+    if (err != hipSuccess) return (int)err;
+  }
   if (slo != nullptr) {
     const size_t tcells = (size_t)slo->n_tgt * (size_t)c->n_cells;
     for (size_t i = 0; i < tcells; ++i) {
@@ -1186,7 +1233,7 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   err = hipMemcpyAsync(c->dev_dyn, c->pin_dyn, (size_t)WVA_DYN_ROWS * c->n_cells * 4,
                        hipMemcpyHostToDevice, c->s0);
   if (err != hipSuccess) return (int)err;
-  err = hipMemsetAsync(c->plan_tot, 0, (size_t)n_scen * n_acc * sizeof(unsigned long long),
+  err = hipMemsetAsync(c->plan_tot, 0, (size_t)n_scen * n_tot * sizeof(unsigned long long),
                        c->s0);
   if (err != hipSuccess) return (int)err;
   const size_t b_cur = (size_t)3 * (size_t)c->n_srv * sizeof(int);
@@ -1209,7 +1256,11 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   }
 
   // 2. planning buckets: same streams, fork/join and order as the reconcile
-  if (tok != nullptr) {
+  if (hold != nullptr) {
+    const WvaHoldArgs ha = {c->n_cells, n_scen, c->plan_scen, (const int *)c->hold_dev};
+    rc = wva_run_buckets(c, c->buckets, c->n_buckets, c->in, c->plan_out, nullptr, nullptr,
+                         nullptr, &ha);
+  } else if (tok != nullptr) {
     // the pass's own task buckets on a view of the inputs whose token rows
     // are the [W][n_cells] arrays; the context's layout is left alone
     WvaCellsIn tin = c->in;
@@ -1231,7 +1282,18 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
 
   // 3. winners, records and totals for all (server, scenario) pairs; a
   // rollout's scenarios are consecutive steps, chained per server
-  if (roll != nullptr) {
+  if (hold != nullptr) {
+    // the held cell's slice per (server, scenario); counts [n_scen][6], then
+    // deficit [n_scen][n_acc], in the totals block
+    const int per_block = WVA_WAVE / c->roll_group;
+    hipLaunchKernelGGL(wva_hold_reduce, dim3((c->n_srv + per_block - 1) / per_block, n_scen),
+                       dim3(WVA_WAVE), 0, c->s0, c->plan_out.feasible, c->plan_out.zero_empty,
+                       c->cell_acc, c->plan_out.num_replicas, c->plan_out.batch, c->plan_out.cost,
+                       c->plan_out.value, c->plan_out.itl, c->plan_out.ttft, c->plan_out.rho,
+                       c->plan_out.max_rate, c->seg_start, c->n_srv, c->n_cells, n_scen, n_acc,
+                       c->roll_group, c->plan_pf, c->plan_pi, c->plan_tot,
+                       c->plan_tot + (size_t)n_scen * WVA_HOLD_STATUSES);
+  } else if (roll != nullptr) {
     const int per_block = WVA_WAVE / c->roll_group;
     hipLaunchKernelGGL(wva_rollout, dim3((c->n_srv + per_block - 1) / per_block), dim3(WVA_WAVE),
                        0, c->s0, c->plan_out.value, c->plan_out.feasible, c->plan_out.zero_empty,
@@ -1285,7 +1347,7 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
                        hipMemcpyDeviceToHost, c->s0);
   if (err != hipSuccess) return (int)err;
   err = hipMemcpyAsync(c->plan_pin_tot, c->plan_tot,
-                       (size_t)n_scen * n_acc * sizeof(unsigned long long),
+                       (size_t)n_scen * n_tot * sizeof(unsigned long long),
                        hipMemcpyDeviceToHost, c->s0);
   if (err != hipSuccess) return (int)err;
   err = hipStreamSynchronize(c->s0);
@@ -1425,6 +1487,37 @@ extern "C" int wva_ctx_plan_tokens(void *ctx, int n_tok, int n_scen, int n_acc,
                       nullptr, nullptr, &tok);
 }
 
+// One hold-analysis pass: the latency a fixed allocation gives under n_scen
+// loads. wva_ctx_plan's staging, uploads, buckets, streams and output arena,
+// with wva_hold_t instead of wva_plan_t and wva_hold_reduce instead of
+// wva_plan_reduce. scen_arrival: host [n_scen][n_cells] fp32 (req/min);
+// scen_held: host [n_scen][n_cells] int32, -1 where the scenario's allocation
+// is not on the cell, else the replicas held there (at most one cell per
+// server and scenario). The out pointers name pinned buffers valid until the
+// next planning pass: hf [n_scen][6][n_srv] fp32 (itl, ttft, rho, rate,
+// slo_rate, cost), hi [n_scen][4][n_srv] i32 (status, accelerator, held,
+// needed), counts [n_scen][6] u64 (servers per status) and deficit [n_scen]
+// [n_acc] u64. wva_ctx_plan_cells works on the result: the ten arrays carry
+// the hold meanings (status, held flag, held, needed, cost, slo_rate, itl,
+// ttft, rho, rate). The reconcile layout, the fused tick's task table, done[]
+// and the captured graph are not touched. -39: the held array could not be
+// allocated (the context is intact).
+extern "C" int wva_ctx_hold(void *ctx, int n_scen, int n_acc, const float *scen_arrival,
+                            const int *scen_held, const void **out_hf, const void **out_hi,
+                            const void **out_counts, const void **out_deficit) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || scen_held == nullptr) return -31;
+  const WvaHoldIn hold = {scen_held};
+  const void *tot = nullptr;
+  const int rc = wva_plan_run(c, n_scen, n_acc, scen_arrival, nullptr, out_hf, out_hi, &tot,
+                              nullptr, nullptr, nullptr, &hold);
+  if (rc != 0) return rc;
+  if (out_counts) *out_counts = tot;
+  if (out_deficit)
+    *out_deficit = (const unsigned long long *)tot + (size_t)n_scen * WVA_HOLD_STATUSES;
+  return 0;
+}
+
 // Per-cell outputs of the last successful wva_ctx_plan, copied into ten host
 // arrays of plan_s * n_cells elements each, in WvaCellsOut order (feasible,
 // zero_empty: u8; num_replicas, batch: i32; cost, value, itl, ttft, rho,
@@ -1462,6 +1555,7 @@ extern "C" void wva_ctx_destroy(void *ctx) {
   wva_plan_release(c);
   wva_slo_release(c);
   wva_tok_release(c);
+  wva_hold_release(c);
   wva_lim_release(c);
   wva_arena_free(c->roll_dev, c->roll_pin);
   if (c->lim_static != nullptr) (void)hipFree(c->lim_static);

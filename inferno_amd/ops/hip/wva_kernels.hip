@@ -52,6 +52,11 @@
 //       (token-mix planning), one block per (set, cell) at the width the cell
 //       has under that set.
 //
+//       And as wva_hold_t<NT>: a FIXED allocation under S scenarios (hold
+//       analysis): the replicas are pinned per (cell, scenario), the slice is a
+//       verdict with the latencies; K4d wva_hold_reduce picks each server's
+//       held cell and sums the verdicts and the replica deficits.
+//
 //   K4 wva_plan_reduce: per (server, scenario) K2's selection, the winner
 //       record and the per-accelerator replica totals, in one launch.
 //
@@ -865,10 +870,23 @@ struct WvaSloArgs {
 #define WVA_MODE_SWEEP 0  // the cell's own targets and arrival rate
 #define WVA_MODE_PLAN 1   // the cell's own targets, n_scen arrival rates
 #define WVA_MODE_SLO 2    // n_tgt target sets x n_load arrival rates
+#define WVA_MODE_HOLD 3   // the cell's own targets, n_scen (arrival rate, held replicas) pairs
+// Hold analysis: the load plan's arguments plus the replicas the cell holds in
+// every scenario. The replica count is pinned, not derived (wva_hold_body).
+struct WvaHoldArgs {
+  int n_cells;
+  int n_scen;
+  const float *scen_arrival;  // device, [n_scen][n_cells]
+  const int *scen_held;       // device, [n_scen][n_cells]: -1 = not held in this
+                              // scenario, >= 0 = held replicas
+};
 template <int MODE>
 using WvaPlanParam = typename std::conditional<
     MODE == WVA_MODE_PLAN, WvaPlanArgs,
-    typename std::conditional<MODE == WVA_MODE_SLO, WvaSloArgs, WvaNoPlan>::type>::type;
+    typename std::conditional<
+        MODE == WVA_MODE_SLO, WvaSloArgs,
+        typename std::conditional<MODE == WVA_MODE_HOLD, WvaHoldArgs, WvaNoPlan>::type>::type>::
+    type;
 
 // The SLO sizing of one cell under targets (t_ttft, t_itl): the concurrent
 // TTFT+ITL bisections (ref queueanalyzer.go:185-255), the minimum of the sized
@@ -988,6 +1006,26 @@ struct WvaView<WVA_MODE_SLO> {
         base = t;
     return base;
   }
+};
+// Hold analysis: the load plan's view plus held(s), the replicas the cell holds
+// under load s (-1: the allocation of scenario s does not name this cell).
+template <>
+struct WvaView<WVA_MODE_HOLD> {
+  const WvaHoldArgs &p;
+  const int cell;
+  const float own_ttft, own_itl;
+  __device__ WvaView(const WvaCellsIn &in, const WvaHoldArgs &p, int cell)
+      : p(p), cell(cell), own_ttft(in.t_ttft[cell]), own_itl(in.t_itl[cell]) {}
+  __device__ static constexpr WvaOne n_tgt() { return {}; }
+  __device__ int n_load() const { return p.n_scen; }
+  __device__ float ttft(int) const { return own_ttft; }
+  __device__ float itl(int) const { return own_itl; }
+  __device__ size_t slot(int, int s) const {
+    return (size_t)s * (size_t)p.n_cells + (size_t)cell;
+  }
+  __device__ float arrival(int s) const { return p.scen_arrival[slot(0, s)]; }
+  __device__ int held(int s) const { return p.scen_held[slot(0, s)]; }
+  __device__ int memo_tgt() const { return 0; }
 };
 
 // (thread 0 only) the "no allocation on this accelerator" verdict of target
@@ -1440,6 +1478,277 @@ __global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
 }
 
 // ---------------------------------------------------------------------------
+// Hold analysis, K1 as wva_hold_t<NT>: what latency a FIXED allocation gives
+// under n_scen loads. Scenario s pins the cell's replica count to held(s)
+// (-1: the allocation of scenario s is not on this cell) where the other modes
+// derive it from the sizing, and the slice gets a verdict instead of a
+// candidate allocation. The ten output arrays keep their types and take the
+// hold meanings:
+//   feasible   -> status (WVA_HOLD_*)        zero_empty -> 1 = the cell is held
+//   num_replicas -> held replicas            batch      -> needed replicas
+//   cost  -> acc_cost * held                 value      -> slo_rate (req/min)
+//   itl, ttft, rho                           max_rate   -> rate (req/s per replica)
+//
+// A sibling of wva_cell_body, not a fourth `if constexpr` arm inside it: the
+// sequence differs at every step but the shared ones (wva_build_geom, the
+// guard, wva_size_cell, wva_evaluate), and the existing kernels keep their
+// registers, scratch and occupancy only if their body is left alone
+// (docs/design/kernels.md, "Hold analysis").
+//
+// Per slice, in this order of precedence:
+//   NOT_HELD   held(s) < 0: floats 0, needed -1;
+//   IDLE       arrival(s) == 0 or out_tok == 0: itl / ttft / rho as
+//              wva_write_zero reports them for the cell, needed 0;
+//   INVALID    the degenerate-rate guard fires: no evaluation;
+//   OVERLOADED held(s) == 0, or the per-replica rate total_rate / held / 1000
+//              is above lam_max (the golden's analyze() refuses it): no
+//              evaluation, itl = ttft = +inf, rho = 1;
+//   else one wva_evaluate<NT, 1> at that rate, itl / ttft / rho exactly as
+//   wva_eval_scenario computes them; OK iff the sizing is feasible and
+//   held >= needed = ceil(total_rate / rate_star) (NOT raised to
+//   min_replicas; -1 when the sizing is infeasible), else SLO_VIOLATED. The
+//   verdict is on integers: the bisection's tolerance never decides it.
+//
+// The steps: (1) a cell that no scenario both holds and loads writes its
+// slices from thread 0 and returns before the memo, the geometry or any
+// barrier; (2) memo lookup as plan mode (same key, one counter move per cell
+// that gets here), but an infeasible hit does not return: the geometry is
+// still needed to evaluate; (3) geometry; (4) guard; (5) wva_size_cell or the
+// memo's word, miss stores as in wva_cell_body, so a hold warms the memo for a
+// reconcile and a reconcile for a hold; (6) per load the slice above.
+//
+// Uniformity: held(s) and arrival(s) depend on (cell, s) only, total_rate on
+// (cell, s), lam_max and the sizing on the cell, so the early exit, the guard
+// exit and every branch of the per-load step are taken by all threads of the
+// cell or by none, and the barrier argument of wva_cell_body's plan loop
+// carries over: every barrier inside wva_size_cell and wva_evaluate is executed
+// by all threads of a multi-wave cell, a one-wave cell executes none. Loop
+// bounds are n_scen. No polling, no cross-block traffic. Outputs and the memo
+// record are stored by thread 0 only.
+// ---------------------------------------------------------------------------
+#define WVA_HOLD_OK 0
+#define WVA_HOLD_SLO_VIOLATED 1
+#define WVA_HOLD_OVERLOADED 2
+#define WVA_HOLD_NOT_HELD 3
+#define WVA_HOLD_IDLE 4
+#define WVA_HOLD_INVALID 5
+#define WVA_HOLD_STATUSES 6
+
+// (thread 0 only) one slice record
+__device__ __forceinline__ void wva_hold_write(const WvaCellsOut &out, size_t o, int status,
+                                               int held, int needed, float cost, float slo_rate,
+                                               float itl, float ttft, float rho, float rate) {
+  out.feasible[o] = (uint8_t)status;
+  out.zero_empty[o] = status != WVA_HOLD_NOT_HELD;
+  out.num_replicas[o] = held;
+  out.batch[o] = needed;
+  out.cost[o] = cost;
+  out.value[o] = slo_rate;
+  out.itl[o] = itl;
+  out.ttft[o] = ttft;
+  out.rho[o] = rho;
+  out.max_rate[o] = rate;
+}
+
+// (thread 0 only) a slice that needs no model of the cell: NOT_HELD, or IDLE
+// with wva_write_zero's latencies (none for a server that may scale to zero,
+// else the batch-1 decode and prefill times)
+__device__ __forceinline__ void wva_hold_write_quiet(const WvaCellsOut &out, size_t o, int held,
+                                                     const WvaCell &c) {
+  if (held < 0) {
+    wva_hold_write(out, o, WVA_HOLD_NOT_HELD, 0, -1, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f);
+  } else {
+    const bool none = c.min_rep == 0;
+    wva_hold_write(out, o, WVA_HOLD_IDLE, held, 0, c.acc_cost * (float)held, 0.0f,
+                   none ? 0.0f : c.alpha + c.beta, none ? 0.0f : c.gamma + c.delta, 0.0f, 0.0f);
+  }
+}
+
+// The verdict and the per-replica analysis of one held, loaded slice: `held`
+// replicas (>= 0) at arrival rate arr (req/min, not 0), written to slot o.
+// rate_star is the sized per-replica rate (req/sec), meaningful when feasible.
+// total_rate, the clamps of `needed`, the per-replica rate and the latency
+// arithmetic are wva_eval_scenario's, with the replica count given instead of
+// derived. Every thread of the block calls this with the same arguments.
+template <int NT, typename SlotT>
+__device__ __forceinline__ void wva_hold_scenario(const WvaCellsOut &out, SlotT o, float arr,
+                                                  int held, bool feasible, double rate_star,
+                                                  const WvaCell &c, const WvaModel &m) {
+  double total_rate;  // req/sec (ref allocation.go:134-139)
+  if (c.t_tps == 0.0f)
+    total_rate = (double)arr / 60.0;
+  else
+    total_rate = (double)c.t_tps / (double)c.out_tok;
+  int needed = -1;
+  if (feasible) {
+    double reps_d = ceil(total_rate / rate_star);
+    if (!(reps_d > 0.0)) reps_d = 0.0;
+    if (reps_d > 2147483000.0) reps_d = 2147483000.0;
+    needed = (int)reps_d;
+  }
+  const float cost = c.acc_cost * (float)held;
+  const float slo_rate = feasible ? (float)(rate_star * (double)held * 60.0) : 0.0f;
+
+  // ---- per-replica analyze (ref allocation.go:148-157), unless the analyzer
+  // refuses the rate (ref queueanalyzer.go:134-140)
+  const double rate = total_rate / (double)held;
+  if (held == 0 || !(rate / 1000.0 <= m.lam_max)) {  // uniform over the cell
+    if (m.tid == 0)
+      wva_hold_write(out, o, WVA_HOLD_OVERLOADED, held, needed, cost, slo_rate, INFINITY, INFINITY,
+                     1.0f, held == 0 ? 0.0f : (float)rate);
+    return;
+  }
+  const WvaEval e = wva_evaluate<NT, 1>(rate / 1000.0, c, m);
+  const float prefill_t = prefill_time_f(c.gamma, c.delta, c.in_tok, (float)e.eff);
+  const float token_t = decode_time_f(c.alpha, c.beta, (float)e.eff);
+  if (m.tid == 0)
+    wva_hold_write(out, o,
+                   (feasible && held >= needed) ? WVA_HOLD_OK : WVA_HOLD_SLO_VIOLATED, held,
+                   needed, cost, slo_rate, token_t, (float)e.wait + prefill_t, (float)e.rho,
+                   (float)rate);
+}
+
+template <int NT, bool GMEM>
+__device__ __forceinline__ void wva_hold_body(const WvaCellsIn &in, const WvaCellsOut &out,
+                                              const int cell, const int tid, double *smem,
+                                              const unsigned slab, int max_n, int analyzer_mode,
+                                              float cv2, float *g_inv, double *g_anchor,
+                                              WvaMemoRec *memo, unsigned *memo_cnt,
+                                              const WvaHoldArgs &hold) {
+  // the current allocation of the tick is not read: the held one replaces it
+  WvaCell c;
+  c.cell = cell;
+  c.in_tok = in.in_tok[cell];
+  c.out_tok = in.out_tok[cell];
+  c.N = in.batch_n[cell];
+  c.alpha = in.alpha[cell];
+  c.beta = in.beta[cell];
+  c.gamma = in.gamma[cell];
+  c.delta = in.delta[cell];
+  c.t_tps = in.t_tps[cell];
+  c.min_rep = in.min_replicas[cell];
+  c.acc_cost = in.acc_cost[cell];
+  c.cur_cost = 0.0f;
+  c.cur_rep = 0;
+  c.cur_same = c.cur_empty = c.has_cur = false;
+  const WvaView<WVA_MODE_HOLD> v(in, hold, cell);
+  const int n_scen = v.n_load();
+
+  // ---- (1) no scenario both holds and loads the cell
+  bool active = false;
+  if (c.out_tok != 0)
+    for (int s = 0; s < n_scen; ++s)
+      active = active || (v.held(s) >= 0 && v.arrival(s) != 0.0f);
+  if (!active) {
+    if (tid == 0)
+      for (int s = 0; s < n_scen; ++s) wva_hold_write_quiet(out, v.slot(0, s), v.held(s), c);
+    return;
+  }
+  // from here on out_tok != 0: slice s is quiet iff it is not held or not loaded
+  const auto quiet = [&](int s) { return v.held(s) < 0 || v.arrival(s) == 0.0f; };
+
+  // ---- (2) sizing memo lookup, as wva_cell_body's: uniform verdict, thread 0
+  // of this cell the only writer
+  WvaMemoRec *const rec = memo ? memo + cell : nullptr;
+  const auto memo_key = [&]() {
+    return memo_make_key(c.in_tok, c.out_tok, c.N, c.alpha, c.beta, c.gamma, c.delta, v.own_ttft,
+                         v.own_itl, c.t_tps, cv2, analyzer_mode, NT);
+  };
+  unsigned memo_status = WVA_MEMO_EMPTY;
+  double memo_tput = 0.0;
+  if (rec) {
+    const WvaMemoRec r = *rec;
+    const WvaMemoKey k = memo_key();
+    bool same = r.status == WVA_MEMO_FEASIBLE || r.status == WVA_MEMO_INFEASIBLE;
+#pragma unroll
+    for (int q = 0; q < WVA_MEMO_KEY_WORDS; ++q) same = same && (r.key[q] == k.w[q]);
+    if (same) {
+      memo_status = r.status;
+      memo_tput = r.tput;
+    }
+    if (tid == 0) atomicAdd(memo_cnt + (same ? 0 : 1), 1u);
+    // (an infeasible hit goes on: the held replicas are still evaluated)
+  }
+  auto memo_miss_store = [&](double tput, unsigned status) {
+    if (rec && tid == 0 && memo_status == WVA_MEMO_EMPTY)
+      memo_store(rec, memo_key(), tput, status);
+  };
+
+  // ---- (3) chain geometry
+  WvaModel m;
+  const bool bad_rate =
+      wva_build_geom<NT, GMEM>(c, tid, analyzer_mode, smem, slab, max_n, g_inv, g_anchor, m.g);
+
+  // ---- (4) rate-range bounds and the degenerate-rate guard, as wva_cell_body's
+  const int num_decode = wva_num_decode(c);
+  float prefill1 = (c.in_tok == 0) ? 0.0f : (c.gamma + c.delta * (float)c.in_tok);
+  float s1 = 1.0f / (prefill1 + (float)num_decode * (c.alpha + c.beta));
+  float prefillN = (c.in_tok == 0) ? 0.0f : (c.gamma + c.delta * (float)c.in_tok * (float)c.N);
+  float sN = (float)c.N / (prefillN + (float)num_decode * (c.alpha + c.beta * (float)c.N));
+  const double any_bad = red_max_p<NT, 1>(bad_rate ? 1.0 : 0.0, smem);
+  if (any_bad > 0.0 || !(s1 > 0.0f) || !(sN > 0.0f) || !isfinite(s1) || !isfinite(sN)) {
+    if (tid == 0)
+      for (int s = 0; s < n_scen; ++s) {
+        const int held = v.held(s);
+        if (quiet(s))
+          wva_hold_write_quiet(out, v.slot(0, s), held, c);
+        else
+          wva_hold_write(out, v.slot(0, s), WVA_HOLD_INVALID, held, -1, c.acc_cost * (float)held,
+                         0.0f, 0.0f, 0.0f, 0.0f, 0.0f);
+      }
+    memo_miss_store(0.0, WVA_MEMO_INFEASIBLE);
+    return;
+  }
+  m.logsN = log((double)sN);
+  m.Kstates = 11 * c.N;
+  m.mode = analyzer_mode;
+  m.cv2d = (double)cv2;
+  m.mu = (double)sN;
+  m.lam_min = (double)s1 * WVA_EPSILON;
+  m.lam_max = (double)sN * (1.0 - WVA_EPSILON);
+  m.scratch = smem;
+  m.tid = tid;
+
+  // ---- (5) the cell's sizing, or the memo's word
+  double tput_at_lam = 0.0;
+  bool feasible;
+  if (memo_status == WVA_MEMO_FEASIBLE) {
+    tput_at_lam = memo_tput;
+    feasible = true;
+  } else if (memo_status == WVA_MEMO_INFEASIBLE) {
+    feasible = false;
+  } else {
+    feasible = wva_size_cell<NT>(v.own_ttft, v.own_itl, c, m, tput_at_lam);
+    memo_miss_store(tput_at_lam, feasible ? WVA_MEMO_FEASIBLE : WVA_MEMO_INFEASIBLE);
+  }
+  const double rate_star = tput_at_lam * 1000.0;  // req/sec
+
+  // ---- (6) per load: quiet slice, overload verdict or evaluation
+  for (int s = 0; s < n_scen; ++s) {
+    if (quiet(s)) {
+      if (tid == 0) wva_hold_write_quiet(out, v.slot(0, s), v.held(s), c);
+    } else {
+      wva_hold_scenario<NT>(out, v.slot(0, s), v.arrival(s), v.held(s), feasible, rate_star, c, m);
+    }
+  }
+}
+
+// out arrays are [n_scen][n_cells] with the hold meanings above; in.arrival_rate
+// and the tick's current allocation are not read. Built for the planning
+// kernels' register budget, one cell per block as wva_plan_t.
+template <int NT, bool GMEM>
+__global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
+    wva_hold_t(WvaCellsIn in, WvaCellsOut out, int n_blocks, const int *cell_ids, int max_n,
+               int analyzer_mode, float cv2, float *g_inv, double *g_anchor, WvaMemoRec *memo,
+               unsigned *memo_cnt, WvaHoldArgs hold) {
+  extern __shared__ double smem[];
+  if ((int)blockIdx.x >= n_blocks) return;
+  const int cell = cell_ids ? cell_ids[blockIdx.x] : (int)blockIdx.x;
+  wva_hold_body<NT, GMEM>(in, out, cell, (int)threadIdx.x, smem, blockIdx.x, max_n, analyzer_mode,
+                          cv2, g_inv, g_anchor, memo, memo_cnt, hold);
+}
+
+// ---------------------------------------------------------------------------
 // K2: segmented argmin per server over the sweep output.
 // ---------------------------------------------------------------------------
 extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_argmin(
@@ -1519,7 +1828,8 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
                               double *g_anchor, WvaMemoRec *memo, unsigned *memo_cnt,
                               const WvaPlanArgs *plan = nullptr,
                               const WvaSloArgs *slo = nullptr,
-                              const WvaTokArgs *tok = nullptr) {
+                              const WvaTokArgs *tok = nullptr,
+                              const WvaHoldArgs *hold = nullptr) {
   if (n_blocks <= 0) return 0;
   const bool gmem = g_inv != nullptr && g_anchor != nullptr;
   if (max_n < 1) return -2;
@@ -1541,7 +1851,8 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
   };
   int rc = -3;
 #define WVA_LAUNCH(NTV, GM)                                        \
-  rc = tok != nullptr    ? launch(&wva_tok_plan_t<NTV, GM>, *tok)  \
+  rc = hold != nullptr   ? launch(&wva_hold_t<NTV, GM>, *hold)     \
+       : tok != nullptr  ? launch(&wva_tok_plan_t<NTV, GM>, *tok)  \
        : slo != nullptr  ? launch(&wva_slo_plan_t<NTV, GM>, *slo)  \
        : plan != nullptr ? launch(&wva_plan_t<NTV, GM>, *plan)     \
                          : launch(&wva_sweep_t<NTV, GM>)
@@ -1819,6 +2130,90 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_rollout(
     cur[1 * n_srv + srv] = cur_rep;
     cur[2 * n_srv + srv] = __float_as_int(cur_cost);
   }
+}
+
+// ---------------------------------------------------------------------------
+// K4d wva_hold_reduce: the server records of a hold analysis; it takes
+// wva_plan_reduce's place. Nothing is minimised: per (server, scenario) at most
+// one cell of the server's segment carries the held flag (the host expands one
+// accelerator per server and scenario), and that cell's slice is the server's
+// record. Should a broken caller flag several, the lowest cell index is taken.
+// A server without a flagged cell (no cells at all included) gets the NOT_HELD
+// record: status 3, accelerator -1, held 0, needed -1, floats 0.
+//
+// Work split as wva_rollout: `group` lanes (a power of two, 1..64) serve one
+// server, 64 / group servers share a one-wave block, grid (blocks, n_scen);
+// lane `sub` of a group looks at cells beg + sub, beg + sub + group, ... The
+// group agrees on the held cell by a minimum over its lanes, the lane that
+// found it writes hf[n_scen][6][n_srv] (itl, ttft, rho, rate, slo_rate, cost)
+// and hi[n_scen][4][n_srv] (status, accelerator, held, needed). It also adds 1
+// to counts[n_scen][6] at the status and max(needed - held, 0), where needed
+// >= 0, to deficit[n_scen][n_acc] at the accelerator: 64-bit integer atomics
+// (needed may be 2 147 483 000 per server, and integer adds make the sums
+// independent of execution order); both arrays must be zero on entry. No
+// barrier, no LDS.
+// ---------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_hold_reduce(
+    const uint8_t *status, const uint8_t *held_flag, const int *cell_acc, const int *held,
+    const int *needed, const float *cost, const float *slo_rate, const float *itl,
+    const float *ttft, const float *rho, const float *rate, const int *seg_start, int n_srv,
+    int n_cells, int n_scen, int n_acc, int group, float *hf, int *hi, unsigned long long *counts,
+    unsigned long long *deficit) {
+  const int lane = (int)threadIdx.x;
+  const int sub = lane & (group - 1);
+  const int srv = (int)blockIdx.x * (WVA_WAVE / group) + lane / group;
+  const int sc = (int)blockIdx.y;
+  if (sc >= n_scen) return;  // whole block
+  // lanes past the last server keep an empty segment and store nothing, but
+  // take part in the shuffles below
+  const bool live = srv < n_srv;
+  const int beg = live ? seg_start[srv] : 0;
+  const int end = live ? seg_start[srv + 1] : 0;
+  const size_t base = (size_t)sc * (size_t)n_cells;
+  const int none = 0x7fffffff;
+  int mine = none;
+  for (int i = beg + sub; i < end; i += group)
+    if (held_flag[base + (size_t)i] != 0 && i < mine) mine = i;
+  int w = mine;
+  for (int off = group >> 1; off > 0; off >>= 1) {
+    const int o = __shfl_xor(w, off, group);
+    w = o < w ? o : w;
+  }
+  if (!live) return;
+  float *gf = hf + (size_t)sc * 6 * (size_t)n_srv;
+  int *gi = hi + (size_t)sc * 4 * (size_t)n_srv;
+  unsigned long long *cnt = counts + (size_t)sc * WVA_HOLD_STATUSES;
+  if (w == none) {
+    if (sub != 0) return;
+    for (int r = 0; r < 6; ++r) gf[r * n_srv + srv] = 0.0f;
+    gi[0 * n_srv + srv] = WVA_HOLD_NOT_HELD;
+    gi[1 * n_srv + srv] = -1;
+    gi[2 * n_srv + srv] = 0;
+    gi[3 * n_srv + srv] = -1;
+    atomicAdd(cnt + WVA_HOLD_NOT_HELD, 1ull);
+    return;
+  }
+  if (mine != w) return;
+  const size_t o = base + (size_t)w;
+  int st = (int)status[o];
+  if (st < 0 || st >= WVA_HOLD_STATUSES) st = WVA_HOLD_INVALID;  // keeps the add in counts[]
+  const int acc = cell_acc[w];
+  const int reps = held[o];
+  const int need = needed[o];
+  gf[0 * n_srv + srv] = itl[o];
+  gf[1 * n_srv + srv] = ttft[o];
+  gf[2 * n_srv + srv] = rho[o];
+  gf[3 * n_srv + srv] = rate[o];
+  gf[4 * n_srv + srv] = slo_rate[o];
+  gf[5 * n_srv + srv] = cost[o];
+  gi[0 * n_srv + srv] = st;
+  gi[1 * n_srv + srv] = acc;
+  gi[2 * n_srv + srv] = reps;
+  gi[3 * n_srv + srv] = need;
+  atomicAdd(cnt + st, 1ull);
+  if (need >= 0 && need > reps && acc >= 0 && acc < n_acc)
+    atomicAdd(deficit + (size_t)sc * (size_t)n_acc + (size_t)acc,
+              (unsigned long long)(need - reps));
 }
 
 // ---------------------------------------------------------------------------

@@ -289,6 +289,19 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_steps][n_acc]
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [3][n_srv] final allocation
     ]
+    # hold analysis (engine/fastpath.py FastSweep.hold)
+    lib.wva_ctx_hold.restype = ctypes.c_int
+    lib.wva_ctx_hold.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_int,  # n_scen (1..PLAN_MAX_S)
+        ctypes.c_int,  # n_acc
+        ctypes.c_void_p,  # host fp32 [n_scen][n_cells] arrival rates
+        ctypes.c_void_p,  # host i32 [n_scen][n_cells] held replicas (-1: not held)
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned fp32 [n_scen][6][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_scen][4][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][6] status counts
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][n_acc] deficits
+    ]
     lib.wva_ctx_plan_cells.restype = ctypes.c_int
     lib.wva_ctx_plan_cells.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
     # capacity-limited planning (FastSweep.plan(capacity=...))
