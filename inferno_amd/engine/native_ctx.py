@@ -263,14 +263,17 @@ class NativeCtx:
         """Diagnostics of the fused tick (synchronous, never on the hot path):
         ``path`` 0 = bucket launches + wva_winner, 1 = one wva_tick_t launch,
         2 = two; the task counts and LDS sizes of the launches; the CU count of
-        the residency rule; ``done_nonzero``, how many arrival counters are
+        the residency rule; ``waves_first`` / ``waves_second``, the launch bound
+        (blocks per CU) of the kernel instantiation each launch uses, 0 for a
+        launch that does not exist; ``done_nonzero``, how many arrival counters are
         not 0 (-1 when the fused tick is off; 0 after every completed tick)."""
-        info = (ctypes.c_int * 6)()
+        info = (ctypes.c_int * 8)()
         nz = ctypes.c_int(-1)
         rc = self._lib.wva_ctx_fused_state(self.ctx, info, ctypes.byref(nz))
         if rc != 0:
             raise HipKernelError(f"wva_ctx_fused_state failed: {rc}")
-        keys = ("path", "n_tasks", "n_tasks_second", "lds_first", "lds_second", "n_cus")
+        keys = ("path", "n_tasks", "n_tasks_second", "lds_first", "lds_second", "n_cus",
+                "waves_first", "waves_second")
         out = dict(zip(keys, (int(v) for v in info)))
         out["done_nonzero"] = int(nz.value)
         return out

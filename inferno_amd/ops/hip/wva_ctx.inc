@@ -197,7 +197,8 @@ extern "C" int wva_abi(const char *name) {
   } table[] = {WVA_ABI(WVA_MAX_N),      WVA_ABI(WVA_XL_MAX_N),  WVA_ABI(WVA_HUGE_MAX_N),
                WVA_ABI(WVA_PLAN_MAX_S), WVA_ABI(WVA_N_SMALL),   WVA_ABI(WVA_N_MED),
                WVA_ABI(WVA_TICK_STALE), WVA_ABI(WVA_DYN_ROWS),  WVA_ABI(WVA_REC_ROWS),
-               WVA_ABI(WVA_CTX_SLOTS),  WVA_ABI(WVA_MAX_BUCKETS)};
+               WVA_ABI(WVA_CTX_SLOTS),  WVA_ABI(WVA_MAX_BUCKETS), WVA_ABI(WVA_TICK_WIDE_WAVES),
+               WVA_ABI(WVA_TICK_MAX_WAVES)};
 #undef WVA_ABI
   if (name == nullptr) return -1;
   for (const auto &e : table)
@@ -333,10 +334,14 @@ extern "C" void *wva_ctx_create(int n_cells, int n_srv, void **p) {
   return c;
 }
 
+static int wva_tick_waves(size_t lds);  // below, with the residency rule
+
 // Diagnostics of the fused tick, never on the hot path (synchronous copy).
-// info[6]: fused_path (0 bucket launches, 1 one launch, 2 two launches), tasks
+// info[8]: fused_path (0 bucket launches, 1 one launch, 2 two launches), tasks
 // in all, tasks of the second launch, dynamic LDS bytes of the first and of the
-// second launch, CU count of the residency rule. done_nonzero: how many done[]
+// second launch, CU count of the residency rule, launch bound (blocks per CU)
+// of the wva_tick_t instantiation of the first and of the second launch (0 =
+// no such launch). done_nonzero: how many done[]
 // words are not 0 (-1 when the fused tick is off). Either pointer may be null.
 extern "C" int wva_ctx_fused_state(void *ctx, int *info, int *done_nonzero) {
   WvaCtx *c = (WvaCtx *)ctx;
@@ -348,6 +353,8 @@ extern "C" int wva_ctx_fused_state(void *ctx, int *info, int *done_nonzero) {
     info[3] = (int)c->lds_a;
     info[4] = (int)c->lds_b;
     info[5] = c->n_cus;
+    info[6] = c->fused_path != 0 ? wva_tick_waves(c->lds_a) : 0;
+    info[7] = c->fused_path == 2 ? wva_tick_waves(c->lds_b) : 0;
   }
   if (done_nonzero != nullptr) {
     *done_nonzero = -1;
@@ -435,11 +442,28 @@ extern "C" int wva_ctx_set_topology(void *ctx, const int *cell_server, const int
   return 0;
 }
 
+// The launch bound (blocks per CU) of the wva_tick_t instantiation that a
+// launch with `lds` bytes of dynamic LDS uses: the wide budget
+// (WVA_TICK_WIDE_WAVES) where the LDS holds the CU to that many blocks anyway,
+// otherwise the narrow one (WVA_TICK_MAX_WAVES). So the register bound never
+// takes a block off a CU that its LDS would have let on.
+static int wva_tick_waves(size_t lds) {
+  const size_t per_cu = lds > 0 ? (size_t)(160 * 1024) / lds : WVA_TICK_MAX_WAVES;
+  return per_cu <= (size_t)WVA_TICK_WIDE_WAVES ? WVA_TICK_WIDE_WAVES : WVA_TICK_MAX_WAVES;
+}
+static const void *wva_tick_func(size_t lds) {
+  return wva_tick_waves(lds) == WVA_TICK_WIDE_WAVES
+             ? reinterpret_cast<const void *>(&wva_tick_t<WVA_TICK_WIDE_WAVES>)
+             : reinterpret_cast<const void *>(&wva_tick_t<WVA_TICK_MAX_WAVES>);
+}
+
 // Blocks of `lds` bytes of dynamic LDS that are resident at once: per CU what
-// fits in its 160 KiB, at most the 4 that wva_tick_t's launch bounds ask for.
+// fits in its 160 KiB, at most what the launch bound of the instantiation
+// chosen for that size asks for.
 static long wva_tick_slots(const WvaCtx *c, size_t lds) {
-  const size_t per_cu = lds > 0 ? (size_t)(160 * 1024) / lds : 4;
-  return (long)c->n_cus * (long)(per_cu < 4 ? per_cu : 4);
+  const size_t bound = (size_t)wva_tick_waves(lds);
+  const size_t per_cu = lds > 0 ? (size_t)(160 * 1024) / lds : bound;
+  return (long)c->n_cus * (long)(per_cu < bound ? per_cu : bound);
 }
 
 // Build and upload the fused tick's task table from the bucket lists just
@@ -549,11 +573,12 @@ static int wva_build_tasks(WvaCtx *c) {
   const size_t all = wide_top > rest ? wide_top : rest;
   const int n_tasks = (int)tasks.size();
   // The fused launch pays where the tick is bound by launches and queues, not
-  // by the chip: a grid of at most one round of blocks at the kernel's launch
-  // bounds (4 per CU). A larger fleet is throughput-bound, and there the
-  // bucket launches, with their one-wave blocks, measured faster (config5,
-  // 32768 cells: 0.735 ms/step against 1.166).
-  if ((long)n_tasks > 4L * c->n_cus_dev) return 0;
+  // by the chip: a grid of at most one round of blocks at the kernel's
+  // narrow launch bound (WVA_TICK_MAX_WAVES per CU; a launch on the wide
+  // budget holds fewer, and the split rule below counts those). A larger fleet
+  // is throughput-bound, and there the bucket launches, with their one-wave
+  // blocks, measured faster (config5, 32768 cells: 0.735 ms/step against 1.166).
+  if ((long)n_tasks > (long)WVA_TICK_MAX_WAVES * c->n_cus_dev) return 0;
   int path = 1;
   size_t lds_a = all, lds_b = 0;
   // Residency rule. When the widest bucket (the XL tier) alone raises the
@@ -569,7 +594,9 @@ static int wva_build_tasks(WvaCtx *c) {
     lds_b = wide_top;
   }
   if (all > (size_t)160 * 1024) return 0;
-  if (wva_optin_lds(reinterpret_cast<const void *>(&wva_tick_t), all) != 0) {
+  // each launch opts in for its own size on the instantiation it will use
+  if (wva_optin_lds(wva_tick_func(lds_a), lds_a) != 0 ||
+      (path == 2 && wva_optin_lds(wva_tick_func(lds_b), lds_b) != 0)) {
     (void)hipGetLastError();
     return 0;
   }
@@ -692,10 +719,16 @@ static int wva_run_buckets(WvaCtx *c, const WvaBucket *buckets, int n_buckets,
 // n tasks of the fused tick's table from task0 on, `lds` bytes of dynamic LDS
 static void wva_tick_launch(WvaCtx *c, int task0, int n, size_t lds, hipStream_t s) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(wva_tick_t, dim3(n), dim3(WVA_TICK_NT), lds, s, c->in, c->out, c->tasks,
-                     task0, n, c->narrow_stride, c->analyzer_mode, c->cv2, c->memo, c->memo_cnt,
-                     c->dev_cell_server, c->done, c->seg_start, c->cell_acc, c->n_srv, c->gather,
-                     c->winner);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(n), dim3(WVA_TICK_NT), lds, s, c->in, c->out, c->tasks, task0,
+                       n, c->narrow_stride, c->analyzer_mode, c->cv2, c->memo, c->memo_cnt,
+                       c->dev_cell_server, c->done, c->seg_start, c->cell_acc, c->n_srv, c->gather,
+                       c->winner);
+  };
+  if (wva_tick_waves(lds) == WVA_TICK_WIDE_WAVES)
+    launch(&wva_tick_t<WVA_TICK_WIDE_WAVES>);
+  else
+    launch(&wva_tick_t<WVA_TICK_MAX_WAVES>);
 }
 
 // enqueue the whole per-tick pipeline on the ctx's streams (used both for

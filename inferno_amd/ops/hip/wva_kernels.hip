@@ -2275,11 +2275,25 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_winner(
 // Invariant: after a completed tick every done[] word is 0 (each server's
 // last arriver resets it). The host zeroes the array at creation, whenever the
 // task table changes and after a failed tick, never per tick.
+//
+// Register budget. MINW is the kernel's launch bound in waves per SIMD, which
+// for these four-wave blocks is blocks per CU. At 4 (128 VGPRs) the kernel
+// spills 216 B/lane, which costs a flagship launch 7.5 us whatever its tasks
+// are; at WVA_TICK_WIDE_WAVES = 2 it takes 192 VGPRs and no scratch.
+// A launch whose dynamic LDS lets at most two blocks onto a CU anyway (an XL
+// cell: 69 952 B on the flagship) loses nothing to the wider budget, so the
+// host picks the instantiation per launch from the launch's LDS size
+// (wva_tick_waves in wva_ctx.inc); every other launch keeps four blocks per CU.
 // ---------------------------------------------------------------------------
 #define WVA_TASK_WIDE (-2)
 #define WVA_TICK_NT 256
+#define WVA_TICK_MAX_WAVES 4
+#ifndef WVA_TICK_WIDE_WAVES
+#define WVA_TICK_WIDE_WAVES 2
+#endif
 
-__global__ void __launch_bounds__(WVA_TICK_NT, 4)
+template <int MINW>
+__global__ void __launch_bounds__(WVA_TICK_NT, MINW)
     wva_tick_t(WvaCellsIn in, WvaCellsOut out, const int4 *tasks, int task0, int n_tasks,
                int narrow_stride, int analyzer_mode, float cv2, WvaMemoRec *memo,
                unsigned *memo_cnt, const int *cell_server, unsigned *done, const int *seg_start,

@@ -223,7 +223,7 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
     lib.wva_ctx_fused_state.restype = ctypes.c_int
     lib.wva_ctx_fused_state.argtypes = [
         ctypes.c_void_p,
-        ctypes.POINTER(ctypes.c_int),  # out: info[6]
+        ctypes.POINTER(ctypes.c_int),  # out: info[8]
         ctypes.POINTER(ctypes.c_int),  # out: done[] words that are not 0
     ]
     # scenario planning (engine/fastpath.py FastSweep.plan)
