@@ -8,6 +8,10 @@ pkg/config wire format) and print the allocation solution.
   python -m inferno_amd.cli plan system.json --slo-scales 0.5,1,2 [--scales ...] [--json]
   python -m inferno_amd.cli plan system.json --rollout --scales 0.5,1,2,1,0.5 [--json]
   python -m inferno_amd.cli plan system.json --hold --scales 0.5,1,2,4 [--json]
+  python -m inferno_amd.cli plan system.json --ensemble-scales "0.5,1,2;0.6,1.2,2.4;0.4,0.9,1.7"
+      [--quantiles 0.5,0.9,1] [--json]
+  python -m inferno_amd.cli plan system.json --scales 0.5,1,2 --ensemble-noise 0.2 --paths 16
+      --seed 7 [--quantiles ...] [--json]
 """
 from __future__ import annotations
 
@@ -118,6 +122,13 @@ def cmd_plan(args) -> int:
     from .engine import FastSweep, SweepEngine
 
     limited = args.limited or args.capacity is not None
+    if args.ensemble_scales is not None or args.ensemble_noise is not None:
+        if (limited or args.slo_scales is not None or args.token_scales is not None
+                or args.rollout or args.hold):
+            raise SystemExit("plan: a forecast ensemble rolls out unlimited-mode reconciles "
+                             "over sampled load paths; it does not combine with --rollout, "
+                             "--hold, --slo-scales, --token-scales, --limited or --capacity")
+        return _cmd_plan_ensemble(args)
     if args.hold:
         if (limited or args.slo_scales is not None or args.token_scales is not None
                 or args.rollout):
@@ -358,6 +369,75 @@ def _cmd_plan_rollout(args) -> int:
     return 0
 
 
+def _parse_ensemble_scales(text: str) -> list[list[float]]:
+    paths = [_parse_scales(p, "--ensemble-scales") for p in text.split(";") if p.strip()]
+    if not paths:
+        raise SystemExit("--ensemble-scales: at least one path is required")
+    if len({len(p) for p in paths}) != 1:
+        raise SystemExit("--ensemble-scales: every path needs the same number of ticks, got "
+                         + ", ".join(str(len(p)) for p in paths))
+    return paths
+
+
+def _cmd_plan_ensemble(args) -> int:
+    """Forecast ensemble: E load paths of consecutive ticks, per tick and
+    quantile the order statistics of the fleet across the paths."""
+    from .engine import FastSweep, SweepEngine, noisy_paths
+
+    if args.ensemble_scales is not None:
+        if args.ensemble_noise is not None or args.scales is not None:
+            raise SystemExit("plan: --ensemble-scales names the paths itself; it does not "
+                             "combine with --ensemble-noise or --scales")
+        paths = _parse_ensemble_scales(args.ensemble_scales)
+    else:
+        if args.scales is None:
+            raise SystemExit("plan: --ensemble-noise needs --scales (the forecast, one factor "
+                             "per tick)")
+        try:
+            paths = noisy_paths(_parse_scales(args.scales), args.ensemble_noise, args.paths,
+                                args.seed).tolist()
+        except ValueError as e:
+            raise SystemExit(f"plan: --ensemble-noise: {e}")
+    quantiles = _parse_scales(args.quantiles, "--quantiles")
+    system, _ = _load_system(args.spec)
+    backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
+    fs = FastSweep(system, backend=backend)
+    try:
+        res = fs.rollout_ensemble(scales=paths, quantiles=quantiles)
+    except ValueError as e:
+        print(f"plan: {e}", file=sys.stderr)
+        return 2
+    n_paths = len(paths)
+    rows = [{
+        "step": s,
+        "quantile": float(q),
+        "rank": int(res.ranks[k]),
+        "totalCost": round(float(res.cost_total_q[k, s]), 2),
+        "replicas": {
+            name: int(res.replicas_by_acc_q[k, s, j]) for j, name in enumerate(fs.acc_names)
+        },
+        "infeasibleServers": int(res.infeasible_q[k, s]),
+        "acceleratorChanges": int(res.acc_changes_q[k, s]),
+        "unanimousServers": int((res.acc_mode_paths[s] == n_paths).sum()),
+    } for s in range(len(paths[0])) for k, q in enumerate(res.quantiles)]
+    if args.json:
+        print(json.dumps({"backend": backend, "servers": len(fs.server_names), "paths": n_paths,
+                          "steps": len(paths[0]), "ensemble": rows}, indent=2))
+        return 0
+    names = fs.acc_names
+    print(f"{'step':>5} {'quantile':>8} {'cost':>12} " + " ".join(f"{n:>10}" for n in names)
+          + f" {'infeasible':>10} {'acc-changes':>11} {'unanimous':>9}")
+    for r in rows:
+        print(f"{r['step']:>5} {r['quantile']:>8g} {r['totalCost']:>12.2f} "
+              + " ".join(f"{r['replicas'][n]:>10}" for n in names)
+              + f" {r['infeasibleServers']:>10} {r['acceleratorChanges']:>11} "
+              f"{r['unanimousServers']:>9}")
+    print(f"({len(fs.server_names)} servers, backend {backend}; {n_paths} paths of "
+          f"{len(paths[0])} consecutive steps; every column is its own order statistic across "
+          "the paths; unanimous = servers on which every path chose the same accelerator)")
+    return 0
+
+
 def _cmd_plan_hold(args) -> int:
     """Hold analysis: the current allocation, unchanged, at each load scale."""
     from .engine import HOLD_OK, HOLD_STATUS_NAMES, FastSweep, SweepEngine
@@ -465,6 +545,18 @@ def main() -> None:
     pp.add_argument("--hold", action="store_true",
                     help="hold analysis: the current allocation is not resized; per load scale "
                          "the SLO verdict of every server, the replicas short by accelerator")
+    pp.add_argument("--ensemble-scales", default=None,
+                    help="forecast ensemble: load paths separated by ';', each a comma-separated "
+                         "list of consecutive step factors of the same length, e.g. "
+                         "'0.5,1,2;0.6,1.2,2.4'; per step and quantile the order statistics "
+                         "across the paths")
+    pp.add_argument("--quantiles", default="0.5,0.9,1",
+                    help="quantiles of a forecast ensemble, each in (0, 1] (nearest rank)")
+    pp.add_argument("--ensemble-noise", type=float, default=None, metavar="SIGMA",
+                    help="forecast ensemble around --scales: --paths paths scale[s] x "
+                         "exp(SIGMA x z), z standard normal; path 0 is the forecast itself")
+    pp.add_argument("--paths", type=int, default=16, help="paths of --ensemble-noise")
+    pp.add_argument("--seed", type=int, default=0, help="seed of --ensemble-noise")
     pp.set_defaults(fn=cmd_plan)
     pa = sub.add_parser("analyze", help="per-variant candidate allocations")
     pa.add_argument("spec")

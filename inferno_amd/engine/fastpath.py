@@ -180,6 +180,116 @@ ROLLOUT_CHUNK = PLAN_MAX_S
 _WINNER_FIELDS = ("acc_idx", "num_replicas", "batch", "cost", "value", "itl", "ttft", "rho",
                   "max_rate")
 
+# Forecast ensembles (FastSweep.rollout_ensemble): most paths, most rows (paths
+# x ticks) and most quantiles of one call; the rows one device pass holds (at
+# most PLAN_MAX_S; a pass holds whole paths, so a forecast of S ticks runs
+# ENSEMBLE_PASS_ROWS // S paths per pass; lowered only by tests); and the bytes
+# the device arena may take when INFERNO_ENSEMBLE_BYTES does not say.
+ENSEMBLE_MAX_PATHS = 256
+ENSEMBLE_MAX_ROWS = 4096
+ENSEMBLE_MAX_QUANTILES = 8
+ENSEMBLE_PASS_ROWS = PLAN_MAX_S
+ENSEMBLE_BYTES = 1 << 30
+
+
+@dataclass
+class EnsemblePaths:
+    """The per-path records of an ensemble (rollout_ensemble(return_paths=True))."""
+
+    winners: WinnerRecord  # every array [E, S, n_servers]
+    final_cur: tuple  # (cur_acc i32, cur_rep i32, cur_cost f32), each [E, n_servers]
+
+
+@dataclass
+class EnsembleResult:
+    """Forecast ensemble: E rollouts of S ticks from one start allocation, and
+    per tick the order statistics across the paths
+    (FastSweep.rollout_ensemble). Q = number of quantiles; band q is the
+    rank-``ranks[q]`` value (0 = smallest) among the E paths' values."""
+
+    quantiles: np.ndarray  # float64 [Q]
+    ranks: np.ndarray  # int64 [Q]: nearest rank of each quantile, 0-based
+    arrival: np.ndarray  # float32 [E, S, n_servers]: the paths evaluated
+    # per path and tick: rollout(arrival=arrival[e])'s fields of the same name
+    path_replicas_by_acc: np.ndarray  # int64 [E, S, n_acc]
+    path_infeasible_servers: np.ndarray  # int64 [E, S]
+    path_acc_changes: np.ndarray  # int64 [E, S]
+    # float64 [E, S]: the sequential fp64 sum, in server order, of the winners'
+    # fp32 cost (rollout().cost_total sums pairwise: last bits may differ)
+    path_cost_total: np.ndarray
+    # fleet bands: order statistics of the four arrays above across the paths
+    replicas_by_acc_q: np.ndarray  # int64 [Q, S, n_acc]
+    cost_total_q: np.ndarray  # float64 [Q, S]
+    infeasible_q: np.ndarray  # int64 [Q, S]
+    acc_changes_q: np.ndarray  # int64 [Q, S]
+    # server bands: order statistics of the winners' replicas and cost
+    server_replicas_q: np.ndarray  # int32 [Q, S, n_servers]
+    server_cost_q: np.ndarray  # float32 [Q, S, n_servers]
+    # agreement: the most frequent winner code across the paths (-2 empty, -1
+    # none, >= 0 accelerator; the smallest code on ties) and how many chose it
+    acc_mode: np.ndarray  # int32 [S, n_servers]
+    acc_mode_paths: np.ndarray  # int32 [S, n_servers]
+    paths: Optional[EnsemblePaths] = None
+
+
+def ensemble_ranks(quantiles, n_paths: int) -> np.ndarray:
+    """Nearest rank (0-based, ascending order) of every quantile among
+    ``n_paths`` values: clamp(ceil(q * E) - 1, 0, E - 1) with q taken as the
+    decimal its repr shows, in exact rational arithmetic: 0.9 of 10 is rank 8,
+    and 0.07 of 100 rank 6, where binary floating point's 0.07 * 100 lies
+    above 7 and would give rank 7."""
+    import math
+    from fractions import Fraction
+
+    return np.array(
+        [min(max(math.ceil(Fraction(repr(float(q))) * n_paths) - 1, 0), n_paths - 1)
+         for q in quantiles], dtype=np.int64)
+
+
+def ensemble_bands(values: np.ndarray, ranks) -> np.ndarray:
+    """Order statistics across the leading (path) axis: [E, ...] -> [Q, ...],
+    row q holding the rank-``ranks[q]`` value of every column."""
+    return np.sort(values, axis=0)[np.asarray(ranks, dtype=np.int64)]
+
+
+def ensemble_mode(codes: np.ndarray):
+    """(mode, count) across the leading (path) axis of integer winner codes
+    >= -2: per column the most frequent code, the smallest on ties, and how
+    many paths hold it; both int32 of the trailing shape."""
+    codes = np.asarray(codes)
+    top = int(codes.max()) if codes.size else -2
+    # counts[c + 2] = paths that hold code c (a bincount per column)
+    counts = np.stack([(codes == c).sum(axis=0) for c in range(-2, top + 1)])
+    mode = counts.argmax(axis=0)  # the first, i.e. smallest, code among the most frequent
+    return (mode - 2).astype(np.int32), counts.max(axis=0).astype(np.int32)
+
+
+def ensemble_path_cost(cost: np.ndarray) -> np.ndarray:
+    """Sequential fp64 sum over the last (server) axis of fp32 costs, in index
+    order from +0.0: what the device's per-row sum computes."""
+    cost = np.asarray(cost, dtype=np.float32)
+    if cost.shape[-1] == 0:
+        return np.zeros(cost.shape[:-1], dtype=np.float64)
+    return np.cumsum(cost.astype(np.float64), axis=-1)[..., -1]
+
+
+def noisy_paths(scales, sigma: float, n_paths: int, seed: int) -> np.ndarray:
+    """E sampled load paths around a forecast: [n_paths, S] factors
+    scale[s] * exp(sigma * z[e, s]) with z standard normal from
+    np.random.Generator(np.random.PCG64(seed)); path 0 is the forecast itself."""
+    sc = np.asarray(scales, dtype=np.float64)
+    if sc.ndim != 1 or sc.shape[0] < 1:
+        raise ValueError(f"scales must be 1-D and non-empty, got shape {sc.shape}")
+    if not np.isfinite(sc).all() or (sc < 0).any():
+        raise ValueError("scales must be finite and non-negative")
+    if not (np.isfinite(sigma) and sigma >= 0):
+        raise ValueError(f"sigma must be finite and non-negative, got {sigma}")
+    if n_paths < 1:
+        raise ValueError(f"n_paths must be at least 1, got {n_paths}")
+    z = np.random.Generator(np.random.PCG64(seed)).standard_normal((n_paths, sc.shape[0]))
+    z[0] = 0.0
+    return sc[None, :] * np.exp(float(sigma) * z)
+
 # the four SaturationPolicy names as ops/native/greedy.cpp numbers them
 _POLICY_CODE = {"None": 0, "PriorityExhaustive": 1, "PriorityRoundRobin": 2, "RoundRobin": 3}
 
@@ -778,6 +888,164 @@ class FastSweep:
             f: np.stack([getattr(r, f) for r in rows]) for f in _WINNER_FIELDS
         })
         return winners, cur
+
+    # ------------------------------------------------------------------
+    # Forecast ensembles
+    # ------------------------------------------------------------------
+    def rollout_ensemble(self, scales=None, arrival=None, quantiles=(0.5, 0.9, 1.0),
+                         return_paths: bool = False) -> EnsembleResult:
+        """Roll out E sampled load paths of S ticks and return, per tick, order
+        statistics across the paths.
+
+        Exactly one of ``scales`` ([E, S] factors on the base arrival rates,
+        formed as ``float32(base) * float32(scale)`` as plan() does) and
+        ``arrival`` ([E, S, n_servers] req/min) is given; 1 <= E <=
+        ENSEMBLE_MAX_PATHS, 1 <= S <= PLAN_MAX_S, E * S <= ENSEMBLE_MAX_ROWS.
+        Every path starts from the same current allocation, as rollout() does;
+        path e is, by definition, ``rollout(arrival=arrival[e])``.
+
+        ``quantiles``: 1 to ENSEMBLE_MAX_QUANTILES values in (0, 1]. Quantile q
+        is the nearest-rank order statistic on the ascending order, rank
+        ``ensemble_ranks`` (exact rational arithmetic on the decimal q is
+        written as: 0.9 of 10 paths is rank 8). A band is that order statistic
+        of one number across the E paths; bands of different numbers, or of
+        different servers, need not come from the same path.
+
+        ``path_cost_total`` is the sequential fp64 sum, in server order, of the
+        winners' fp32 cost (a server without a winner holds 0 and is added). It
+        differs from ``rollout().cost_total``, which numpy sums pairwise, in the
+        last bits at most. ``acc_mode`` is the winner code most paths chose for
+        a (tick, server), ``acc_mode_paths`` how many did; where
+        ``acc_mode_paths == E`` the server's replica band is over one
+        accelerator and can be read as replicas of that accelerator.
+
+        ``paths`` holds every path's winners and final allocation only with
+        ``return_paths``. On the GPU a bands-only call downloads the bands, the
+        mode pair and the per-path aggregates and nothing else: the per-cell
+        work is plan()'s pass over ENSEMBLE_PASS_ROWS // S paths at a time
+        (the sizing memo sees one lookup per loaded cell and pass), the chains
+        of all paths of a pass run in one kernel and the selections in another.
+        The device arena, about 12 * E * S * n_servers bytes, must not exceed
+        INFERNO_ENSEMBLE_BYTES (default 1 GiB, read per call). A call changes
+        nothing a following reconcile(), plan(), rollout() or hold() returns
+        and leaves the server objects as they were."""
+        scen = self._ensemble_scenarios(scales, arrival)
+        n_paths, n_steps, n_srv = scen.shape
+        qs, ranks = _ensemble_quantiles(quantiles, n_paths)
+        n_acc = len(self.acc_names)
+        need = _ensemble_arena_bytes(n_paths, n_steps, n_srv, n_acc, len(qs))
+        env = os.environ.get("INFERNO_ENSEMBLE_BYTES")
+        try:
+            limit = int(env) if env else ENSEMBLE_BYTES
+        except ValueError:
+            raise ValueError(f"INFERNO_ENSEMBLE_BYTES must be an integer, got {env!r}") from None
+        if need > limit:
+            raise ValueError(
+                f"rollout_ensemble() needs a device arena of {need} bytes for {n_paths} paths x "
+                f"{n_steps} ticks x {n_srv} servers, above the limit of {limit} "
+                "(INFERNO_ENSEMBLE_BYTES)")
+        start = tuple(np.array(a) for a in self._base_cur())
+        if self.backend == "gpu" and self.n_cells > 0 and n_acc > 0:
+            return self._ensemble_gpu(scen, start, qs, ranks, return_paths)
+        if self.backend == "gpu":
+            rolled = [(_empty_winners(n_steps, n_srv), start)] * n_paths
+        else:
+            rolled = [self._rollout_cpu(scen[e], start) for e in range(n_paths)]
+        winners = WinnerRecord(**{
+            f: np.stack([getattr(w, f) for w, _ in rolled]) for f in _WINNER_FIELDS
+        })
+        final_cur = tuple(np.stack([cur[k] for _, cur in rolled]) for k in range(3))
+        totals = np.stack([self._plan_totals(w, None)[0] for w, _ in rolled])
+        bands = _ensemble_bands_of(winners, totals, start[0], ranks)
+        return EnsembleResult(
+            quantiles=qs, ranks=ranks, arrival=scen,
+            paths=EnsemblePaths(winners, final_cur) if return_paths else None, **bands)
+
+    def _ensemble_scenarios(self, scales, arrival) -> np.ndarray:
+        """Validate rollout_ensemble()'s load input and return the [E, S,
+        n_servers] fp32 rates."""
+        who = "rollout_ensemble()"
+        if (scales is None) == (arrival is None):
+            raise ValueError(f"{who} takes exactly one of scales and arrival")
+        n_srv = len(self.server_names)
+        if scales is not None:
+            try:
+                vals = np.asarray(scales, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"scales is not numeric: {e}") from None
+            if vals.ndim != 2:
+                raise ValueError(f"scales must have shape [E, S], got {vals.shape}")
+            what = "scales"
+        else:
+            try:
+                vals = np.asarray(arrival, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"arrival is not numeric: {e}") from None
+            if vals.ndim != 3 or vals.shape[2] != n_srv:
+                raise ValueError(f"arrival must have shape [E, S, {n_srv}], got {vals.shape}")
+            what = "arrival"
+        n_paths, n_steps = vals.shape[:2]
+        if not 1 <= n_paths <= ENSEMBLE_MAX_PATHS:
+            raise ValueError(f"{who} takes 1..{ENSEMBLE_MAX_PATHS} paths, got {n_paths}")
+        if not 1 <= n_steps <= PLAN_MAX_S:
+            raise ValueError(f"{who} takes 1..{PLAN_MAX_S} steps, got {n_steps}")
+        if n_paths * n_steps > ENSEMBLE_MAX_ROWS:
+            raise ValueError(
+                f"{who} takes at most {ENSEMBLE_MAX_ROWS} paths x steps, got "
+                f"{n_paths} x {n_steps} = {n_paths * n_steps}")
+        if not np.isfinite(vals).all() or (vals < 0).any():
+            raise ValueError(f"{what} must be finite and non-negative")
+        with np.errstate(over="ignore"):  # an overflow is reported below
+            if scales is not None:
+                base = self._base_load()[0]
+                scen = base[None, None, :] * vals.astype(np.float32)[:, :, None]
+            else:
+                scen = vals.astype(np.float32)
+        scen = np.ascontiguousarray(scen, dtype=np.float32)
+        if not np.isfinite(scen).all():
+            raise ValueError(f"{what} overflows float32")
+        return scen
+
+    def _ensemble_gpu(self, scen: np.ndarray, start, qs, ranks, return_paths: bool):
+        n_paths, n_steps, n_srv = scen.shape
+        n_acc = len(self.acc_names)
+        dims = (n_paths, n_steps, len(qs))
+        per_pass = max(1, min(int(ENSEMBLE_PASS_ROWS), PLAN_MAX_S) // n_steps)
+        pf, pi = [], []
+        for e0 in range(0, n_paths, per_pass):
+            rows = scen[e0:e0 + per_pass].reshape(-1, n_srv)
+            # staged exactly as a rollout pass: the pass's own zero-load cells
+            # make the bucket layout stale, which is resynchronised there
+            self._tick(plan_arrival=rows, launch=False, cur=start)
+            cell_scen = np.ascontiguousarray(rows[:, self.cell_server], dtype=np.float32)
+            rec = self._gpu.ensemble_pass(cell_scen, dims, e0, n_acc, start, return_paths)
+            if return_paths:
+                pf.append(rec[0])
+                pi.append(rec[1])
+        out = self._gpu.ensemble_bands(dims, n_acc, ranks, return_paths)
+        paths = None
+        if return_paths:
+            w = _winner_record(np.concatenate(pf), np.concatenate(pi))
+            winners = WinnerRecord(**{
+                f: getattr(w, f).reshape(n_paths, n_steps, n_srv) for f in _WINNER_FIELDS
+            })
+            fin = out["final"]
+            paths = EnsemblePaths(winners, (
+                np.ascontiguousarray(fin[:, 0]), np.ascontiguousarray(fin[:, 1]),
+                np.ascontiguousarray(fin[:, 2]).view(np.float32)))
+        fleet = out["fleet_q"]
+        return EnsembleResult(
+            quantiles=qs, ranks=ranks, arrival=scen,
+            path_replicas_by_acc=out["totals"].astype(np.int64),
+            path_infeasible_servers=out["nowin"].astype(np.int64),
+            path_acc_changes=out["changes"].astype(np.int64),
+            path_cost_total=out["cost"],
+            replicas_by_acc_q=np.ascontiguousarray(fleet[:, :, :n_acc]),
+            cost_total_q=np.ascontiguousarray(fleet[:, :, n_acc + 2]).view(np.float64),
+            infeasible_q=np.ascontiguousarray(fleet[:, :, n_acc]),
+            acc_changes_q=np.ascontiguousarray(fleet[:, :, n_acc + 1]),
+            server_replicas_q=out["srv_reps_q"], server_cost_q=out["srv_cost_q"],
+            acc_mode=out["mode"], acc_mode_paths=out["mode_paths"], paths=paths)
 
     # ------------------------------------------------------------------
     # Hold analysis
@@ -1623,6 +1891,55 @@ def _acc_changes(start_acc: np.ndarray, acc_idx: np.ndarray) -> np.ndarray:
                      start_acc[None, :])
     before = np.concatenate([start_acc[None, :], after[:-1]])
     return (after != before).sum(axis=1).astype(np.int64)
+
+
+def _ensemble_quantiles(quantiles, n_paths: int):
+    """Validate rollout_ensemble()'s quantiles: (float64 [Q], int64 ranks)."""
+    try:
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"quantiles is not numeric: {e}") from None
+    if qs.ndim != 1 or not 1 <= qs.shape[0] <= ENSEMBLE_MAX_QUANTILES:
+        raise ValueError(
+            f"rollout_ensemble() takes 1..{ENSEMBLE_MAX_QUANTILES} quantiles, got shape {qs.shape}")
+    if not (np.isfinite(qs).all() and (qs > 0).all() and (qs <= 1).all()):
+        raise ValueError("quantiles must lie in (0, 1]")
+    return qs, ensemble_ranks(qs, n_paths)
+
+
+def _ensemble_arena_bytes(n_paths: int, n_steps: int, n_srv: int, n_acc: int, n_q: int) -> int:
+    """Bytes of the device arena of an ensemble, as ops/hip/wva_ctx.inc lays it
+    out (every segment padded to 256 bytes): the three compact records, the
+    per-row aggregates, the final allocations, the bands."""
+    rows = n_paths * n_steps
+    sizes = [rows * n_srv * 4] * 3 + [rows * n_acc * 8, rows * 4, rows * 4, rows * 8,
+                                      n_paths * 3 * n_srv * 4]
+    sizes += [n_q * n_steps * n_srv * 4] * 2 + [n_steps * n_srv * 4] * 2
+    sizes.append(n_q * n_steps * (n_acc + 3) * 8)
+    return sum((b + 255) // 256 * 256 for b in sizes)
+
+
+def _ensemble_bands_of(winners: WinnerRecord, totals: np.ndarray, start_acc: np.ndarray,
+                       ranks: np.ndarray) -> dict:
+    """The per-path aggregates, bands and mode pair of an EnsembleResult from
+    the paths' winners ([E, S, n_servers] arrays) and replica totals ([E, S,
+    n_acc]), all by the module's helpers: the definition the device is checked
+    against."""
+    acc = winners.acc_idx
+    infeasible = (acc == -1).sum(axis=2).astype(np.int64)
+    changes = np.stack([_acc_changes(start_acc, a) for a in acc])
+    cost = ensemble_path_cost(winners.cost)
+    mode, mode_paths = ensemble_mode(acc)
+    return dict(
+        path_replicas_by_acc=totals, path_infeasible_servers=infeasible,
+        path_acc_changes=changes, path_cost_total=cost,
+        replicas_by_acc_q=ensemble_bands(totals, ranks),
+        cost_total_q=ensemble_bands(cost, ranks),
+        infeasible_q=ensemble_bands(infeasible, ranks),
+        acc_changes_q=ensemble_bands(changes, ranks),
+        server_replicas_q=ensemble_bands(winners.num_replicas, ranks),
+        server_cost_q=ensemble_bands(winners.cost, ranks),
+        acc_mode=mode, acc_mode_paths=mode_paths)
 
 
 def _empty_hold(n_scen: int, n_srv: int) -> dict:

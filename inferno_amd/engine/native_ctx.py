@@ -432,6 +432,67 @@ class NativeCtx:
             (end[0], end[1], end[2].view(np.float32)),
         )
 
+    def ensemble_pass(self, cell_scen: np.ndarray, dims, path0: int, n_acc: int, cur,
+                      full: bool):
+        """wva_ctx_ensemble_pass on [P * S, n_cells] fp32 arrivals, row p * S +
+        s being tick s of path path0 + p of an ensemble of ``dims`` = (E, S,
+        Q), every path starting from ``cur`` (which the tick was staged with).
+        The results stay on the device; with ``full`` the pass's records come
+        back as rollout()'s first two arrays, else None."""
+        n_total, n_steps, n_q = dims
+        n_paths = cell_scen.shape[0] // n_steps
+        cur = (np.ascontiguousarray(cur[0], dtype=np.int32),
+               np.ascontiguousarray(cur[1], dtype=np.int32),
+               np.ascontiguousarray(cur[2], dtype=np.float32))
+        for a in cur:
+            if a.shape != (self.n_srv,):
+                raise ValueError(
+                    f"per-server override has shape {a.shape}, expected ({self.n_srv},)"
+                )
+        out = [ctypes.c_void_p() for _ in range(2)]
+        rc = self._lib.wva_ctx_ensemble_pass(
+            self.ctx, n_total, n_steps, n_q, n_acc, path0, n_paths, cell_scen.ctypes.data,
+            cur[0].ctypes.data, cur[1].ctypes.data, cur[2].ctypes.data, 1 if full else 0,
+            *[ctypes.byref(p) for p in out],
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_ensemble_pass failed: {rc}")
+        if not full:
+            return None
+        rows = n_paths * n_steps
+        return (_copy_out(out[0], ctypes.c_float, (rows, 6, self.n_srv)),
+                _copy_out(out[1], ctypes.c_int32, (rows, 4, self.n_srv)))
+
+    def ensemble_bands(self, dims, n_acc: int, ranks: np.ndarray, want_final: bool) -> dict:
+        """wva_ctx_ensemble_bands after the last pass of an ensemble of
+        ``dims`` = (E, S, Q): the per-row aggregates, the bands and the mode
+        pair as numpy copies, ``final`` (int32 [E, 3, n_srv]) only with
+        ``want_final``."""
+        n_total, n_steps, n_q = dims
+        rk = np.ascontiguousarray(ranks, dtype=np.int32)
+        out = (ctypes.c_void_p * 10)()
+        rc = self._lib.wva_ctx_ensemble_bands(self.ctx, rk.ctypes.data, n_q,
+                                              1 if want_final else 0, out)
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_ensemble_bands failed: {rc}")
+        n_srv = self.n_srv
+        spec = (
+            ("totals", ctypes.c_uint64, (n_total, n_steps, n_acc)),
+            ("nowin", ctypes.c_int32, (n_total, n_steps)),
+            ("changes", ctypes.c_int32, (n_total, n_steps)),
+            ("cost", ctypes.c_double, (n_total, n_steps)),
+            ("final", ctypes.c_int32, (n_total, 3, n_srv)),
+            ("srv_reps_q", ctypes.c_int32, (n_q, n_steps, n_srv)),
+            ("srv_cost_q", ctypes.c_float, (n_q, n_steps, n_srv)),
+            ("mode", ctypes.c_int32, (n_steps, n_srv)),
+            ("mode_paths", ctypes.c_int32, (n_steps, n_srv)),
+            ("fleet_q", ctypes.c_int64, (n_q, n_steps, n_acc + 3)),
+        )
+        return {
+            name: _copy_out(ctypes.c_void_p(out[i]), ctype, shape)
+            for i, (name, ctype, shape) in enumerate(spec) if out[i]
+        }
+
     def hold(self, cell_scen: np.ndarray, cell_held: np.ndarray, n_acc: int):
         """wva_ctx_hold on [S, n_cells] fp32 arrivals and int32 held replicas
         (-1: the scenario's allocation is not on the cell; the tick is staged

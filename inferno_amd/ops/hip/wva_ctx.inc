@@ -148,6 +148,16 @@ struct WvaCtx {
   int roll_group = 1;  // lanes per server in wva_rollout (wva_ctx_set_topology)
   void *roll_dev;      // device [3][n_srv]
   void *roll_pin;      // its pinned source and mirror
+  // forecast ensembles (wva_ctx_ensemble_pass, wva_ctx_ensemble_bands): one
+  // device and one pinned allocation, made on first use, grown to the largest
+  // ensemble seen and freed in destroy. They are carved up per ensemble
+  // (WvaEnsLayout) when its first pass arrives; ens_next counts the paths the
+  // passes have delivered since.
+  void *ens_dev;
+  void *ens_pin;
+  size_t ens_dev_cap, ens_pin_cap;  // bytes held (0 = not allocated)
+  int ens_paths, ens_steps, ens_acc, ens_q;  // the ensemble under way (ens_paths 0 = none)
+  int ens_next;
   // capacity-limited planning (wva_ctx_plan_limited): the static greedy
   // inputs (wva_ctx_set_greedy_static) and the per-scenario workspace, both
   // allocated on first use and freed in destroy
@@ -1150,6 +1160,11 @@ extern "C" int wva_ctx_set_greedy_static(void *ctx, const int *cell_type, const 
 // With hold (wva_ctx_hold) the held replicas go up next to the arrivals, step
 // 2 launches the hold kernels, step 3 is wva_hold_reduce, and the totals block
 // holds the status counts and the deficits; everything else is the same pass.
+//
+// With ens (wva_ctx_ensemble_pass, which also brings roll for the start
+// allocation) the slices are whole paths of consecutive ticks, step 3 is
+// wva_rollout_paths, whose results stay in the ensemble arena, and step 4
+// downloads the pf / pi records only when asked and nothing else.
 struct WvaLimArgs {
   int n_types;
   const int *capacity;  // host [n_scen][n_types]
@@ -1177,13 +1192,32 @@ struct WvaTokSets {
 struct WvaHoldIn {
   const int *scen_held;  // host [n_scen][n_cells]: -1 not held, >= 0 held replicas
 };
+// The carving of the ensemble arena for one ensemble. Device: the compact
+// records, then what the pinned block mirrors at the same distances from its
+// start: the per-row aggregates (TOT..RCOST, one download), the final
+// allocations, the band outputs (SRQ..FLEET, one download).
+struct WvaEnsLayout {
+  enum { D_CODE, D_REPS, D_COST, D_TOT, D_NOWIN, D_CHG, D_RCOST, D_FIN, D_SRQ, D_SCQ, D_MODE,
+         D_MODEP, D_FLEET, D_N };
+  size_t off[D_N];
+  size_t dev_bytes, pin_bytes;
+  size_t pin(int seg) const { return off[seg] - off[D_TOT]; }  // offset in the pinned block
+};
+struct WvaEnsArgs {
+  int n_paths;  // paths of this pass; the pass's slices are n_paths x n_steps
+  int n_steps;
+  int path0;    // the pass's first path in the ensemble
+  int full;     // write and download the pf / pi records too
+  const WvaEnsLayout *lay;
+};
 
 static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arrival,
                         const WvaLimArgs *lim, const void **out_pf, const void **out_pi,
                         const void **out_totals, const WvaSloTargets *slo = nullptr,
                         const WvaRollArgs *roll = nullptr, const WvaTokSets *tok = nullptr,
-                        const WvaHoldIn *hold = nullptr) {
+                        const WvaHoldIn *hold = nullptr, const WvaEnsArgs *ens = nullptr) {
   if (c == nullptr || scen_arrival == nullptr) return -31;
+  if (ens != nullptr && (roll == nullptr || ens->n_paths * ens->n_steps != n_scen)) return -32;
   if (n_scen < 1 || n_scen > WVA_PLAN_MAX_S || n_acc < 1) return -32;
   if (hold != nullptr && (lim != nullptr || slo != nullptr || roll != nullptr || tok != nullptr))
     return -32;
@@ -1326,6 +1360,24 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
                        c->plan_out.max_rate, c->seg_start, c->n_srv, c->n_cells, n_scen, n_acc,
                        c->roll_group, c->plan_pf, c->plan_pi, c->plan_tot,
                        c->plan_tot + (size_t)n_scen * WVA_HOLD_STATUSES);
+  } else if (ens != nullptr) {
+    // the slices are ens->n_paths paths of consecutive ticks, every path
+    // chained from the same start allocation
+    const int per_block = WVA_WAVE / c->roll_group;
+    char *d = (char *)c->ens_dev;
+    const size_t *off = ens->lay->off;
+    hipLaunchKernelGGL(
+        wva_rollout_paths, dim3((c->n_srv + per_block - 1) / per_block, ens->n_paths),
+        dim3(WVA_WAVE), 0, c->s0, c->plan_out.value, c->plan_out.feasible, c->plan_out.zero_empty,
+        c->cell_acc, c->plan_out.num_replicas, c->plan_out.batch, c->plan_out.cost,
+        c->plan_out.itl, c->plan_out.ttft, c->plan_out.rho, c->plan_out.max_rate, c->seg_start,
+        c->n_srv, c->n_cells, ens->n_steps, ens->n_paths, n_acc, c->roll_group, ens->path0,
+        ens->full, c->plan_pf, c->plan_pi, (const int *)c->roll_dev,
+        (int *)(d + off[WvaEnsLayout::D_CODE]), (int *)(d + off[WvaEnsLayout::D_REPS]),
+        (float *)(d + off[WvaEnsLayout::D_COST]),
+        (unsigned long long *)(d + off[WvaEnsLayout::D_TOT]),
+        (int *)(d + off[WvaEnsLayout::D_NOWIN]), (int *)(d + off[WvaEnsLayout::D_CHG]),
+        (int *)(d + off[WvaEnsLayout::D_FIN]));
   } else if (roll != nullptr) {
     const int per_block = WVA_WAVE / c->roll_group;
     hipLaunchKernelGGL(wva_rollout, dim3((c->n_srv + per_block - 1) / per_block), dim3(WVA_WAVE),
@@ -1368,7 +1420,25 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
     if (err != hipSuccess) return (int)err;
   }
 
-  // 4. downloads
+  // 4. downloads; an ensemble pass leaves its results in the ensemble arena
+  // and downloads the records only when asked
+  if (ens != nullptr) {
+    if (ens->full) {
+      err = hipMemcpyAsync(c->plan_pin_pf, c->plan_pf,
+                           (size_t)n_scen * 6 * c->n_srv * sizeof(float), hipMemcpyDeviceToHost,
+                           c->s0);
+      if (err != hipSuccess) return (int)err;
+      err = hipMemcpyAsync(c->plan_pin_pi, c->plan_pi, (size_t)n_scen * 4 * c->n_srv * sizeof(int),
+                           hipMemcpyDeviceToHost, c->s0);
+      if (err != hipSuccess) return (int)err;
+    }
+    err = hipStreamSynchronize(c->s0);
+    if (err != hipSuccess) return (int)err;
+    c->plan_s = n_scen;
+    if (out_pf) *out_pf = c->plan_pin_pf;
+    if (out_pi) *out_pi = c->plan_pin_pi;
+    return 0;
+  }
   if (roll != nullptr) {
     err = hipMemcpyAsync(c->roll_pin, c->roll_dev, b_cur, hipMemcpyDeviceToHost, c->s0);
     if (err != hipSuccess) return (int)err;
@@ -1551,6 +1621,157 @@ extern "C" int wva_ctx_hold(void *ctx, int n_scen, int n_acc, const float *scen_
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// Forecast ensembles: n_paths rollouts of n_steps ticks from one start
+// allocation, delivered in passes of whole paths, then the order statistics
+// across the paths. Ensemble row e * n_steps + s is tick s of path e.
+// ---------------------------------------------------------------------------
+static void wva_ens_layout(const WvaCtx *c, int n_paths, int n_steps, int n_acc, int n_q,
+                           WvaEnsLayout *lay) {
+  const size_t rows = (size_t)n_paths * (size_t)n_steps;
+  const size_t b_rec = rows * (size_t)c->n_srv * 4;
+  const size_t b_band = (size_t)n_q * (size_t)n_steps * (size_t)c->n_srv * 4;
+  const size_t b_mode = (size_t)n_steps * (size_t)c->n_srv * 4;
+  const size_t size[WvaEnsLayout::D_N] = {
+      b_rec, b_rec, b_rec, rows * (size_t)n_acc * 8, rows * 4, rows * 4, rows * 8,
+      (size_t)n_paths * 3 * (size_t)c->n_srv * 4, b_band, b_band, b_mode, b_mode,
+      (size_t)n_q * (size_t)n_steps * (size_t)(n_acc + 3) * 8};
+  lay->dev_bytes = wva_arena_layout(size, WvaEnsLayout::D_N, lay->off);
+  lay->pin_bytes = lay->dev_bytes - lay->off[WvaEnsLayout::D_TOT];
+}
+
+static void wva_ens_release(WvaCtx *c) {
+  wva_arena_free(c->ens_dev, c->ens_pin);
+  c->ens_dev_cap = c->ens_pin_cap = 0;
+  c->ens_paths = c->ens_next = 0;
+}
+
+// (re)allocate the ensemble arena for a layout; on failure nothing is held and
+// reconciles and the planning calls keep working
+static int wva_ens_reserve(WvaCtx *c, const WvaEnsLayout &lay) {
+  if (lay.dev_bytes <= c->ens_dev_cap && lay.pin_bytes <= c->ens_pin_cap) return 0;
+  const size_t dcap = lay.dev_bytes > c->ens_dev_cap ? lay.dev_bytes : c->ens_dev_cap;
+  const size_t pcap = lay.pin_bytes > c->ens_pin_cap ? lay.pin_bytes : c->ens_pin_cap;
+  wva_ens_release(c);
+  if (!wva_arena_alloc(c, dcap, pcap, false, &c->ens_dev, &c->ens_pin)) return -40;
+  c->ens_dev_cap = dcap;
+  c->ens_pin_cap = pcap;
+  return 0;
+}
+
+// One pass of an ensemble of n_total paths x n_steps ticks with n_q quantiles:
+// the n_paths paths from path0 on, scen_arrival being their host [n_paths *
+// n_steps][n_cells] fp32 arrivals (req/min), n_paths * n_steps <=
+// WVA_PLAN_MAX_S. The passes of an ensemble arrive in path order; the one with
+// path0 == 0 opens it (the arena is reserved and its sums are zeroed), and
+// every pass brings the same start allocation cur_acc / cur_rep / cur_cost
+// (host [n_srv]), which the caller staged the tick with. wva_ctx_plan's
+// staging, uploads and buckets, then wva_rollout_paths; the results stay in
+// the ensemble arena. With full the pass's records are downloaded as by
+// wva_ctx_rollout: out_pf [n_paths * n_steps][6][n_srv] fp32, out_pi [..][4]
+// [n_srv] i32, pinned, valid until the next planning pass. Ends in a
+// synchronise. -40: the arena could not be allocated (the context is intact).
+extern "C" int wva_ctx_ensemble_pass(void *ctx, int n_total, int n_steps, int n_q, int n_acc,
+                                     int path0, int n_paths, const float *scen_arrival,
+                                     const int *cur_acc, const int *cur_rep,
+                                     const float *cur_cost, int full, const void **out_pf,
+                                     const void **out_pi) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || cur_acc == nullptr || cur_rep == nullptr || cur_cost == nullptr) return -31;
+  if (n_total < 1 || n_total > WVA_ENS_MAX_PATHS || n_steps < 1 || n_steps > WVA_PLAN_MAX_S ||
+      n_q < 1 || n_q > WVA_ENS_MAX_Q || n_acc < 1 || n_paths < 1 || path0 < 0 ||
+      n_paths > WVA_PLAN_MAX_S / n_steps || path0 > n_total - n_paths)
+    return -32;
+  if (c->n_cells <= 0 || c->n_srv <= 0) return -33;
+  WvaEnsLayout lay;
+  wva_ens_layout(c, n_total, n_steps, n_acc, n_q, &lay);
+  if (path0 == 0) {
+    c->ens_paths = c->ens_next = 0;
+    const int rc = wva_ens_reserve(c, lay);
+    if (rc != 0) return rc;
+    // the integer sums start from zero: TOT, NOWIN and CHG follow each other
+    if (hipMemsetAsync((char *)c->ens_dev + lay.off[WvaEnsLayout::D_TOT], 0,
+                       lay.off[WvaEnsLayout::D_RCOST] - lay.off[WvaEnsLayout::D_TOT],
+                       c->s0) != hipSuccess)
+      return -2;
+    c->ens_paths = n_total;
+    c->ens_steps = n_steps;
+    c->ens_acc = n_acc;
+    c->ens_q = n_q;
+  } else if (c->ens_paths != n_total || c->ens_steps != n_steps || c->ens_acc != n_acc ||
+             c->ens_q != n_q || c->ens_next != path0) {
+    return -32;  // not the next pass of the ensemble under way
+  }
+  const WvaRollArgs roll = {cur_acc, cur_rep, cur_cost};
+  const WvaEnsArgs ens = {n_paths, n_steps, path0, full ? 1 : 0, &lay};
+  const int rc = wva_plan_run(c, n_paths * n_steps, n_acc, scen_arrival, nullptr, out_pf, out_pi,
+                              nullptr, nullptr, &roll, nullptr, nullptr, &ens);
+  if (rc != 0) {
+    c->ens_paths = c->ens_next = 0;  // the ensemble is void
+    return rc;
+  }
+  c->ens_next = path0 + n_paths;
+  return 0;
+}
+
+// The bands of the ensemble whose last pass has run: the per-row cost sums
+// (wva_ensemble_cost), then wva_ensemble_bands with the n_q ranks (0-based,
+// below the path count), then the downloads. out[10] names pinned buffers
+// valid until the next ensemble call: per-row totals u64 [rows][n_acc],
+// servers without a winner i32 [rows], accelerator changes i32 [rows], cost
+// f64 [rows]; the final allocations i32 [paths][3][n_srv] (downloaded only
+// with want_final, else null); server replica bands i32 [n_q][n_steps][n_srv],
+// server cost bands f32 of the same shape, mode and mode_paths i32 [n_steps]
+// [n_srv]; fleet bands [n_q][n_steps][n_acc + 3] 8-byte words (i64 replica
+// totals per accelerator, servers without a winner, accelerator changes, then
+// the f64 cost). Ends in a synchronise.
+extern "C" int wva_ctx_ensemble_bands(void *ctx, const int *ranks, int n_q, int want_final,
+                                      const void **out) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || ranks == nullptr || out == nullptr) return -31;
+  if (c->ens_paths < 1 || c->ens_next != c->ens_paths || n_q != c->ens_q) return -32;
+  WvaEnsRanks rk = {};
+  for (int q = 0; q < n_q; ++q) {
+    if (ranks[q] < 0 || ranks[q] >= c->ens_paths) return -32;
+    rk.k[q] = ranks[q];
+  }
+  typedef WvaEnsLayout L;
+  L lay;
+  wva_ens_layout(c, c->ens_paths, c->ens_steps, c->ens_acc, n_q, &lay);
+  char *d = (char *)c->ens_dev, *h = (char *)c->ens_pin;
+  const int rows = c->ens_paths * c->ens_steps;
+  hipLaunchKernelGGL(wva_ensemble_cost, dim3((rows + WVA_WAVE - 1) / WVA_WAVE), dim3(WVA_WAVE), 0,
+                     c->s0, (const float *)(d + lay.off[L::D_COST]), c->n_srv, rows,
+                     (double *)(d + lay.off[L::D_RCOST]));
+  hipLaunchKernelGGL(
+      wva_ensemble_bands, dim3(c->ens_steps * (c->n_srv + c->ens_acc + 3)), dim3(WVA_WAVE), 0,
+      c->s0, (const int *)(d + lay.off[L::D_CODE]), (const int *)(d + lay.off[L::D_REPS]),
+      (const float *)(d + lay.off[L::D_COST]),
+      (const unsigned long long *)(d + lay.off[L::D_TOT]), (const int *)(d + lay.off[L::D_NOWIN]),
+      (const int *)(d + lay.off[L::D_CHG]), (const double *)(d + lay.off[L::D_RCOST]), c->n_srv,
+      c->ens_acc, c->ens_steps, c->ens_paths, n_q, rk, (int *)(d + lay.off[L::D_SRQ]),
+      (float *)(d + lay.off[L::D_SCQ]), (int *)(d + lay.off[L::D_MODE]),
+      (int *)(d + lay.off[L::D_MODEP]), (long long *)(d + lay.off[L::D_FLEET]));
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return (int)err;
+  // the aggregates, the final allocations when asked, the bands
+  const int from[3] = {L::D_TOT, L::D_FIN, L::D_SRQ};
+  const size_t to[3] = {lay.off[L::D_FIN], lay.off[L::D_SRQ], lay.dev_bytes};
+  for (int i = 0; i < 3; ++i) {
+    if (i == 1 && !want_final) continue;
+    err = hipMemcpyAsync(h + lay.pin(from[i]), d + lay.off[from[i]], to[i] - lay.off[from[i]],
+                         hipMemcpyDeviceToHost, c->s0);
+    if (err != hipSuccess) return (int)err;
+  }
+  err = hipStreamSynchronize(c->s0);
+  if (err != hipSuccess) return (int)err;
+  const int segs[10] = {L::D_TOT, L::D_NOWIN, L::D_CHG,  L::D_RCOST, L::D_FIN,
+                        L::D_SRQ, L::D_SCQ,   L::D_MODE, L::D_MODEP, L::D_FLEET};
+  for (int i = 0; i < 10; ++i) out[i] = h + lay.pin(segs[i]);
+  if (!want_final) out[4] = nullptr;
+  return 0;
+}
+
 // Per-cell outputs of the last successful wva_ctx_plan, copied into ten host
 // arrays of plan_s * n_cells elements each, in WvaCellsOut order (feasible,
 // zero_empty: u8; num_replicas, batch: i32; cost, value, itl, ttft, rho,
@@ -1591,6 +1812,7 @@ extern "C" void wva_ctx_destroy(void *ctx) {
   wva_hold_release(c);
   wva_lim_release(c);
   wva_arena_free(c->roll_dev, c->roll_pin);
+  wva_ens_release(c);
   if (c->lim_static != nullptr) (void)hipFree(c->lim_static);
   free(c->topo);
   delete c;

@@ -2133,6 +2133,328 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_rollout(
 }
 
 // ---------------------------------------------------------------------------
+// K4e wva_rollout_paths: wva_rollout for the paths of a forecast ensemble. The
+// planning sweep's slices are n_paths paths of n_steps consecutive ticks, slice
+// p * n_steps + s being tick s of the pass's p-th path; grid (server groups,
+// n_paths), block (x, p) runs wva_rollout's chain for its servers on path p.
+// Work split, value expression, selection rule and shuffle order are
+// wva_rollout's, written out here so that wva_rollout keeps its registers.
+// Every path starts from start[3][n_srv], which nobody writes.
+//
+// Per (path, tick) = ensemble row gr = (path0 + p) * n_steps + s the lane that
+// owns the winner (lane 0 of the group when there is none) writes the compact
+// record ens_code / ens_reps / ens_cost [rows][n_srv] (row-major: the stores
+// of a wave's servers are consecutive words) and adds the winner's replicas to
+// ens_tot[rows][n_acc] with the 64-bit integer atomic; lane 0 of the group
+// counts the server into ens_nowin[rows] when the tick has no winner and into
+// ens_chg[rows] when the current accelerator after the tick differs from the
+// one before (a tick without a winner changes nothing). Integer atomics on
+// words that are zero on entry: the sums do not depend on the order. After the
+// last tick the path's allocation goes to ens_fin[paths][3][n_srv].
+//
+// With `full` the pass also writes the pf / pi records of its slices and the
+// recomputed per-cell value, as wva_rollout does. No barrier, no LDS, no
+// polling; the loop runs n_steps times whatever the data.
+// ---------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_rollout_paths(
+    float *value, const uint8_t *feasible, const uint8_t *zero_empty, const int *cell_acc,
+    const int *num_replicas, const int *batch, const float *cost, const float *itl,
+    const float *ttft, const float *rho, const float *max_rate, const int *seg_start, int n_srv,
+    int n_cells, int n_steps, int n_paths, int n_acc, int group, int path0, int full, float *pf,
+    int *pi, const int *start, int *ens_code, int *ens_reps, float *ens_cost,
+    unsigned long long *ens_tot, int *ens_nowin, int *ens_chg, int *ens_fin) {
+  const int lane = (int)threadIdx.x;
+  const int sub = lane & (group - 1);
+  const int srv = (int)blockIdx.x * (WVA_WAVE / group) + lane / group;
+  const int p = (int)blockIdx.y;
+  if (p >= n_paths) return;  // whole block
+  // lanes past the last server keep an empty segment and store nothing, but
+  // stay in the loop: the shuffles below are executed by the whole wave
+  const bool live = srv < n_srv;
+  const int beg = live ? seg_start[srv] : 0;
+  const int end = live ? seg_start[srv + 1] : 0;
+  int cur_acc = live ? start[0 * n_srv + srv] : -3;
+  int cur_rep = live ? start[1 * n_srv + srv] : 0;
+  float cur_cost = live ? __int_as_float(start[2 * n_srv + srv]) : 0.0f;
+
+  for (int s = 0; s < n_steps; ++s) {
+    const size_t slice = (size_t)p * (size_t)n_steps + (size_t)s;
+    const size_t base = slice * (size_t)n_cells;
+    float best = INFINITY;
+    int best_i = -1;
+    int b_acc = -1, b_reps = 0, b_batch = 0;
+    float b_cost = 0.0f, b_itl = 0.0f, b_ttft = 0.0f, b_rho = 0.0f, b_rate = 0.0f;
+    for (int i = beg + sub; i < end; i += group) {
+      const size_t o = base + (size_t)i;
+      if (!feasible[o]) continue;
+      const bool ze = zero_empty[o] != 0;
+      const int reps = num_replicas[o];
+      const float c = cost[o];
+      const int acc = cell_acc[i];
+      const float v = wva_rollout_value(ze, reps, c, acc, cur_acc, cur_rep, cur_cost);
+      if (full) value[o] = v;
+      if (best_i == -1 || v < best) {
+        best = v;
+        best_i = i;
+        b_acc = ze ? -2 : acc;
+        b_reps = reps;
+        b_cost = c;
+        if (full) {
+          b_batch = batch[o];
+          b_itl = itl[o];
+          b_ttft = ttft[o];
+          b_rho = rho[o];
+          b_rate = max_rate[o];
+        }
+      }
+    }
+    float win = best;
+    int w = best_i;
+    for (int off = group >> 1; off > 0; off >>= 1) {
+      const float ov = __shfl_down(win, off, group);
+      const int oi = __shfl_down(w, off, group);
+      if (oi != -1 && (w == -1 || ov < win || (ov == win && oi < w))) {
+        win = ov;
+        w = oi;
+      }
+    }
+    w = __shfl(w, 0, group);
+    const size_t gr = ((size_t)path0 + (size_t)p) * (size_t)n_steps + (size_t)s;
+    const bool owner = live && w >= 0 && w == best_i;
+    if (owner || (live && w < 0 && sub == 0)) {
+      const size_t r = gr * (size_t)n_srv + (size_t)srv;
+      ens_code[r] = b_acc;
+      ens_reps[r] = b_reps;
+      ens_cost[r] = b_cost;
+      if (b_acc >= 0 && b_acc < n_acc && b_reps > 0)
+        atomicAdd(ens_tot + gr * (size_t)n_acc + (size_t)b_acc, (unsigned long long)b_reps);
+      if (full) {
+        float *gf = pf + slice * 6 * (size_t)n_srv;
+        int *gi = pi + slice * 4 * (size_t)n_srv;
+        gf[0 * n_srv + srv] = b_cost;
+        gf[1 * n_srv + srv] = owner ? best : 0.0f;
+        gf[2 * n_srv + srv] = b_itl;
+        gf[3 * n_srv + srv] = b_ttft;
+        gf[4 * n_srv + srv] = b_rho;
+        gf[5 * n_srv + srv] = b_rate;
+        gi[0 * n_srv + srv] = b_acc;
+        gi[1 * n_srv + srv] = b_reps;
+        gi[2 * n_srv + srv] = b_batch;
+        gi[3 * n_srv + srv] = w;
+      }
+    }
+    // desired -> current, on every lane of the group
+    const int src = (w >= 0) ? ((w - beg) & (group - 1)) : 0;
+    const int n_acc_code = __shfl(b_acc, src, group);
+    const int n_reps = __shfl(b_reps, src, group);
+    const float n_cost = __shfl(b_cost, src, group);
+    if (w >= 0) {
+      const int new_acc = (n_acc_code == -2) ? -1 : n_acc_code;
+      if (live && sub == 0 && new_acc != cur_acc) atomicAdd(ens_chg + gr, 1);
+      cur_acc = new_acc;
+      cur_rep = n_reps;
+      cur_cost = n_cost;
+    } else if (live && sub == 0) {
+      atomicAdd(ens_nowin + gr, 1);
+    }
+  }
+  if (live && sub == 0) {
+    int *fin = ens_fin + ((size_t)path0 + (size_t)p) * 3 * (size_t)n_srv;
+    fin[0 * n_srv + srv] = cur_acc;
+    fin[1 * n_srv + srv] = cur_rep;
+    fin[2 * n_srv + srv] = __float_as_int(cur_cost);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// K4f wva_ensemble_cost: per ensemble row the fp64 sum of the row's compact
+// fp32 costs, servers in ascending index from +0.0 (a server without a winner
+// holds 0 and is simply added). One lane per row: the n_srv adds of a row
+// depend on each other, the rows do not.
+// ---------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_ensemble_cost(
+    const float *ens_cost, int n_srv, int n_rows, double *row_cost) {
+  const int r = (int)blockIdx.x * WVA_WAVE + (int)threadIdx.x;
+  if (r >= n_rows) return;
+  const float *c = ens_cost + (size_t)r * (size_t)n_srv;
+  double sum = 0.0;
+  for (int v = 0; v < n_srv; ++v) sum += (double)c[v];
+  row_cost[r] = sum;
+}
+
+// ---------------------------------------------------------------------------
+// K4g wva_ensemble_bands: the order statistics of a forecast ensemble across
+// its n_paths <= WVA_ENS_MAX_PATHS paths, one wave per item, grid
+// n_steps * (n_srv + n_acc + 3):
+//   server item (tick s, server v): the n_q ranks among the paths' winner
+//     replicas -> srv_reps_q[n_q][n_steps][n_srv], the same among their costs
+//     (compared as floats) -> srv_cost_q, and the most frequent winner code
+//     with the number of paths that chose it (smallest code on ties) ->
+//     mode[n_steps][n_srv], mode_paths;
+//   fleet item (tick s, column c): the n_q ranks among the paths' values of
+//     column c < n_acc of the replica totals, n_acc the servers without a
+//     winner, n_acc + 1 the accelerator changes (64-bit integer keys), n_acc +
+//     2 the row cost (a double key) -> fleet_q[n_q][n_steps][n_acc + 3] 8-byte
+//     words, the last column holding doubles.
+// Path e's value of tick s is in ensemble row e * n_steps + s.
+//
+// Selection is rank by counting (wva_ens_select, the one body of every use):
+// the wave copies its keys, up to four per lane, into its LDS slice; every
+// lane then counts, for each of its keys, the keys that are smaller, or equal
+// with a lower path index, reading the same LDS word as the other lanes in
+// each step (a broadcast); the count is the key's unique rank, and the key
+// whose rank is requested is stored as that quantile. At most n_paths *
+// ceil(n_paths / 64) compares per lane. The mode counts equal codes with the
+// same loop and takes the (largest count, smallest code) over the wave with
+// shuffles, so it does not depend on how many accelerators there are.
+//
+// One-wave blocks, no barrier: a wave's LDS accesses are served in issue order,
+// and the s_waitcnt between the key stores and the counting loop completes the
+// stores before the first read (the discipline of the one-wave cell function).
+// The three key arrays are separate, so no slice is rewritten while it is read.
+// ---------------------------------------------------------------------------
+#define WVA_ENS_MAX_PATHS 256
+#define WVA_ENS_MAX_Q 8
+#define WVA_ENS_KEYS (WVA_ENS_MAX_PATHS / WVA_WAVE)  // keys per lane
+
+struct WvaEnsRanks {
+  int k[WVA_ENS_MAX_Q];
+};
+
+// cnt[t] = the rank of this lane's key t (path lane + 64 t) among the n keys
+// in lds, ties by path index
+template <typename K>
+__device__ __forceinline__ void wva_ens_rank(const K (&mine)[WVA_ENS_KEYS], K *lds, int n,
+                                             int lane, int (&cnt)[WVA_ENS_KEYS]) {
+#pragma unroll
+  for (int t = 0; t < WVA_ENS_KEYS; ++t) {
+    const int e = lane + t * WVA_WAVE;
+    if (e < n) lds[e] = mine[t];
+    cnt[t] = 0;
+  }
+  __builtin_amdgcn_s_waitcnt(0);  // one wave: the stores above before the reads below
+  for (int j = 0; j < n; ++j) {
+    const K kj = lds[j];
+#pragma unroll
+    for (int t = 0; t < WVA_ENS_KEYS; ++t) {
+      const int e = lane + t * WVA_WAVE;
+      cnt[t] += (kj < mine[t] || (kj == mine[t] && j < e)) ? 1 : 0;
+    }
+  }
+}
+
+// out[q * stride] = the key of rank ranks.k[q], for every q < n_q
+template <typename K, typename O>
+__device__ __forceinline__ void wva_ens_select(const K (&mine)[WVA_ENS_KEYS], K *lds, int n,
+                                               int lane, const WvaEnsRanks &ranks, int n_q,
+                                               O *out, size_t stride) {
+  int cnt[WVA_ENS_KEYS];
+  wva_ens_rank(mine, lds, n, lane, cnt);
+#pragma unroll
+  for (int t = 0; t < WVA_ENS_KEYS; ++t) {
+    if (lane + t * WVA_WAVE >= n) continue;
+    for (int q = 0; q < n_q; ++q)
+      if (ranks.k[q] == cnt[t]) out[(size_t)q * stride] = (O)mine[t];
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_ensemble_bands(
+    const int *ens_code, const int *ens_reps, const float *ens_cost,
+    const unsigned long long *ens_tot, const int *ens_nowin, const int *ens_chg,
+    const double *row_cost, int n_srv, int n_acc, int n_steps, int n_paths, int n_q,
+    WvaEnsRanks ranks, int *srv_reps_q, float *srv_cost_q, int *mode, int *mode_paths,
+    long long *fleet_q) {
+  __shared__ long long lds_i[WVA_ENS_MAX_PATHS];
+  __shared__ double lds_d[WVA_ENS_MAX_PATHS];
+  __shared__ int lds_c[WVA_ENS_MAX_PATHS];
+  const int lane = (int)threadIdx.x;
+  const int n_cols = n_acc + 3;
+  const int n_srv_items = n_steps * n_srv;
+  const int item = (int)blockIdx.x;
+  if (n_paths > WVA_ENS_MAX_PATHS || n_q > WVA_ENS_MAX_Q) return;
+  if (item >= n_srv_items + n_steps * n_cols) return;
+  if (item < n_srv_items) {
+    const int s = item / n_srv, v = item - s * n_srv;
+    long long kr[WVA_ENS_KEYS];
+    double kc[WVA_ENS_KEYS];
+    int code[WVA_ENS_KEYS];
+#pragma unroll
+    for (int t = 0; t < WVA_ENS_KEYS; ++t) {
+      const int e = lane + t * WVA_WAVE;
+      const size_t r = ((size_t)(e < n_paths ? e : 0) * (size_t)n_steps + (size_t)s) *
+                           (size_t)n_srv + (size_t)v;
+      kr[t] = (long long)ens_reps[r];
+      kc[t] = (double)ens_cost[r];  // exact, and ordered as the floats are
+      code[t] = ens_code[r];
+    }
+    const size_t o = (size_t)s * (size_t)n_srv + (size_t)v;
+    const size_t stride = (size_t)n_steps * (size_t)n_srv;
+    wva_ens_select(kr, lds_i, n_paths, lane, ranks, n_q, srv_reps_q + o, stride);
+    wva_ens_select(kc, lds_d, n_paths, lane, ranks, n_q, srv_cost_q + o, stride);
+    // mode: every path counts the paths that hold its code
+    int cnt[WVA_ENS_KEYS];
+#pragma unroll
+    for (int t = 0; t < WVA_ENS_KEYS; ++t) {
+      const int e = lane + t * WVA_WAVE;
+      if (e < n_paths) lds_c[e] = code[t];
+      cnt[t] = 0;
+    }
+    __builtin_amdgcn_s_waitcnt(0);  // one wave: the stores above before the reads below
+    for (int j = 0; j < n_paths; ++j) {
+      const int cj = lds_c[j];
+#pragma unroll
+      for (int t = 0; t < WVA_ENS_KEYS; ++t) cnt[t] += (cj == code[t]) ? 1 : 0;
+    }
+    int best_n = 0, best_c = 0x7fffffff;
+#pragma unroll
+    for (int t = 0; t < WVA_ENS_KEYS; ++t) {
+      if (lane + t * WVA_WAVE >= n_paths) continue;
+      if (cnt[t] > best_n || (cnt[t] == best_n && code[t] < best_c)) {
+        best_n = cnt[t];
+        best_c = code[t];
+      }
+    }
+    for (int off = WVA_WAVE / 2; off > 0; off >>= 1) {
+      const int on = __shfl_xor(best_n, off, WVA_WAVE);
+      const int oc = __shfl_xor(best_c, off, WVA_WAVE);
+      if (on > best_n || (on == best_n && oc < best_c)) {
+        best_n = on;
+        best_c = oc;
+      }
+    }
+    if (lane == 0) {
+      mode[o] = best_c;
+      mode_paths[o] = best_n;
+    }
+    return;
+  }
+  const int f = item - n_srv_items;
+  const int s = f / n_cols, col = f - s * n_cols;
+  long long *out = fleet_q + (size_t)s * (size_t)n_cols + (size_t)col;
+  const size_t stride = (size_t)n_steps * (size_t)n_cols;
+  if (col == n_acc + 2) {
+    double kc[WVA_ENS_KEYS];
+#pragma unroll
+    for (int t = 0; t < WVA_ENS_KEYS; ++t) {
+      const int e = lane + t * WVA_WAVE;
+      kc[t] = row_cost[(size_t)(e < n_paths ? e : 0) * (size_t)n_steps + (size_t)s];
+    }
+    wva_ens_select(kc, lds_d, n_paths, lane, ranks, n_q, (double *)out, stride);
+    return;
+  }
+  long long ki[WVA_ENS_KEYS];
+#pragma unroll
+  for (int t = 0; t < WVA_ENS_KEYS; ++t) {
+    const int e = lane + t * WVA_WAVE;
+    const size_t r = (size_t)(e < n_paths ? e : 0) * (size_t)n_steps + (size_t)s;
+    ki[t] = col < n_acc      ? (long long)ens_tot[r * (size_t)n_acc + (size_t)col]
+            : col == n_acc   ? (long long)ens_nowin[r]
+                             : (long long)ens_chg[r];
+  }
+  wva_ens_select(ki, lds_i, n_paths, lane, ranks, n_q, out, stride);
+}
+
+// ---------------------------------------------------------------------------
 // K4d wva_hold_reduce: the server records of a hold analysis; it takes
 // wva_plan_reduce's place. Nothing is minimised: per (server, scenario) at most
 // one cell of the server's segment carries the held flag (the host expands one

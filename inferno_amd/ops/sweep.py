@@ -289,6 +289,32 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_steps][n_acc]
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [3][n_srv] final allocation
     ]
+    # forecast ensembles (engine/fastpath.py FastSweep.rollout_ensemble)
+    lib.wva_ctx_ensemble_pass.restype = ctypes.c_int
+    lib.wva_ctx_ensemble_pass.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_int,  # paths of the ensemble (1..256)
+        ctypes.c_int,  # n_steps (1..PLAN_MAX_S)
+        ctypes.c_int,  # quantiles (1..8)
+        ctypes.c_int,  # n_acc
+        ctypes.c_int,  # first path of this pass
+        ctypes.c_int,  # paths of this pass (paths * n_steps <= PLAN_MAX_S)
+        ctypes.c_void_p,  # host fp32 [paths * n_steps][n_cells] arrival rates
+        ctypes.c_void_p,  # host i32 [n_srv] cur_acc every path starts from
+        ctypes.c_void_p,  # host i32 [n_srv] cur_rep
+        ctypes.c_void_p,  # host fp32 [n_srv] cur_cost
+        ctypes.c_int,  # write and download the pass's records
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned fp32 [paths * n_steps][6][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [paths * n_steps][4][n_srv]
+    ]
+    lib.wva_ctx_ensemble_bands.restype = ctypes.c_int
+    lib.wva_ctx_ensemble_bands.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_void_p,  # host i32 [n_q] ranks
+        ctypes.c_int,  # n_q
+        ctypes.c_int,  # download the final allocations too
+        ctypes.POINTER(ctypes.c_void_p),  # out: ten pinned result buffers
+    ]
     # hold analysis (engine/fastpath.py FastSweep.hold)
     lib.wva_ctx_hold.restype = ctypes.c_int
     lib.wva_ctx_hold.argtypes = [
