@@ -154,6 +154,7 @@ class ChainStats:
     avg_wait_time: float  # msec
     p0: float
     pK: float
+    pN: float = 0.0  # p[N]: the first of the geometric queue weights p[N+j] = p[N] r^j
 
 
 def within_tolerance(x: float, value: float, tolerance: float) -> bool:
@@ -165,7 +166,7 @@ def within_tolerance(x: float, value: float, tolerance: float) -> bool:
     return abs((x - value) / value) <= tolerance
 
 
-def binary_search(x_min, x_max, y_target, eval_fn):
+def binary_search(x_min, x_max, y_target, eval_fn, nondecreasing=False):
     """Find x* with f(x*)=y_target for monotone f over [x_min, x_max].
 
     Returns (x_star, indicator): indicator is -1 when the target lies below
@@ -174,6 +175,10 @@ def binary_search(x_min, x_max, y_target, eval_fn):
     within relative tolerance return immediately; otherwise <=100 bisection
     iterations with early exit on relative tolerance.
     Raises AnalyzerError when eval_fn fails.
+
+    ``nondecreasing`` states that f never decreases, so equal boundary values
+    count as increasing too (the reference's ``y_lo < y_hi`` test would call
+    a flat function decreasing and answer +1 where it lies above the target).
     """
     if x_min > x_max:
         raise AnalyzerError(f"invalid range [{x_min}, {x_max}]")
@@ -184,7 +189,7 @@ def binary_search(x_min, x_max, y_target, eval_fn):
     if within_tolerance(y_hi, y_target, SEARCH_TOLERANCE):
         return x_max, 0
 
-    increasing = y_lo < y_hi
+    increasing = nondecreasing or y_lo < y_hi
     if (increasing and y_target < y_lo) or (not increasing and y_target > y_lo):
         return x_min, -1  # below the bounded region
     if (increasing and y_target > y_hi) or (not increasing and y_target < y_hi):
@@ -323,6 +328,7 @@ class StateDependentChain:
             avg_wait_time=avg_wait,
             p0=p0,
             pK=pK,
+            pN=wN / Z,
         )
 
 
@@ -369,6 +375,7 @@ class QueueAnalyzer:
         self.rate_max = lambda_max * 1000.0  # req/sec
         K = cfg.max_queue_size + cfg.max_batch_size
         self.chain = StateDependentChain(K, self.serv_rate)
+        self._lgamma = None  # lgamma(j + 1), j < max_queue_size, on first wait_tail
 
     # -- internal evaluators (x is lambda in req/msec) --------------------
 
@@ -397,6 +404,106 @@ class QueueAnalyzer:
     def eval_waiting_time(self, lam: float) -> float:
         """Avg waiting time at lam (req/msec). Ref: pkg/analyzer/utils.go:84-90."""
         return self.chain.solve(lam).avg_wait_time
+
+    # -- wait-time distribution (percentile TTFT planning) ------------------
+
+    def _tail_from(self, st: ChainStats, lam: float, t: float) -> float:
+        """P(wait > t) of an accepted request from a chain solve at lam
+        (req/msec): a request that finds N + j in the system waits for j + 1
+        departures at rate mu = s(N), so with x = mu t
+        ``sum_{j<Q} p[N+j] / (1 - p[K]) * P(Pois(x) <= j)``. A plain fp64 sum over
+        all Q queue states."""
+        N, K = self.chain.N, self.chain.K
+        Q = K - N
+        if Q <= 0:
+            return 0.0
+        if t < 0:
+            return 1.0
+        mu = float(self.serv_rate[-1])
+        x = mu * t
+        log_r = math.log(lam) - math.log(mu)
+        a_N = st.pN / (1.0 - st.pK)
+        j = np.arange(Q, dtype=np.float64)
+        weights = a_N * np.exp(j * log_r)
+        if x == 0.0:
+            return float(np.sum(weights))
+        if self._lgamma is None:
+            self._lgamma = np.array([math.lgamma(i + 1.0) for i in range(Q)])
+        with np.errstate(under="ignore"):
+            pmf = np.exp(j * math.log(x) - x - self._lgamma)
+        cdf = np.minimum(np.cumsum(pmf), 1.0)
+        return float(np.sum(weights * cdf))
+
+    def wait_tail(self, lam: float, t: float) -> float:
+        """Fraction of accepted requests that wait longer than t msec in the
+        queue at arrival rate lam (req/msec, 0 < lam <= rate_max / 1000). 1 for
+        t < 0; P(wait > 0) at t = 0; its mean over t is avg_wait_time."""
+        if not 0 < lam <= self.rate_max / 1000.0:
+            raise AnalyzerError(f"lambda={lam} outside (0, {self.rate_max / 1000.0}]")
+        return self._tail_from(self.chain.solve(lam), lam, t)
+
+    def ttft_tail(self, lam: float, target_ttft: float) -> float:
+        """g(lam): the fraction of requests whose wait exceeds what the TTFT
+        target (msec, taken as float32 like the kernel's) leaves after the
+        prefill time at the effective concurrency."""
+        st = self.chain.solve(lam)
+        eff = effective_concurrency(
+            st.avg_serv_time, self.service_parms, self.request_size, self.max_batch_size
+        )
+        budget = float(np.float32(target_ttft)) - self.service_parms.prefill.prefill_time(
+            self.request_size.avg_input_tokens, eff
+        )
+        return self._tail_from(st, lam, budget)
+
+    def size_tail(self, targets: TargetPerf, q: float):
+        """size() with the TTFT target held at quantile q in (0, 1): the TTFT
+        search is for ``ttft_tail(lam) = 1 - q`` instead of mean TTFT = target;
+        the ITL search, the TPS bound and the returned triple are size()'s (the
+        achieved TTFT is still the mean)."""
+        targets.check()
+        if not 0.0 < q < 1.0:
+            raise AnalyzerError(f"quantile {q} outside (0, 1)")
+        lambda_min = self.rate_min / 1000.0
+        lambda_max = self.rate_max / 1000.0
+
+        lam_ttft = lambda_max
+        if targets.target_ttft > 0:
+            lam_ttft, ind = binary_search(
+                lambda_min, lambda_max, 1.0 - q,
+                lambda lam: self.ttft_tail(lam, targets.target_ttft), nondecreasing=True,
+            )
+            if ind < 0:
+                raise AnalyzerError(
+                    f"failed to calculate lambdaStarTTFT, targetTTFT={targets.target_ttft} "
+                    f"at quantile {q}: target is below the bounded region"
+                )
+        lam_itl = lambda_max
+        if targets.target_itl > 0:
+            lam_itl, ind = binary_search(
+                lambda_min, lambda_max, targets.target_itl, self._eval_itl
+            )
+            if ind < 0:
+                raise AnalyzerError(
+                    f"failed to calculate lambdaStarITL, targetITL={targets.target_itl}: "
+                    "target is below the bounded region"
+                )
+        lam_tps = lambda_max
+        if targets.target_tps > 0:
+            lam_tps = lambda_max * (1.0 - STABILITY_SAFETY_FRACTION)
+
+        lam = min(lam_ttft, lam_itl, lam_tps)
+        metrics = self.analyze(lam * 1000.0)
+        target_rate = TargetRate(
+            rate_target_ttft=lam_ttft * 1000.0,
+            rate_target_itl=lam_itl * 1000.0,
+            rate_target_tps=lam_tps * 1000.0,
+        )
+        achieved = TargetPerf(
+            target_ttft=metrics.avg_wait_time + metrics.avg_prefill_time,
+            target_itl=metrics.avg_token_time,
+            target_tps=metrics.throughput * float(self.request_size.avg_output_tokens),
+        )
+        return target_rate, metrics, achieved
 
     # -- public API --------------------------------------------------------
 

@@ -6,6 +6,7 @@ pkg/config wire format) and print the allocation solution.
   python -m inferno_amd.cli plan system.json --scales 0.5,1,1.5,2 [--backend ...] [--json]
       [--limited] [--capacity TYPE=N,...] [--saturation-policy P] [--delayed-best-effort]
   python -m inferno_amd.cli plan system.json --slo-scales 0.5,1,2 [--scales ...] [--json]
+  python -m inferno_amd.cli plan system.json --ttft-quantiles 0.5,0.9,0.99 [--scales ...] [--json]
   python -m inferno_amd.cli plan system.json --rollout --scales 0.5,1,2,1,0.5 [--json]
   python -m inferno_amd.cli plan system.json --hold --scales 0.5,1,2,4 [--json]
   python -m inferno_amd.cli plan system.json --ensemble-scales "0.5,1,2;0.6,1.2,2.4;0.4,0.9,1.7"
@@ -122,6 +123,13 @@ def cmd_plan(args) -> int:
     from .engine import FastSweep, SweepEngine
 
     limited = args.limited or args.capacity is not None
+    if args.ttft_quantiles is not None:
+        if (limited or args.slo_scales is not None or args.token_scales is not None
+                or args.rollout or args.hold or args.ensemble_scales is not None
+                or args.ensemble_noise is not None):
+            raise SystemExit("plan: --ttft-quantiles is an unlimited-mode plan over --scales; "
+                             "it does not combine with the other plan modes")
+        return _cmd_plan_tail(args)
     if args.ensemble_scales is not None or args.ensemble_noise is not None:
         if (limited or args.slo_scales is not None or args.token_scales is not None
                 or args.rollout or args.hold):
@@ -215,6 +223,52 @@ def cmd_plan(args) -> int:
     if limited:
         print(f"(limited mode: saturation policy {kw['saturation_policy']}, "
               f"delayed best-effort {'on' if kw['delayed_best_effort'] else 'off'})")
+    return 0
+
+
+def _cmd_plan_tail(args) -> int:
+    """Percentile TTFT plan: the unlimited-mode solution with the TTFT target
+    held at each quantile of the wait distribution, at each load scale."""
+    import numpy as np
+
+    from .engine import FastSweep, SweepEngine
+
+    quantiles = _parse_scales(args.ttft_quantiles, "--ttft-quantiles")
+    scales = _parse_scales(args.scales) if args.scales is not None else [1.0]
+    system, _ = _load_system(args.spec)
+    backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
+    fs = FastSweep(system, backend=backend)
+    try:
+        res = fs.plan_tail(quantiles, scales=scales)
+    except ValueError as e:
+        print(f"plan: {e}", file=sys.stderr)
+        return 2
+    blocks = []
+    for k, q in enumerate(quantiles):
+        rows = []
+        for s, scale in enumerate(scales):
+            late = res.wait_tail[k, s][res.winners.acc_idx[k, s] >= 0]
+            rows.append({
+                "scale": scale,
+                "totalCost": round(float(res.cost_total[k, s]), 2),
+                "replicas": {
+                    name: int(res.replicas_by_acc[k, s, j]) for j, name in enumerate(fs.acc_names)
+                },
+                "infeasibleServers": int(res.infeasible_servers[k, s]),
+                "maxLateShare": float(np.max(late)) if late.size else 0.0,
+            })
+        blocks.append({"ttftQuantile": q, "scenarios": rows})
+    if args.json:
+        print(json.dumps({"backend": backend, "servers": len(fs.server_names),
+                          "quantileScenarios": blocks}, indent=2))
+        return 0
+    for b in blocks:
+        print(f"TTFT quantile {b['ttftQuantile']:g} (at most {1 - b['ttftQuantile']:.4g} of the "
+              "requests may wait past the TTFT budget)")
+        for r in b["scenarios"]:
+            reps = " ".join(f"{n}={c}" for n, c in r["replicas"].items())
+            print(f"  load x{r['scale']:g}: cost {r['totalCost']:.2f}  {reps}  "
+                  f"infeasible {r['infeasibleServers']}  max late share {r['maxLateShare']:.4g}")
     return 0
 
 
@@ -525,6 +579,10 @@ def main() -> None:
     pp.add_argument("--slo-scales", default=None,
                     help="comma-separated factors on every TTFT and ITL target, e.g. 0.5,1,2: "
                          "one block per SLO scale (load scale 1 unless --scales is given)")
+    pp.add_argument("--ttft-quantiles", default=None,
+                    help="comma-separated quantiles in (0, 1), e.g. 0.5,0.9,0.99: size the TTFT "
+                         "target at each quantile of the wait distribution instead of the mean "
+                         "(load scale 1 unless --scales is given)")
     pp.add_argument("--token-scales", default=None,
                     help="comma-separated IN:OUT factors on every server's average input and "
                          "output tokens, e.g. 1:1,4:1,1:0.5: one block per pair (load scale 1 "

@@ -41,6 +41,9 @@ class Allocation:
     ttft: float = 0.0  # expected avg queueing + prefill time (msec)
     rho: float = 0.0
     max_arrv_rate_per_replica: float = 0.0  # req/msec
+    # percentile sizing only (create_allocation(ttft_quantile=q)): the fraction
+    # of requests whose wait exceeds the TTFT budget at the operating rate
+    wait_tail: float = 0.0
 
     @property
     def max_rpm(self) -> float:
@@ -179,8 +182,13 @@ def reallocate(system, server_name: str):
     return min_alloc, min_alloc.accelerator
 
 
-def create_allocation(system, server_name: str, acc_name: str) -> Optional[Allocation]:
+def create_allocation(system, server_name: str, acc_name: str,
+                      ttft_quantile: Optional[float] = None) -> Optional[Allocation]:
     """Size an accelerator for a server; None when infeasible.
+
+    With ``ttft_quantile`` q the TTFT target is held at that quantile of the
+    wait distribution (QueueAnalyzer.size_tail) instead of the mean, and the
+    allocation carries ``wait_tail``; chain analyzer only.
 
     Mirrors CreateAllocation (pkg/core/allocation.go:27-163):
       1. resolve server/accelerator/model-perf/SLO-target, bail on any miss;
@@ -249,7 +257,10 @@ def create_allocation(system, server_name: str, acc_name: str) -> Optional[Alloc
         target_ttft=target.ttft, target_itl=target.itl, target_tps=target.tps
     )
     try:
-        _, metrics, _ = qa.size(targets)
+        if ttft_quantile is None:
+            _, metrics, _ = qa.size(targets)
+        else:
+            _, metrics, _ = qa.size_tail(targets, ttft_quantile)
     except AnalyzerError:
         return None
     rate_star = metrics.throughput  # req/sec
@@ -280,5 +291,7 @@ def create_allocation(system, server_name: str, acc_name: str) -> Optional[Alloc
         rho=metrics.rho,
         max_arrv_rate_per_replica=rate_star / 1000.0,
     )
+    if ttft_quantile is not None:
+        alloc.wait_tail = qa.ttft_tail(rate / 1000.0, target.ttft)
     alloc.value = alloc.cost
     return alloc

@@ -94,6 +94,26 @@ class SloPlanResult:
 
 
 @dataclass
+class TailPlanResult:
+    """Percentile TTFT plan: the unlimited-mode solution of Q quantiles of the
+    TTFT target times S arrival-rate scenarios of one fleet
+    (FastSweep.plan_tail). The winners' ``ttft`` is still the MEAN TTFT."""
+
+    winners: WinnerRecord  # every array [Q, S, n_servers]
+    replicas_by_acc: np.ndarray  # int64 [Q, S, n_acc], columns = FastSweep.acc_names
+    cost_total: np.ndarray  # float64 [Q, S]: fp64 sum of the winners' fp32 cost
+    infeasible_servers: np.ndarray  # int64 [Q, S]: servers with acc_idx == -1
+    arrival: np.ndarray  # float32 [S, n_servers]: the load scenarios evaluated
+    quantiles: np.ndarray  # float64 [Q]
+    # float32 [Q, S, n_servers]: the fraction of the winner's requests that wait
+    # longer than TTFT target - prefill time at its per-replica rate (<= 1 - q
+    # up to the search tolerance); 0 for a zero-load winner, NaN without one
+    wait_tail: np.ndarray
+    # reconcile_cells() layout plus "wait_tail", arrays [Q, S, n_cells]
+    cells: Optional[dict] = None
+
+
+@dataclass
 class TokenPlanResult:
     """What-if token-mix plan: the unlimited-mode solution of W sets of
     per-server average input / output token counts times S arrival-rate
@@ -188,6 +208,8 @@ _WINNER_FIELDS = ("acc_idx", "num_replicas", "batch", "cost", "value", "itl", "t
 ENSEMBLE_MAX_PATHS = 256
 ENSEMBLE_MAX_ROWS = 4096
 ENSEMBLE_MAX_QUANTILES = 8
+# quantiles of one plan_tail() (WVA_TAIL_MAX_Q of ops/hip/wva_ctx.inc)
+TAIL_MAX_QUANTILES = 8
 ENSEMBLE_PASS_ROWS = PLAN_MAX_S
 ENSEMBLE_BYTES = 1 << 30
 
@@ -1397,6 +1419,118 @@ class FastSweep:
             t_itl=t_itl,
             cells=cells,
         )
+
+    # ------------------------------------------------------------------
+    # Percentile TTFT planning
+    # ------------------------------------------------------------------
+    def plan_tail(self, quantiles, scales=None, arrival=None,
+                  return_cells: bool = False) -> TailPlanResult:
+        """Solve Q quantiles of the TTFT target times S arrival-rate scenarios
+        of the fleet in one pass: how many replicas hold "p95 TTFT <= target",
+        and what fraction of requests still miss it.
+
+        ``quantiles``: 1 to 8 floats in the open interval (0, 1). For quantile
+        q a cell meets its TTFT target T at a rate iff at most 1 - q of the
+        accepted requests wait longer than T minus the prefill time there (the
+        chain's exact wait distribution); the ITL and TPS targets are sized as
+        ever. Load axis: ``scales`` or ``arrival`` as in plan_slo(); with
+        neither, the base load alone (S = 1). 1 <= Q * S <= 256.
+
+        The result has SloPlanResult's fields with [Q, S, ...] arrays, whose
+        ``ttft`` REMAINS THE MEAN TTFT at the chosen allocation, plus
+        ``wait_tail``. Chain analyzer only (``analyzer="mg1"`` raises
+        ValueError), unlimited mode only. The sizing memo is neither read nor
+        written, and nothing a following reconcile(), plan*(), rollout*() or
+        hold() returns changes."""
+        if getattr(self.system, "analyzer_mode", "mm1k") == "mg1":
+            raise ValueError("plan_tail() needs the chain analyzer: the M/G/1 evaluator has "
+                             "no wait distribution")
+        try:
+            qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"quantiles is not numeric: {e}") from None
+        if qs.ndim != 1 or not 1 <= qs.shape[0] <= TAIL_MAX_QUANTILES:
+            raise ValueError(
+                f"plan_tail() takes 1..{TAIL_MAX_QUANTILES} quantiles, got shape {qs.shape}")
+        if not (np.isfinite(qs).all() and (qs > 0).all() and (qs < 1).all()):
+            raise ValueError("quantiles must lie in the open interval (0, 1)")
+        if scales is None and arrival is None:
+            scen = np.ascontiguousarray(self._base_load()[0][None, :], dtype=np.float32)
+        else:
+            scen = self._plan_scenarios(scales, arrival)
+        n_q, n_load = qs.shape[0], scen.shape[0]
+        if not 1 <= n_q * n_load <= PLAN_MAX_S:
+            raise ValueError(
+                f"plan_tail() takes 1..{PLAN_MAX_S} (quantile, load) pairs, got {n_q} x {n_load}")
+        n_srv, n_acc = len(self.server_names), len(self.acc_names)
+        cells = totals = None
+        if self.backend != "gpu":
+            flat, wait_tail = self._plan_tail_cpu(scen, qs)
+        elif self.n_cells == 0 or n_acc == 0:
+            flat = _empty_winners(n_q * n_load, n_srv)
+            wait_tail = np.full((n_q * n_load, n_srv), np.nan, dtype=np.float32)
+        else:
+            self._tick(plan_arrival=scen, launch=False)  # stage + bucket layout
+            of, oi, totals, wait_tail = self._gpu.plan_tail(
+                np.ascontiguousarray(scen[:, self.cell_server], dtype=np.float32),
+                np.ascontiguousarray(1.0 - qs), n_acc,
+            )
+            flat = _winner_record(of, oi)
+            if return_cells:
+                cells = self._plan_cells_gpu(n_q * n_load)
+                cells["wait_tail"] = self._gpu.plan_tail_cells(n_q * n_load)
+                for k in CELL_KEYS + ("wait_tail",):
+                    cells[k] = cells[k].reshape(n_q, n_load, self.n_cells)
+        totals, cost_total, infeasible = self._plan_totals(flat, totals)
+        grid = (n_q, n_load)
+        return TailPlanResult(
+            winners=WinnerRecord(**{
+                f: getattr(flat, f).reshape(grid + (n_srv,)) for f in _WINNER_FIELDS
+            }),
+            replicas_by_acc=totals.reshape(grid + (n_acc,)),
+            cost_total=cost_total.reshape(grid),
+            infeasible_servers=infeasible.reshape(grid),
+            arrival=scen,
+            quantiles=qs,
+            wait_tail=wait_tail.reshape(grid + (n_srv,)),
+            cells=cells,
+        )
+
+    def _plan_tail_cpu(self, scen: np.ndarray, qs: np.ndarray):
+        """Golden path: _reconcile_cpu's winner selection per (quantile, load)
+        with every cell sized by QueueAnalyzer.size_tail (create_allocation's
+        ttft_quantile). Returns (winners [Q * S, n_srv], wait_tail)."""
+        n_srv = len(self.server_names)
+        rows, tails = [], []
+        with self._scenario_loads() as set_loads:
+            for q in qs:
+                for row in scen:
+                    set_loads(row)
+                    rec = _empty_winner(n_srv)
+                    wt = np.full(n_srv, np.nan, dtype=np.float32)
+                    for seg, name in enumerate(self.server_names):
+                        server = self.system.servers[name]
+                        best = None
+                        for acc_name in sorted(server.candidate_accelerators(self.system)):
+                            alloc = create_allocation(self.system, name, acc_name,
+                                                      ttft_quantile=float(q))
+                            if alloc is None:
+                                continue
+                            if server.cur_allocation is not None:
+                                alloc.value = server.cur_allocation.transition_penalty(alloc)
+                            if best is None or alloc.value < best.value:
+                                best = alloc
+                        if best is None:
+                            continue
+                        _set_winner(rec, seg, best, -2 if best.accelerator == ""
+                                    else self._acc_index[best.accelerator])
+                        wt[seg] = best.wait_tail
+                    rows.append(rec)
+                    tails.append(wt)
+        flat = WinnerRecord(**{
+            f: np.stack([getattr(r, f) for r in rows]) for f in _WINNER_FIELDS
+        })
+        return flat, np.stack(tails)
 
     # ------------------------------------------------------------------
     # What-if token-mix planning

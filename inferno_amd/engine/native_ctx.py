@@ -332,6 +332,35 @@ class NativeCtx:
             _copy_out(out[2], ctypes.c_uint64, (n_scen, n_acc)).astype(np.int64),
         )
 
+    def plan_tail(self, cell_scen: np.ndarray, y: np.ndarray, n_acc: int):
+        """wva_ctx_plan_tail on [S, n_cells] fp32 arrivals and [Q] fp64 tail
+        targets 1 - q (the tick is staged and the buckets are set): plan()'s
+        first three arrays with Q * S leading, slice k * S + s being quantile k
+        at arrival rates s, then the winners' wait_tail, fp32 [Q * S, n_srv]."""
+        n_load, n_q = cell_scen.shape[0], y.shape[0]
+        n_scen = n_q * n_load
+        out = [ctypes.c_void_p() for _ in range(4)]
+        rc = self._lib.wva_ctx_plan_tail(
+            self.ctx, n_q, n_scen, n_acc, cell_scen.ctypes.data, y.ctypes.data,
+            *[ctypes.byref(p) for p in out],
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_plan_tail failed: {rc}")
+        return (
+            _copy_out(out[0], ctypes.c_float, (n_scen, 6, self.n_srv)),
+            _copy_out(out[1], ctypes.c_int32, (n_scen, 4, self.n_srv)),
+            _copy_out(out[2], ctypes.c_uint64, (n_scen, n_acc)).astype(np.int64),
+            _copy_out(out[3], ctypes.c_float, (n_scen, self.n_srv)),
+        )
+
+    def plan_tail_cells(self, n_scen: int) -> np.ndarray:
+        """The per-cell wait_tail of the last plan_tail, fp32 [n_scen, n_cells]."""
+        dst = np.empty((n_scen, self.n_cells), dtype=np.float32)
+        rc = self._lib.wva_ctx_plan_tail_cells(self.ctx, dst.ctypes.data)
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_plan_tail_cells failed: {rc}")
+        return dst
+
     def tok_buckets_for(self, task_n: np.ndarray):
         """Task buckets of a token-mix plan, chosen over the flattened
         [W * n_cells] task batch sizes and cached on their bytes: [(nt, device

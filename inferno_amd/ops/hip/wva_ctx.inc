@@ -125,6 +125,17 @@ struct WvaCtx {
   float *slo_itl;    // device [T][n_cells]
   float *slo_pin_ttft;  // pinned mirrors
   float *slo_pin_itl;
+  // percentile planning (wva_ctx_plan_tail): the quantile targets, the
+  // per-cell wait_tail output and the winners' wait_tail, allocated on first
+  // use, grown to the largest slice count seen, freed in destroy
+  int tail_cap;        // slices the buffers hold (0 = not allocated)
+  void *tail_dev;      // one device allocation, carved up below
+  void *tail_pin;      // one pinned host allocation, carved up below
+  double *tail_y;      // device [8]: 1 - q per quantile
+  float *tail_cells;   // device [slices][n_cells]
+  float *tail_win;     // device [slices][n_srv]
+  double *tail_pin_y;  // pinned mirrors of tail_y / tail_win
+  float *tail_pin_win;
   // token-mix planning (wva_ctx_plan_tokens): the per-cell token sets,
   // allocated on first use, grown to the largest count seen, freed in destroy
   int tok_cap;       // token sets the buffers hold (0 = not allocated)
@@ -699,10 +710,12 @@ extern "C" int wva_ctx_set_buckets(void *ctx, int n_buckets, const int *nts,
 static int wva_run_buckets(WvaCtx *c, const WvaBucket *buckets, int n_buckets,
                            const WvaCellsIn &in, const WvaCellsOut &out, const WvaPlanArgs *plan,
                            const WvaSloArgs *slo = nullptr, const WvaTokArgs *tok = nullptr,
-                           const WvaHoldArgs *hold = nullptr) {
+                           const WvaHoldArgs *hold = nullptr, const WvaTailArgs *tail = nullptr) {
   if (n_buckets < 0 || n_buckets > WVA_MAX_BUCKETS) return -1;
-  WvaMemoRec *memo = tok != nullptr ? nullptr : c->memo;
-  unsigned *memo_cnt = tok != nullptr ? nullptr : c->memo_cnt;
+  // (token-mix and percentile planning leave the sizing memo alone)
+  const bool no_memo = tok != nullptr || tail != nullptr;
+  WvaMemoRec *memo = no_memo ? nullptr : c->memo;
+  unsigned *memo_cnt = no_memo ? nullptr : c->memo_cnt;
   if (hipEventRecord(c->e_up, c->s0) != hipSuccess) return -10;
   for (int i = 0; i < n_buckets; ++i) {
     hipStream_t s = (i == 0) ? c->s0 : c->side[i - 1];
@@ -716,7 +729,7 @@ static int wva_run_buckets(WvaCtx *c, const WvaBucket *buckets, int n_buckets,
       const int n = b.n_blocks - at < step ? b.n_blocks - at : step;
       const int rc = wva_sweep_dispatch(n, b.max_n, b.nt, b.cell_ids ? b.cell_ids + at : nullptr,
                                         c->analyzer_mode, c->cv2, s, in, out, b.g_inv,
-                                        b.g_anchor, memo, memo_cnt, plan, slo, tok, hold);
+                                        b.g_anchor, memo, memo_cnt, plan, slo, tok, hold, tail);
       if (rc != 0) return rc;
     }
     if (i > 0 && hipEventRecord(c->e_b[i - 1], s) != hipSuccess) return -12;
@@ -1003,6 +1016,35 @@ static int wva_slo_reserve(WvaCtx *c, int n_tgt) {
   return 0;
 }
 
+static void wva_tail_release(WvaCtx *c) {
+  wva_arena_free(c->tail_dev, c->tail_pin);
+  c->tail_cap = 0;
+}
+
+// (re)allocate the percentile-planning arrays for n_scen slices; on failure
+// nothing is held and reconciles and the other plans keep working
+#define WVA_TAIL_MAX_Q 8
+static int wva_tail_reserve(WvaCtx *c, int n_scen) {
+  if (n_scen <= c->tail_cap) return 0;
+  wva_tail_release(c);
+  enum { D_Y, D_WIN, D_CELLS, D_N };  // the pinned block holds the first two
+  const size_t size[D_N] = {WVA_TAIL_MAX_Q * sizeof(double),
+                            (size_t)n_scen * (size_t)c->n_srv * sizeof(float),
+                            (size_t)n_scen * (size_t)c->n_cells * sizeof(float)};
+  size_t off[D_N];
+  const size_t dev_bytes = wva_arena_layout(size, D_N, off);
+  const size_t pin_bytes = off[D_CELLS];
+  if (!wva_arena_alloc(c, dev_bytes, pin_bytes, false, &c->tail_dev, &c->tail_pin)) return -43;
+  c->tail_cap = n_scen;
+  char *d = (char *)c->tail_dev, *h = (char *)c->tail_pin;
+  c->tail_y = (double *)(d + off[D_Y]);
+  c->tail_win = (float *)(d + off[D_WIN]);
+  c->tail_cells = (float *)(d + off[D_CELLS]);
+  c->tail_pin_y = (double *)(h + off[D_Y]);
+  c->tail_pin_win = (float *)(h + off[D_WIN]);
+  return 0;
+}
+
 static void wva_tok_release(WvaCtx *c) {
   wva_arena_free(c->tok_dev, c->tok_pin);
   c->tok_cap = 0;
@@ -1161,6 +1203,13 @@ extern "C" int wva_ctx_set_greedy_static(void *ctx, const int *cell_type, const 
 // 2 launches the hold kernels, step 3 is wva_hold_reduce, and the totals block
 // holds the status counts and the deficits; everything else is the same pass.
 //
+// With tail (wva_ctx_plan_tail) the n_scen slices are n_q quantiles of the
+// TTFT target times n_scen / n_q arrival-rate scenarios, quantile-major: the
+// targets 1 - q go up as doubles, step 2 launches the percentile kernels, which
+// also fill the per-cell wait_tail, and after step 3 (wva_plan_reduce,
+// unchanged) wva_tail_gather picks the winners' wait_tail, which comes down
+// with the records; everything else is the same pass.
+//
 // With ens (wva_ctx_ensemble_pass, which also brings roll for the start
 // allocation) the slices are whole paths of consecutive ticks, step 3 is
 // wva_rollout_paths, whose results stay in the ensemble arena, and step 4
@@ -1189,6 +1238,10 @@ struct WvaTokSets {
   const WvaBucket *buckets;  // the pass's task buckets
   int n_buckets;
 };
+struct WvaTailIn {
+  int n_q;
+  const double *y;  // host [n_q]: 1 - q
+};
 struct WvaHoldIn {
   const int *scen_held;  // host [n_scen][n_cells]: -1 not held, >= 0 held replicas
 };
@@ -1215,8 +1268,13 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
                         const WvaLimArgs *lim, const void **out_pf, const void **out_pi,
                         const void **out_totals, const WvaSloTargets *slo = nullptr,
                         const WvaRollArgs *roll = nullptr, const WvaTokSets *tok = nullptr,
-                        const WvaHoldIn *hold = nullptr, const WvaEnsArgs *ens = nullptr) {
+                        const WvaHoldIn *hold = nullptr, const WvaEnsArgs *ens = nullptr,
+                        const WvaTailIn *tail = nullptr) {
   if (c == nullptr || scen_arrival == nullptr) return -31;
+  if (tail != nullptr && (lim != nullptr || slo != nullptr || roll != nullptr || tok != nullptr ||
+                          hold != nullptr || tail->n_q < 1 || tail->n_q > WVA_TAIL_MAX_Q ||
+                          n_scen % tail->n_q != 0))
+    return -32;
   if (ens != nullptr && (roll == nullptr || ens->n_paths * ens->n_steps != n_scen)) return -32;
   if (n_scen < 1 || n_scen > WVA_PLAN_MAX_S || n_acc < 1) return -32;
   if (hold != nullptr && (lim != nullptr || slo != nullptr || roll != nullptr || tok != nullptr))
@@ -1243,6 +1301,10 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
     rc = wva_tok_reserve(c, tok->n_tok);
     if (rc != 0) return rc;
   }
+  if (tail != nullptr) {
+    rc = wva_tail_reserve(c, n_scen);
+    if (rc != 0) return rc;
+  }
   if (lim != nullptr) {
     rc = wva_lim_reserve(c, n_scen, lim->n_types);
     if (rc != 0) return rc;
@@ -1255,7 +1317,8 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   // token-mix plan
   const int n_load = slo != nullptr   ? n_scen / slo->n_tgt
                      : tok != nullptr ? n_scen / tok->n_tok
-                                      : n_scen;
+                     : tail != nullptr ? n_scen / tail->n_q
+                                       : n_scen;
   const size_t cells = (size_t)n_load * (size_t)c->n_cells;
   hipError_t err;
 
@@ -1281,6 +1344,12 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
                          hipMemcpyHostToDevice, c->s0);
     if (err != hipSuccess) return (int)err;
     err = hipMemcpyAsync(c->slo_itl, c->slo_pin_itl, tcells * sizeof(float),
+                         hipMemcpyHostToDevice, c->s0);
+    if (err != hipSuccess) return (int)err;
+  }
+  if (tail != nullptr) {
+    for (int k = 0; k < tail->n_q; ++k) c->tail_pin_y[k] = tail->y[k];
+    err = hipMemcpyAsync(c->tail_y, c->tail_pin_y, (size_t)tail->n_q * sizeof(double),
                          hipMemcpyHostToDevice, c->s0);
     if (err != hipSuccess) return (int)err;
   }
@@ -1337,6 +1406,10 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
     const WvaTokArgs ta = {c->n_cells, n_load, c->plan_scen, tok->n_tok};
     rc = wva_run_buckets(c, tok->buckets, tok->n_buckets, tin, c->plan_out, nullptr, nullptr,
                          &ta);
+  } else if (tail != nullptr) {
+    const WvaTailArgs ta = {c->n_cells, n_load, c->plan_scen, tail->n_q, c->tail_y, c->tail_cells};
+    rc = wva_run_buckets(c, c->buckets, c->n_buckets, c->in, c->plan_out, nullptr, nullptr,
+                         nullptr, nullptr, &ta);
   } else if (slo != nullptr) {
     const WvaSloArgs sa = {c->n_cells, n_load,       c->plan_scen,
                            slo->n_tgt, c->slo_ttft, c->slo_itl};
@@ -1411,6 +1484,17 @@ static int wva_plan_run(WvaCtx *c, int n_scen, int n_acc, const float *scen_arri
   }
   err = hipGetLastError();
   if (err != hipSuccess) return (int)err;
+  if (tail != nullptr) {
+    hipLaunchKernelGGL(wva_tail_gather, dim3((c->n_srv + WVA_WAVE - 1) / WVA_WAVE, n_scen),
+                       dim3(WVA_WAVE), 0, c->s0, c->plan_pi, c->tail_cells, c->n_srv, c->n_cells,
+                       c->tail_win);
+    err = hipGetLastError();
+    if (err != hipSuccess) return (int)err;
+    err = hipMemcpyAsync(c->tail_pin_win, c->tail_win,
+                         (size_t)n_scen * (size_t)c->n_srv * sizeof(float), hipMemcpyDeviceToHost,
+                         c->s0);
+    if (err != hipSuccess) return (int)err;
+  }
   if (lim != nullptr) {
     err = hipMemcpyAsync(c->lim_pin_capacity, c->lim_capacity, n_capacity * sizeof(int),
                          hipMemcpyDeviceToHost, c->s0);
@@ -1511,6 +1595,40 @@ extern "C" int wva_ctx_plan_slo(void *ctx, int n_tgt, int n_scen, int n_acc,
   const WvaSloTargets slo = {n_tgt, scen_ttft, scen_itl};
   return wva_plan_run((WvaCtx *)ctx, n_scen, n_acc, scen_arrival, nullptr, out_pf, out_pi,
                       out_totals, &slo);
+}
+
+// One percentile-planning pass: n_q quantiles of the TTFT target times n_load =
+// n_scen / n_q arrival-rate scenarios, n_scen slices in all (1..WVA_PLAN_MAX_S),
+// slice k * n_load + s being quantile k at arrival rates s. scen_arrival: host
+// [n_load][n_cells] fp32 (req/min); y: host [n_q] fp64, 1 - q (1..8 of them).
+// Staging, buckets and the three out pointers are as for wva_ctx_plan;
+// out_wait_tail: pinned fp32 [n_scen][n_srv], the winners' wait_tail (NaN: no
+// winner). Chain analyzer only (-6). -43: the arrays of this pass could not be
+// allocated (the context is intact).
+extern "C" int wva_ctx_plan_tail(void *ctx, int n_q, int n_scen, int n_acc,
+                                 const float *scen_arrival, const double *y, const void **out_pf,
+                                 const void **out_pi, const void **out_totals,
+                                 const void **out_wait_tail) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || y == nullptr) return -31;
+  const WvaTailIn tail = {n_q, y};
+  const int rc = wva_plan_run(c, n_scen, n_acc, scen_arrival, nullptr, out_pf, out_pi, out_totals,
+                              nullptr, nullptr, nullptr, nullptr, nullptr, &tail);
+  if (rc != 0) return rc;
+  if (out_wait_tail) *out_wait_tail = c->tail_pin_win;
+  return 0;
+}
+
+// The per-cell wait_tail of the last successful wva_ctx_plan_tail, copied into
+// a host array of plan_s * n_cells floats (next to wva_ctx_plan_cells).
+extern "C" int wva_ctx_plan_tail_cells(void *ctx, float *dst) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || dst == nullptr || c->plan_s < 1 || c->plan_s > c->tail_cap) return -31;
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -1;
+  if (hipMemcpy(dst, c->tail_cells, (size_t)c->plan_s * (size_t)c->n_cells * sizeof(float),
+                hipMemcpyDeviceToHost) != hipSuccess)
+    return -2;
+  return 0;
 }
 
 // One forecast-rollout pass: the n_steps rows of scen_arrival ([n_steps]
@@ -1809,6 +1927,7 @@ extern "C" void wva_ctx_destroy(void *ctx) {
   wva_plan_release(c);
   wva_slo_release(c);
   wva_tok_release(c);
+  wva_tail_release(c);
   wva_hold_release(c);
   wva_lim_release(c);
   wva_arena_free(c->roll_dev, c->roll_pin);

@@ -301,12 +301,22 @@ struct ChainGeom {
   int ksub;                // anchors per lane = ceil(chunk/SUB)
 };
 
+// What the wait-time tail (chain_wait_tail) needs from a chain evaluation
+// besides ChainOut: the queue states' weights are a_N * r^j, j = 0..Q-1.
+struct ChainAux {
+  double a_N;    // p[N] / (1 - p[K])
+  double log_r;  // log(lam / s(N))
+};
+
 // Geometric tail (n = N+1..K, ratio r = lam/s(N)) + final chain statistics
 // from the reduced head sums. Pure scalar fp64; factored out so chain_eval
 // can run it on one wave per part and broadcast (see epilogue there).
+// AUX also fills *aux; the default instantiation is the code it always was.
+template <bool AUX = false>
 __device__ __forceinline__ ChainOut chain_tail_stats(double lam, double loglam, double logsN,
                                                      double S_total, int N, int K, double m,
-                                                     double head_sum, double head_n_sum) {
+                                                     double head_sum, double head_n_sum,
+                                                     ChainAux *aux = nullptr) {
   const double log_r = loglam - logsN;
   const double r = exp(log_r);
   const double wN = exp((double)N * loglam - S_total - m);
@@ -342,6 +352,10 @@ __device__ __forceinline__ ChainOut chain_tail_stats(double lam, double loglam, 
   const double resp = avg_n_sys / o.throughput;
   o.serv = avg_n_serv / o.throughput;
   o.wait = fmax(resp - o.serv, 0.0);
+  if constexpr (AUX) {
+    aux->a_N = (wN / Z) / (1.0 - pK);
+    aux->log_r = log_r;
+  }
   return o;
 }
 
@@ -350,9 +364,9 @@ __device__ __forceinline__ ChainOut chain_tail_stats(double lam, double loglam, 
 // each half-block independently evaluates its own lam (each half covers all
 // N states by walking two lane-chunks), enabling the concurrent TTFT/ITL
 // bisections.
-template <int NT, int PART>
+template <int NT, int PART, bool AUX = false>
 __device__ ChainOut chain_eval(double lam, const ChainGeom &g, double logsN, int N, int K,
-                               double *scratch) {
+                               double *scratch, ChainAux *aux = nullptr) {
   constexpr int W = NT / PART;
   // the thread's index within its part. W divides 64 for a one-wave cell, so
   // threadIdx.x % W is also right when such a cell is one wave of a wider
@@ -394,6 +408,17 @@ __device__ ChainOut chain_eval(double lam, const ChainGeom &g, double logsN, int
       // SQ_WAIT_ANY was 50% of wave cycles). Arithmetic order is unchanged
       // (bit-identical results).
       int j = j0 + 1;
+      if constexpr (AUX) {
+        // exact geometry (wva_build_geom<.., true>): the table holds the fp32
+        // rates themselves and the factor is an fp64 quotient, so the head
+        // sums carry fp64 rounding only; this loop then runs to jend and the
+        // three below do nothing
+        for (; j <= jend; ++j) {
+          w *= lam / (double)g.inv_s_t[j * NT + c];
+          head_sum += w;
+          head_n_sum += (double)(n0c + j) * w;
+        }
+      }
       for (; j + 7 <= jend; j += 8) {
         double f[8];
 #pragma unroll
@@ -443,13 +468,15 @@ __device__ ChainOut chain_eval(double lam, const ChainGeom &g, double logsN, int
   if constexpr (NWH_T > 1) {
     __syncthreads();  // scratch handoff from red_sum2_p
     if (lane < WVA_WAVE) {
-      o = chain_tail_stats(lam, loglam, logsN, g.S_total, N, K, m, head_sum, head_n_sum);
+      o = chain_tail_stats<AUX>(lam, loglam, logsN, g.S_total, N, K, m, head_sum, head_n_sum,
+                                aux);
       if (lane == 0) {
         const int part = threadIdx.x / W;
         scratch[part * 4 + 0] = o.throughput;
         scratch[part * 4 + 1] = o.wait;
         scratch[part * 4 + 2] = o.serv;
         scratch[part * 4 + 3] = o.in_servers;
+        if constexpr (AUX) scratch[8 + part] = aux->a_N;  // behind the two parts' four
       }
     }
     __syncthreads();
@@ -458,12 +485,160 @@ __device__ ChainOut chain_eval(double lam, const ChainGeom &g, double logsN, int
     o.wait = scratch[part * 4 + 1];
     o.serv = scratch[part * 4 + 2];
     o.in_servers = scratch[part * 4 + 3];
+    if constexpr (AUX) {
+      aux->a_N = scratch[8 + part];
+      aux->log_r = loglam - logsN;  // as chain_tail_stats forms it
+    }
   } else {
     // single-wave part: lockstep execution makes the redundancy free (and the
     // one-wave cell stays barrier-free, which the fused tick relies on)
-    o = chain_tail_stats(lam, loglam, logsN, g.S_total, N, K, m, head_sum, head_n_sum);
+    o = chain_tail_stats<AUX>(lam, loglam, logsN, g.S_total, N, K, m, head_sum, head_n_sum, aux);
   }
   return o;
+}
+
+// ---------------------------------------------------------------------------
+// Wait-time tail of the chain: the probability that an accepted request waits
+// longer than t msec before it enters the batch.
+//
+// A request that finds n = N + j requests in the system (j = 0..Q-1, Q = K - N)
+// waits for j + 1 departures at rate mu = s(N), an Erlang(j + 1, mu) time, so
+// with x = mu * t
+//   tail(lam, t) = sum_{j=0}^{Q-1} c_j F(j),   c_j = p[N+j] / (1 - p[K]) = a_N r^j,
+//   F(j) = P(Pois(x) <= j) = e^-x sum_{i<=j} x^i / i!.
+// t < 0 gives 1, Q = 0 gives 0, t = 0 gives P(wait > 0) = sum c_j.
+//
+// Window. With L = WVA_TAIL_L and delta = e^-L (8.8e-27), the Chernoff bounds
+//   P(Pois(x) <= x - d) <= exp(-d^2 / (2x)),
+//   P(Pois(x) >= x + d) <= exp(-d^2 / (2 (x + d/3)))
+// give P(Pois(x) < j_lo) <= delta for j_lo = floor(x - sqrt(2 x L)) and
+// P(Pois(x) > j_hi) <= delta for j_hi = ceil(x + L/3 + sqrt(L^2/9 + 2 x L))
+// (the root of d^2 = 2 L (x + d/3)). So F(j) < delta below the window, where
+// the terms are dropped; F(j) > 1 - delta above it, where F is taken as 1 and
+// the remainder sum_{j>j_hi} c_j is the geometric closed form; and inside it
+// F(j) is summed from j_lo, which misses less than delta. The c_j are
+// non-negative and sum to at most 1, so delta bounds the absolute error of the
+// result, 1e-10 of an fp64 ulp of 1. The window depends on (lam, t) only and
+// is about 2 sqrt(2 x L) + L/3 = 22 sqrt(x) + 20 states wide whatever Q is.
+//
+// Inside the window (clipped to [0, Q-1]) each of the W = NT / PART lanes owns
+// a contiguous run of j: it takes the Poisson pmf f at the run's start in log
+// space (wva_pois_log_pmf), advances it by f(i+1) = f(i) x / (i+1), keeps the
+// run's local CDF, and takes c_j from one exp(j log r) and then by
+// multiplication. The lanes' run totals are combined by a __shfl_up scan (and
+// across the waves of a wider part through the reduction scratch), the lane's
+// sum_j c_j (before + local CDF_j) goes through red_sum2_p. Registers and
+// shuffles only: no geometry is read, so one code path serves every N tier.
+//
+// Barriers: a part of at most one wave executes none. A wider part executes
+// four (two for the scan, two in red_sum2_p) on EVERY call, whatever the
+// arguments are: all of the special cases above are an empty window, not an
+// early return. `live` = false is the empty window too: the ITL half of the
+// dual bisection calls it that way, only to keep in step with the TTFT half.
+//
+// lam is taken in (0, s(N)): r < 1, so r^j cannot overflow. Every lane of the
+// part returns the same value.
+// ---------------------------------------------------------------------------
+#define WVA_TAIL_L 60.0
+
+// log of the Poisson pmf e^-x x^i / i! for integer-valued i >= 0 and x > 0.
+// i log x - x - lgamma(i + 1) is used as it stands below 16, where its terms
+// are small. Above, the three terms are ~ x log x each and cancel to O(1),
+// which would cost |x log x| ulps (1e-11 at x = 2e4); the saddle-point form
+//   -log sqrt(2 pi i) - stirlerr(i) - i (v - log1p(v)),  v = (x - i) / i,
+// (Loader 2000) has no large term: its error is ~|x - i| ulps, below 2e-13
+// over any window. stirlerr is lgamma's Stirling remainder, 1e-14 at i = 16.
+__device__ __forceinline__ double wva_pois_log_pmf(double i, double x) {
+  if (i < 16.0) return i * log(x) - x - lgamma(i + 1.0);
+  const double v = (x - i) / i;
+  const double i2 = 1.0 / (i * i);
+  const double stirlerr =
+      (1.0 / 12.0 - (1.0 / 360.0 - (1.0 / 1260.0 - (1.0 / 1680.0) * i2) * i2) * i2) / i;
+  return -0.5 * log(6.283185307179586477 * i) - stirlerr - i * (v - log1p(v));
+}
+
+template <int NT, int PART>
+__device__ double chain_wait_tail(bool live, double lam, double t, double mu, int N, int K,
+                                  double a_N, double log_r, double *scratch) {
+  constexpr int W = NT / PART;
+  static_assert(NT > WVA_WAVE || WVA_WAVE % W == 0, "one-wave cell: W must divide the wave");
+  const int lane = threadIdx.x % W;
+  const int Q = K - N;
+  const double x = mu * t;
+
+  // the window [lo, hi] (empty: hi < lo) and rem0, the first j of the
+  // remainder with F = 1 (Q: none). Uniform over the part.
+  int lo = 0, hi = -1, rem0 = Q;
+  const bool one = live && t < 0.0;
+  if (live && !one && Q > 0 && a_N > 0.0 && lam > 0.0 && log_r < 0.0) {
+    if (x == 0.0) {
+      rem0 = 0;
+    } else {
+      const double jlo = floor(x - sqrt(2.0 * x * WVA_TAIL_L));
+      const double jhi = ceil(x + WVA_TAIL_L / 3.0 +
+                              sqrt(WVA_TAIL_L * WVA_TAIL_L / 9.0 + 2.0 * x * WVA_TAIL_L));
+      if (jlo <= (double)(Q - 1)) {  // else every term lies below the window
+        lo = jlo > 0.0 ? (int)jlo : 0;
+        hi = jhi < (double)(Q - 1) ? (int)jhi : Q - 1;
+        rem0 = hi + 1;
+      }
+    }
+  }
+
+  // the lane's run [i0, i1] of the window
+  const int n_win = hi - lo + 1;
+  const int len = (n_win + W - 1) / W;
+  const int i0 = lo + lane * len;
+  const int i1 = min(i0 + len - 1, hi);
+  double cdf = 0.0, acc = 0.0, csum = 0.0;
+  if (i0 <= i1) {
+    const double r = exp(log_r);
+    double f = exp(wva_pois_log_pmf((double)i0, x));
+    double c = a_N * exp((double)i0 * log_r);
+    for (int i = i0; i <= i1; ++i) {
+      cdf += f;         // local CDF: sum of f over [i0, i]
+      acc += c * cdf;
+      csum += c;
+      f *= x / (double)(i + 1);
+      c *= r;
+    }
+  }
+
+  // exclusive scan of the run totals: `before` = sum of f over [lo, i0)
+  constexpr int SW = W < WVA_WAVE ? W : WVA_WAVE;
+  double incl = cdf;
+#pragma unroll
+  for (int off = 1; off < SW; off <<= 1) {
+    const double v = __shfl_up(incl, off, SW);
+    if ((lane & (SW - 1)) >= off) incl += v;
+  }
+  double before = __shfl_up(incl, 1, SW);
+  if ((lane & (SW - 1)) == 0) before = 0.0;
+  if constexpr (W > WVA_WAVE) {
+    constexpr int NWH = W / WVA_WAVE;
+    const int part = threadIdx.x / W;
+    const int widx = lane / WVA_WAVE;
+    __syncthreads();  // the scratch may still be read (chain_eval's broadcast)
+    if ((lane & (WVA_WAVE - 1)) == WVA_WAVE - 1) scratch[part * NWH + widx] = incl;
+    __syncthreads();
+    for (int w = 0; w < widx; ++w) before += scratch[part * NWH + w];
+  }
+  double sum = acc + before * csum, unused = 0.0;
+  red_sum2_p<NT, PART>(sum, unused, scratch);
+
+  // remainder a_N sum_{j=rem0}^{Q-1} r^j = a_N r^rem0 (1 - r^n) / (1 - r), the
+  // expm1-stable form of chain_tail_stats; near r = 1 the series to first order
+  // in n log r (error (n log r)^2 / 6 < 2e-17 relative under the threshold)
+  double rem = 0.0;
+  if (rem0 < Q) {
+    const double n = (double)(Q - rem0);
+    const double z = n * log_r;
+    const double geo = fabs(z) < 1e-8 ? n * (1.0 + 0.5 * (n - 1.0) * log_r)
+                                      : expm1(z) / expm1(log_r);
+    rem = a_N * exp((double)rem0 * log_r) * geo;
+  }
+  if (live && !one && !(lam > 0.0 && log_r < 0.0)) return NAN;  // lam outside (0, s(N))
+  return one ? 1.0 : sum + rem;
 }
 
 // ---------------------------------------------------------------------------
@@ -538,7 +713,7 @@ struct WvaModel {
 struct WvaEval {
   double tput, wait, eff, rho;
 };
-template <int NT, int PART>
+template <int NT, int PART, bool AUX = false>
 __device__ __forceinline__ WvaEval wva_evaluate(double lam, const WvaCell &c, const WvaModel &m) {
   WvaEval e;
   if (m.mode == 1) {
@@ -548,7 +723,14 @@ __device__ __forceinline__ WvaEval wva_evaluate(double lam, const WvaCell &c, co
     e.eff = o.eff;
     e.rho = o.rho;
   } else {
-    ChainOut o = chain_eval<NT, PART>(lam, m.g, m.logsN, c.N, m.Kstates, m.scratch);
+    // (AUX: the cell's geometry is the exact one, see chain_eval)
+    ChainOut o;
+    if constexpr (AUX) {
+      ChainAux aux;
+      o = chain_eval<NT, PART, true>(lam, m.g, m.logsN, c.N, m.Kstates, m.scratch, &aux);
+    } else {
+      o = chain_eval<NT, PART>(lam, m.g, m.logsN, c.N, m.Kstates, m.scratch);
+    }
     e.tput = o.throughput;
     e.wait = o.wait;
     e.eff = effective_concurrency(o.serv, c.gamma, c.alpha, c.delta, c.beta, c.in_tok, c.out_tok,
@@ -804,7 +986,7 @@ __device__ __forceinline__ void wva_write_zero(const WvaCellsOut &out, SlotT o, 
 // rate arr (req/min), written to output slot o (ref allocation.go:134-163).
 // rate_star is the sized per-replica rate (req/sec). Every thread of the block
 // calls this with the same arguments.
-template <int NT, typename SlotT>
+template <int NT, bool AUX = false, typename SlotT>
 __device__ __forceinline__ void wva_eval_scenario(const WvaCellsOut &out, SlotT o, float arr,
                                                   double rate_star, const WvaCell &c,
                                                   const WvaModel &m) {
@@ -823,7 +1005,7 @@ __device__ __forceinline__ void wva_eval_scenario(const WvaCellsOut &out, SlotT 
 
   // ---- per-replica analyze (ref allocation.go:148-157) ----
   const double rate = total_rate / (double)num_replicas;
-  const WvaEval e = wva_evaluate<NT, 1>(rate / 1000.0, c, m);
+  const WvaEval e = wva_evaluate<NT, 1, AUX>(rate / 1000.0, c, m);
   const float prefill_t = prefill_time_f(c.gamma, c.delta, c.in_tok, (float)e.eff);
   const float token_t = decode_time_f(c.alpha, c.beta, (float)e.eff);
 
@@ -1063,7 +1245,28 @@ __device__ __forceinline__ void wva_write_infeasible(const WvaCellsOut &out, con
 __device__ __forceinline__ int wva_num_decode(const WvaCell &c) {
   return (c.in_tok == 0 && c.out_tok == 1) ? 1 : c.out_tok - 1;
 }
-template <int NT, bool GMEM>
+// s(n) in fp32 with every operation rounded on its own, in the order
+// build_service_rates (analyzer/queue.py) applies them
+__device__ __forceinline__ float wva_rate_exact(const WvaCell &c, int num_decode, int n) {
+#pragma clang fp contract(off)
+  const float nf = (float)n;
+  float prefill = 0.0f;
+  if (c.in_tok != 0) {
+    const float slope = c.delta * (float)c.in_tok;
+    const float var = slope * nf;
+    prefill = c.gamma + var;
+  }
+  const float step = c.beta * nf;
+  const float decode = c.alpha + step;
+  const float dec = (float)num_decode * decode;
+  const float den = prefill + dec;
+  return nf / den;
+}
+// EXACT (the percentile kernels): the rates are rounded after every operation
+// as build_service_rates rounds them (no fused multiply-add), and the table
+// holds the fp32 rates themselves for chain_eval<.., AUX = true> to divide by,
+// so that nothing of the chain is rounded to fp32 but the rates.
+template <int NT, bool GMEM, bool EXACT = false>
 __device__ __forceinline__ bool wva_build_geom(const WvaCell &c, int tid, int analyzer_mode,
                                                double *smem, unsigned slab, int max_n,
                                                float *g_inv, double *g_anchor, ChainGeom &geom) {
@@ -1096,10 +1299,11 @@ __device__ __forceinline__ bool wva_build_geom(const WvaCell &c, int tid, int an
     float prefill = (c.in_tok == 0) ? 0.0f : (c.gamma + c.delta * (float)c.in_tok * nf);
     float decode = c.alpha + c.beta * nf;
     float s = nf / (prefill + (float)num_decode * decode);  // fp32 like the reference
+    if constexpr (EXACT) s = wva_rate_exact(c, num_decode, n);
     bad_rate = bad_rate || !(s > 0.0f) || !isfinite(s);
     local += log((double)s);
     const int j = n - n0;
-    inv_s_t[j * NT + tid] = (float)(1.0 / (double)s);
+    inv_s_t[j * NT + tid] = EXACT ? s : (float)(1.0 / (double)s);
     if ((j % WVA_SUB) == 0) S_anchor[tid * ksub + j / WVA_SUB] = local;  // chunk-local
   }
   // scan of per-thread chunk totals: intra-wave in registers...
@@ -1749,6 +1953,390 @@ __global__ void __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
 }
 
 // ---------------------------------------------------------------------------
+// Percentile TTFT planning, K1 as wva_tail_plan_t<NT>: n_q quantiles of the
+// TTFT target times n_load arrival rates. For quantile q the cell meets its
+// TTFT target T at rate lam iff at most 1 - q of the accepted requests wait
+// longer than what T leaves after the prefill:
+//   g(lam) = tail(lam, T - prefill_time(in_tok, eff(lam))) <= y = 1 - q,
+// with eval_metric's prefill term, each fp32 operation rounded on its own as the
+// golden rounds it (wva_prefill_exact). The kernels run the exact variant of
+// the chain (wva_build_geom<.., EXACT>, chain_eval<.., AUX>): a_N and mu decide
+// the tail, and the reconcile chain's fp32 table is 1e-7 off. The
+// TTFT half of the dual bisection searches g for y (formed in fp64 on the
+// host), the ITL half the mean ITL as ever; the TPS bound, the minimum of the
+// three, the sized-rate evaluation and wva_eval_scenario are unchanged, so the
+// ten outputs keep their meanings (ttft stays the MEAN). One more per-slot
+// output, wait_tail: g at the per-replica operating rate, 0 for a zero-load
+// slot, NaN for an infeasible one.
+//
+// g never decreases in lam (the tail grows, the budget shrinks), so the search
+// takes it as increasing also when both ends are equal: a budget that is
+// negative at every rate (g = 1 throughout) is the infeasible verdict -1, not
+// the +1 the reference's `y_lo < y_hi` test would give a flat function.
+//
+// A sibling of wva_cell_body, as wva_hold_body is and for the same reason: the
+// existing kernels keep their code only if their body and dual_bisect are left
+// alone. One block per cell looping over the quantiles (the SLO plan's form):
+// the geometry is built once per cell and the pass runs on the context's
+// buckets as they are. Chain analyzer only. No sizing memo: its key has no q.
+//
+// Uniformity: the quantiles, T and every exit depend on the cell, on (cell, k)
+// or on (cell, s) only; both halves of dual_bisect_tail call chain_eval and
+// chain_wait_tail once per step, so the barrier counts of a multi-wave cell
+// match, and a one-wave cell executes none. Outputs are stored by thread 0.
+// ---------------------------------------------------------------------------
+// the percentile kernels are compiled without packed fp32 arithmetic (a device
+// feature: the host pass does not know it)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define WVA_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define WVA_NO_PK_F32
+#endif
+
+struct WvaTailArgs {
+  int n_cells;
+  int n_load;
+  const float *scen_arrival;  // device, [n_load][n_cells]
+  int n_q;
+  const double *y;   // device, [n_q]: 1 - q
+  float *wait_tail;  // device, [n_q][n_load][n_cells]
+};
+
+// prefill_time_f with every operation rounded on its own, as the golden's
+// PrefillParms.prefill_time rounds them: the budget T - prefill decides g
+__device__ __forceinline__ float wva_prefill_exact(const WvaCell &c, float b) {
+#pragma clang fp contract(off)
+  if (c.in_tok == 0) return 0.0f;
+  const float slope = c.delta * (float)c.in_tok;
+  const float var = slope * b;
+  return c.gamma + var;
+}
+
+// kind 0: g(lam) for TTFT target t_ttft, kind 1: mean ITL at rate lam. kind is
+// uniform over the part. Kind 1 runs the tail on an empty window (see there).
+template <int NT, int PART>
+__device__ __forceinline__ double tail_metric(int kind, double lam, float t_ttft, const WvaCell &c,
+                                              const WvaModel &m) {
+  ChainAux aux;
+  const ChainOut o = chain_eval<NT, PART, true>(lam, m.g, m.logsN, c.N, m.Kstates, m.scratch, &aux);
+  const double eff =
+      effective_concurrency(o.serv, c.gamma, c.alpha, c.delta, c.beta, c.in_tok, c.out_tok, c.N);
+  const double b = (double)t_ttft - (double)wva_prefill_exact(c, (float)eff);
+  const double g = chain_wait_tail<NT, PART>(kind == 0, lam, b, m.mu, c.N, m.Kstates, aux.a_N,
+                                             aux.log_r, m.scratch);
+  return kind == 0 ? g : (double)decode_time_f(c.alpha, c.beta, (float)eff);
+}
+
+// dual_bisect with the TTFT half on g and target y: the same boundary checks,
+// indicators, iteration cap, fixed-point exit, lock-step and result slots.
+template <int NT>
+__device__ __forceinline__ void dual_bisect_tail(float t_ttft, double y, float t_itl,
+                                                 const WvaCell &c, const WvaModel &m,
+                                                 double lam_star[2], int ind_out[2]) {
+  constexpr int W = NT / 2;
+  const int tid = m.tid;
+  double *const res_slot = m.scratch + 33;  // 4 doubles
+  const int h = tid / W;  // 0 = TTFT quantile, 1 = ITL
+  const double target = (h == 0) ? y : (double)t_itl;
+  const bool active = (h == 0) ? t_ttft > 0.0f : t_itl > 0.0f;
+
+  double x_min = m.lam_min, x_max = m.lam_max;
+  double x_star = m.lam_max;
+  double y_lo = 0.0;
+  bool increasing = true;
+  int ind = 0;
+  int phase = active ? 0 : 3;  // 0 eval lo, 1 eval hi, 2 bisect, 3 done
+  int iters = 0;
+
+  for (int step = 0; step < WVA_MAX_ITERS + 3; ++step) {
+    double x_eval;
+    if (phase == 0)
+      x_eval = x_min;
+    else if (phase == 2)
+      x_eval = 0.5 * (x_min + x_max);
+    else
+      x_eval = x_max;  // phase 1, or done: dummy evaluation, barriers stay uniform
+    const double v = tail_metric<NT, 2>(h, x_eval, t_ttft, c, m);
+    if (phase == 0) {
+      y_lo = v;
+      if (within_tol(y_lo, target)) {
+        x_star = x_min;
+        phase = 3;
+      } else {
+        phase = 1;
+      }
+    } else if (phase == 1) {
+      const double y_hi = v;
+      if (within_tol(y_hi, target)) {
+        x_star = x_max;
+        phase = 3;
+      } else {
+        increasing = (h == 0) || y_lo < y_hi;  // g never decreases (see above)
+        if ((increasing && target < y_lo) || (!increasing && target > y_lo)) {
+          ind = -1;
+          x_star = x_min;
+          phase = 3;
+        } else if ((increasing && target > y_hi) || (!increasing && target < y_hi)) {
+          ind = +1;
+          x_star = x_max;
+          phase = 3;
+        } else {
+          phase = 2;
+        }
+      }
+    } else if (phase == 2) {
+      x_star = x_eval;
+      ++iters;
+      const bool fixed_pt = (x_eval == x_min) || (x_eval == x_max);
+      if (within_tol(v, target) || iters >= WVA_MAX_ITERS || fixed_pt) {
+        phase = 3;
+      } else if ((increasing && target < v) || (!increasing && target > v)) {
+        x_max = x_star;
+      } else {
+        x_min = x_star;
+      }
+    }
+    const bool done = (phase == 3);
+    if constexpr (NT == WVA_WAVE) {
+      if (__all(done ? 1 : 0)) break;  // one-wave cell: a wave vote, no barrier
+    } else {
+      if (__syncthreads_and(done ? 1 : 0)) break;
+    }
+  }
+
+  if ((tid % W) == 0) {
+    res_slot[2 * h] = x_star;
+    res_slot[2 * h + 1] = (double)ind;
+  }
+  if constexpr (NT == WVA_WAVE) {
+    __builtin_amdgcn_s_waitcnt(0);
+  } else {
+    __syncthreads();
+  }
+  lam_star[0] = res_slot[0];
+  ind_out[0] = (int)res_slot[1];
+  lam_star[1] = res_slot[2];
+  ind_out[1] = (int)res_slot[3];
+}
+
+// The cell's scalars the percentile kernels read, the geometry, the
+// degenerate-rate guard and the model, as steps (3) and (4) of wva_cell_body.
+// Returns false when the guard fires (uniformly).
+template <int NT, bool GMEM>
+__device__ __forceinline__ bool wva_tail_model(const WvaCellsIn &in, int cell, int tid,
+                                               double *smem, unsigned slab, int max_n,
+                                               float *g_inv, double *g_anchor, WvaCell &c,
+                                               WvaModel &m) {
+  c.cell = cell;
+  c.in_tok = in.in_tok[cell];
+  c.out_tok = in.out_tok[cell];
+  c.N = in.batch_n[cell];
+  c.alpha = in.alpha[cell];
+  c.beta = in.beta[cell];
+  c.gamma = in.gamma[cell];
+  c.delta = in.delta[cell];
+  c.t_tps = in.t_tps[cell];
+  const bool bad_rate =
+      wva_build_geom<NT, GMEM, true>(c, tid, 0, smem, slab, max_n, g_inv, g_anchor, m.g);
+  const int num_decode = wva_num_decode(c);
+  const float s1 = wva_rate_exact(c, num_decode, 1);
+  const float sN = wva_rate_exact(c, num_decode, c.N);
+  const double any_bad = red_max_p<NT, 1>(bad_rate ? 1.0 : 0.0, smem);
+  if (any_bad > 0.0 || !(s1 > 0.0f) || !(sN > 0.0f) || !isfinite(s1) || !isfinite(sN))
+    return false;
+  m.logsN = log((double)sN);
+  m.Kstates = 11 * c.N;
+  m.mode = 0;
+  m.cv2d = 1.0;
+  m.mu = (double)sN;
+  m.lam_min = (double)s1 * WVA_EPSILON;
+  m.lam_max = (double)sN * (1.0 - WVA_EPSILON);
+  m.scratch = smem;
+  m.tid = tid;
+  return true;
+}
+
+template <int NT, bool GMEM>
+__global__ void WVA_NO_PK_F32 __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
+    wva_tail_plan_t(WvaCellsIn in, WvaCellsOut out, int n_blocks, const int *cell_ids, int max_n,
+                    int, float, float *g_inv, double *g_anchor, WvaMemoRec *, unsigned *,
+                    WvaTailArgs p) {
+  extern __shared__ double smem[];
+  if ((int)blockIdx.x >= n_blocks) return;
+  const int cell = cell_ids ? cell_ids[blockIdx.x] : (int)blockIdx.x;
+  const int tid = (int)threadIdx.x;
+  const auto arrival = [&](int s) __attribute__((always_inline)) {
+    return p.scen_arrival[(size_t)s * (size_t)p.n_cells + (size_t)cell];
+  };
+  const auto slot = [&](int k, int s) __attribute__((always_inline)) {
+    return ((size_t)k * (size_t)p.n_load + (size_t)s) * (size_t)p.n_cells + (size_t)cell;
+  };
+  // (the lambdas are inlined by force: code left out of line would not carry
+  // the kernel's target attribute)
+  // (thread 0 only) a slot that is not evaluated: the zero-traffic result
+  // first, else the infeasible verdict
+  WvaCell c;
+  const auto quiet_slot = [&](int k, int s) __attribute__((always_inline)) {
+    const size_t o = slot(k, s);
+    if (arrival(s) == 0.0f || c.out_tok == 0) {
+      wva_write_zero(out, o, c, in.perf_max_batch);
+      p.wait_tail[o] = 0.0f;
+    } else {
+      out.feasible[o] = 0;
+      out.zero_empty[o] = 0;
+      p.wait_tail[o] = NAN;
+    }
+  };
+  const int flags = in.flags[cell];
+  c.min_rep = in.min_replicas[cell];
+  c.acc_cost = in.acc_cost[cell];
+  c.cur_cost = in.cur_cost[cell];
+  c.cur_rep = in.cur_replicas[cell];
+  c.cur_same = flags & 1;
+  c.cur_empty = flags & 2;
+  c.has_cur = flags & 4;
+  c.cell = cell;
+  c.out_tok = in.out_tok[cell];
+  c.alpha = in.alpha[cell];
+  c.beta = in.beta[cell];
+  c.gamma = in.gamma[cell];
+  c.delta = in.delta[cell];
+
+  // zero traffic in every load: no geometry, no barrier
+  bool any_load = false;
+  if (c.out_tok != 0)
+    for (int s = 0; s < p.n_load; ++s) any_load = any_load || (arrival(s) != 0.0f);
+  WvaModel m;
+  if (!any_load || !wva_tail_model<NT, GMEM>(in, cell, tid, smem, blockIdx.x, max_n, g_inv,
+                                             g_anchor, c, m)) {
+    if (tid == 0)
+      for (int k = 0; k < p.n_q; ++k)
+        for (int s = 0; s < p.n_load; ++s) quiet_slot(k, s);
+    return;
+  }
+  const float t_ttft = in.t_ttft[cell], t_itl = in.t_itl[cell];
+
+  for (int k = 0; k < p.n_q; ++k) {
+    // the sizing of wva_size_cell with the TTFT half on quantile k
+    double lam_star[2];
+    int inds[2];
+    dual_bisect_tail<NT>(t_ttft, p.y[k], t_itl, c, m, lam_star, inds);
+    bool feasible = true;
+    double lam_ttft = m.lam_max;
+    if (t_ttft > 0.0f) {
+      lam_ttft = lam_star[0];
+      if (inds[0] < 0) feasible = false;
+    }
+    double lam_itl = m.lam_max;
+    if (feasible && t_itl > 0.0f) {
+      lam_itl = lam_star[1];
+      if (inds[1] < 0) feasible = false;
+    }
+    double rate_star = 0.0;  // req/sec
+    if (feasible) {
+      const double lam_tps =
+          (c.t_tps > 0.0f) ? m.lam_max * (1.0 - WVA_STABILITY_FRACTION) : m.lam_max;
+      const double lam = fmin(fmin(lam_ttft, lam_itl), lam_tps);
+      rate_star = wva_evaluate<NT, 1, true>(lam, c, m).tput * 1000.0;
+    }
+    for (int s = 0; s < p.n_load; ++s) {
+      const float arr = arrival(s);
+      if (arr == 0.0f || !feasible) {
+        if (tid == 0) quiet_slot(k, s);
+        continue;
+      }
+      const size_t o = slot(k, s);
+      wva_eval_scenario<NT, true>(out, o, arr, rate_star, c, m);
+      // g at the per-replica rate wva_eval_scenario analysed
+      const double total_rate =
+          (c.t_tps == 0.0f) ? (double)arr / 60.0 : (double)c.t_tps / (double)c.out_tok;
+      double reps_d = ceil(total_rate / rate_star);
+      if (!(reps_d > 0.0)) reps_d = 0.0;
+      if (reps_d > 2147483000.0) reps_d = 2147483000.0;
+      int num_replicas = (int)reps_d;
+      if (num_replicas < c.min_rep) num_replicas = c.min_rep;
+      const double rate = total_rate / (double)num_replicas;
+      const double g = tail_metric<NT, 1>(0, rate / 1000.0, t_ttft, c, m);
+      if (tid == 0) p.wait_tail[o] = (float)g;
+    }
+  }
+}
+
+// One-shot probe of the tail evaluator and the percentile sizing, for tests
+// and tools: per cell n_pairs values tail(lam_i, t_i) and n_q sizings
+// (lam_ttft, indicator) of the cell's own TTFT target, all fp64, by the code
+// and at the width the planning kernel runs the cell with. A cell whose rates
+// are degenerate gets NaN tails and indicator -2.
+struct WvaProbeArgs {
+  int n_pairs;
+  const double *lam;  // device, [n_cells][n_pairs] (req/msec)
+  const double *t;    // device, [n_cells][n_pairs] (msec)
+  double *tail;       // device, [n_cells][n_pairs]
+  int n_q;
+  const double *y;    // device, [n_q]: 1 - q
+  double *lam_ttft;   // device, [n_cells][n_q] (req/msec)
+  int *ind;           // device, [n_cells][n_q]
+};
+template <int NT, bool GMEM>
+__global__ void WVA_NO_PK_F32 __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
+    wva_tail_probe_t(WvaCellsIn in, WvaCellsOut, int n_blocks, const int *cell_ids, int max_n, int,
+                     float, float *g_inv, double *g_anchor, WvaMemoRec *, unsigned *,
+                     WvaProbeArgs p) {
+  extern __shared__ double smem[];
+  if ((int)blockIdx.x >= n_blocks) return;
+  const int cell = cell_ids ? cell_ids[blockIdx.x] : (int)blockIdx.x;
+  const int tid = (int)threadIdx.x;
+  WvaCell c;
+  WvaModel m;
+  const bool ok =
+      wva_tail_model<NT, GMEM>(in, cell, tid, smem, blockIdx.x, max_n, g_inv, g_anchor, c, m);
+  const size_t pair0 = (size_t)cell * (size_t)p.n_pairs, q0 = (size_t)cell * (size_t)p.n_q;
+  if (!ok) {
+    if (tid == 0) {
+      for (int i = 0; i < p.n_pairs; ++i) p.tail[pair0 + i] = NAN;
+      for (int k = 0; k < p.n_q; ++k) {
+        p.lam_ttft[q0 + k] = NAN;
+        p.ind[q0 + k] = -2;
+      }
+    }
+    return;
+  }
+  for (int i = 0; i < p.n_pairs; ++i) {
+    const double lam = p.lam[pair0 + i];
+    double v = NAN;
+    if (lam > 0.0 && lam < m.mu) {  // uniform: same address on every thread
+      ChainAux aux;
+      chain_eval<NT, 1, true>(lam, m.g, m.logsN, c.N, m.Kstates, m.scratch, &aux);
+      v = chain_wait_tail<NT, 1>(true, lam, p.t[pair0 + i], m.mu, c.N, m.Kstates, aux.a_N,
+                                 aux.log_r, m.scratch);
+    }
+    if (tid == 0) p.tail[pair0 + i] = v;
+  }
+  const float t_ttft = in.t_ttft[cell];
+  for (int k = 0; k < p.n_q; ++k) {
+    double lam_star[2];
+    int inds[2];
+    dual_bisect_tail<NT>(t_ttft, p.y[k], 0.0f, c, m, lam_star, inds);
+    if (tid == 0) {
+      p.lam_ttft[q0 + k] = lam_star[0];
+      p.ind[q0 + k] = inds[0];
+    }
+  }
+}
+
+// winners' wait_tail: per (server, slice) the per-cell value at the winning
+// cell of wva_plan_reduce's record (pi row 3), NaN without a winner
+__global__ void wva_tail_gather(const int *pi, const float *wait_tail, int n_srv, int n_cells,
+                                float *out) {
+  const int srv = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t sc = blockIdx.y;
+  if (srv >= n_srv) return;
+  const int w = pi[(sc * 4 + 3) * (size_t)n_srv + srv];
+  out[sc * (size_t)n_srv + srv] =
+      (w >= 0 && w < n_cells) ? wait_tail[sc * (size_t)n_cells + w] : NAN;
+}
+
+// ---------------------------------------------------------------------------
 // K2: segmented argmin per server over the sweep output.
 // ---------------------------------------------------------------------------
 extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_argmin(
@@ -1829,10 +2417,14 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
                               const WvaPlanArgs *plan = nullptr,
                               const WvaSloArgs *slo = nullptr,
                               const WvaTokArgs *tok = nullptr,
-                              const WvaHoldArgs *hold = nullptr) {
+                              const WvaHoldArgs *hold = nullptr,
+                              const WvaTailArgs *tail = nullptr,
+                              const WvaProbeArgs *probe = nullptr) {
   if (n_blocks <= 0) return 0;
   const bool gmem = g_inv != nullptr && g_anchor != nullptr;
   if (max_n < 1) return -2;
+  // the percentile kernels model the chain only
+  if ((tail != nullptr || probe != nullptr) && analyzer_mode != 0) return -6;
   if (!gmem && max_n > WVA_XL_MAX_N) return -2;
   if (gmem && max_n > WVA_HUGE_MAX_N) return -4;
   // the spill path keeps only the header in LDS
@@ -1851,7 +2443,9 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
   };
   int rc = -3;
 #define WVA_LAUNCH(NTV, GM)                                        \
-  rc = hold != nullptr   ? launch(&wva_hold_t<NTV, GM>, *hold)     \
+  rc = probe != nullptr  ? launch(&wva_tail_probe_t<NTV, GM>, *probe) \
+       : tail != nullptr ? launch(&wva_tail_plan_t<NTV, GM>, *tail) \
+       : hold != nullptr ? launch(&wva_hold_t<NTV, GM>, *hold)     \
        : tok != nullptr  ? launch(&wva_tok_plan_t<NTV, GM>, *tok)  \
        : slo != nullptr  ? launch(&wva_slo_plan_t<NTV, GM>, *slo)  \
        : plan != nullptr ? launch(&wva_plan_t<NTV, GM>, *plan)     \
@@ -1904,6 +2498,33 @@ extern "C" int wva_argmin_launch(int n_servers, void *stream, const float *value
   hipLaunchKernelGGL(wva_argmin, dim3(n_servers), dim3(WVA_WAVE), 0, (hipStream_t)stream, value,
                      feasible, seg_start, n_servers, winner);
   return (int)hipGetLastError();
+}
+
+// One bucket of the tail probe (wva_tail_probe_t): n_blocks cells of up to
+// max_n states on nt threads, dispatched as a sweep bucket is. All pointers are
+// device pointers; the per-cell arrays are the sweep's (only these are read).
+// -6 is never returned here: the probe always models the chain.
+extern "C" int wva_tail_probe_launch(
+    int n_blocks, int max_n, int nt, const int *cell_ids, void *stream, const int *in_tok,
+    const int *out_tok, const int *batch_n, const float *alpha, const float *beta,
+    const float *gamma, const float *delta, const float *t_ttft, const float *t_tps, int n_pairs,
+    const double *lam, const double *t, double *tail, int n_q, const double *y, double *lam_ttft,
+    int *ind, void *g_inv, void *g_anchor) {
+  if (n_pairs < 0 || n_q < 0) return -2;
+  WvaCellsIn in = {};
+  in.in_tok = in_tok;
+  in.out_tok = out_tok;
+  in.batch_n = batch_n;
+  in.alpha = alpha;
+  in.beta = beta;
+  in.gamma = gamma;
+  in.delta = delta;
+  in.t_ttft = t_ttft;
+  in.t_tps = t_tps;
+  const WvaProbeArgs pa = {n_pairs, lam, t, tail, n_q, y, lam_ttft, ind};
+  return wva_sweep_dispatch(n_blocks, max_n, nt, cell_ids, 0, 1.0f, (hipStream_t)stream, in,
+                            WvaCellsOut{}, (float *)g_inv, (double *)g_anchor, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, &pa);
 }
 
 extern "C" int wva_device_count(int *count) { return (int)hipGetDeviceCount(count); }

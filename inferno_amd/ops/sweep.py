@@ -251,6 +251,27 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_scen][4][n_srv]
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][n_acc]
     ]
+    # percentile planning (engine/fastpath.py FastSweep.plan_tail)
+    lib.wva_ctx_plan_tail.restype = ctypes.c_int
+    lib.wva_ctx_plan_tail.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_int,  # n_q (1..8)
+        ctypes.c_int,  # n_scen = n_q * n_load (1..PLAN_MAX_S)
+        ctypes.c_int,  # n_acc
+        ctypes.c_void_p,  # host fp32 [n_load][n_cells] arrival rates
+        ctypes.c_void_p,  # host fp64 [n_q] 1 - q
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned fp32 [n_scen][6][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_scen][4][n_srv]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][n_acc]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned fp32 [n_scen][n_srv] wait_tail
+    ]
+    lib.wva_ctx_plan_tail_cells.restype = ctypes.c_int
+    lib.wva_ctx_plan_tail_cells.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.wva_tail_probe_launch.restype = ctypes.c_int
+    lib.wva_tail_probe_launch.argtypes = (
+        [ctypes.c_int] * 3 + [ctypes.c_void_p] * 11 + [ctypes.c_int] + [ctypes.c_void_p] * 3
+        + [ctypes.c_int] + [ctypes.c_void_p] * 5
+    )
     # token-mix planning (engine/fastpath.py FastSweep.plan_tokens)
     lib.wva_ctx_plan_tokens.restype = ctypes.c_int
     lib.wva_ctx_plan_tokens.argtypes = [
@@ -492,6 +513,59 @@ def run_argmin(value, feasible, seg_start) -> "object":
     if rc != 0:
         raise HipKernelError(f"wva_argmin_launch failed with hipError {rc}")
     return winner
+
+
+def run_tail_probe(arrays: dict, lam, t, quantiles=(), device: str = "cuda"):
+    """One-shot probe of the wait-time tail and the percentile TTFT sizing
+    (wva_tail_probe_t), for tests and tools.
+
+    ``arrays``: the sweep's per-cell CPU tensors (in_tok, out_tok, batch_n,
+    alpha, beta, gamma, delta, t_ttft, t_tps are read). ``lam`` (req/msec) and
+    ``t`` (msec): float64 [n_cells, P]. Returns numpy arrays: tail [n_cells, P]
+    (NaN where lam is outside (0, s(N))), and for ``quantiles`` [Q] the sized
+    lam_ttft [n_cells, Q] (req/msec) with its indicator [n_cells, Q] (-1 below,
+    0 within, +1 above the reachable range; -2 degenerate rates). Cells go to
+    the block width and geometry tier choose_buckets gives their N."""
+    import numpy as np
+    import torch
+
+    if not torch.cuda.is_available():
+        raise HipKernelError("run_tail_probe requires a GPU")
+    lib = load_library()
+    n_cells = int(arrays["in_tok"].shape[0])
+    lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(n_cells, -1)
+    t = np.ascontiguousarray(t, dtype=np.float64).reshape(n_cells, -1)
+    if lam.shape != t.shape:
+        raise ValueError("lam and t differ in shape")
+    q = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+    if ((q <= 0) | (q >= 1)).any():
+        raise ValueError("quantiles must lie in (0, 1)")
+    n_pairs, n_q = lam.shape[1], len(q)
+    keys = ("in_tok", "out_tok", "batch_n", "alpha", "beta", "gamma", "delta", "t_ttft", "t_tps")
+    dev = {k: arrays[k].to(device) for k in keys}
+    f64 = dict(dtype=torch.float64, device=device)
+    d_lam, d_t = torch.from_numpy(lam).to(device), torch.from_numpy(t).to(device)
+    d_y = torch.from_numpy(1.0 - q).to(device)
+    d_tail = torch.full((n_cells, max(n_pairs, 1)), float("nan"), **f64)
+    d_lamq = torch.full((n_cells, max(n_q, 1)), float("nan"), **f64)
+    d_ind = torch.full((n_cells, max(n_q, 1)), -2, dtype=torch.int32, device=device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    keep = []
+    for nt, ids, bmax, count, gmem in choose_buckets(arrays["batch_n"].numpy()):
+        ids_t = torch.from_numpy(ids).to(device) if ids is not None else None
+        slabs = alloc_gmem_slabs(count, bmax, nt, device) if gmem else (None, None)
+        keep.append((ids_t, slabs))
+        rc = lib.wva_tail_probe_launch(
+            count, max(bmax, 1), nt, _ptr(ids_t) if ids_t is not None else None, stream,
+            *[_ptr(dev[k]) for k in keys], n_pairs, _ptr(d_lam), _ptr(d_t), _ptr(d_tail),
+            n_q, _ptr(d_y), _ptr(d_lamq), _ptr(d_ind),
+            _ptr(slabs[0]) if gmem else None, _ptr(slabs[1]) if gmem else None,
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_tail_probe_launch(nt={nt}) failed: {rc}")
+    torch.cuda.synchronize()
+    return (d_tail.cpu().numpy()[:, :n_pairs], d_lamq.cpu().numpy()[:, :n_q],
+            d_ind.cpu().numpy()[:, :n_q])
 
 
 def run_greedy_native(cand_value, cand_acc_type, cand_units, cand_replicas,
