@@ -137,6 +137,10 @@ def cmd_plan(args) -> int:
                              "over sampled load paths; it does not combine with --rollout, "
                              "--hold, --slo-scales, --token-scales, --limited or --capacity")
         return _cmd_plan_ensemble(args)
+    if args.lag_times is not None:
+        if not args.hold:
+            raise SystemExit("plan: --lag-times goes with --hold (the allocation that is held)")
+        return _cmd_plan_lag(args)
     if args.hold:
         if (limited or args.slo_scales is not None or args.token_scales is not None
                 or args.rollout):
@@ -492,6 +496,65 @@ def _cmd_plan_ensemble(args) -> int:
     return 0
 
 
+def _cmd_plan_lag(args) -> int:
+    """Lag analysis: the current allocation held while the load steps from the
+    base load to each scale; the latency curve at the checkpoint times."""
+    from .engine import LAG_OK, LAG_STATUS_NAMES, FastSweep, SweepEngine
+
+    if args.scales is None:
+        raise SystemExit("plan: --lag-times needs --scales")
+    scales = _parse_scales(args.scales)
+    try:
+        times = [float(t) for t in args.lag_times.split(",") if t.strip()]
+    except ValueError:
+        raise SystemExit(f"plan: --lag-times is not a list of seconds: {args.lag_times!r}")
+    system, _ = _load_system(args.spec)
+    backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
+    fs = FastSweep(system, backend=backend)
+    try:
+        res = fs.lag(scales=scales, times=times)
+    except ValueError as e:
+        print(f"plan: {e}", file=sys.stderr)
+        return 2
+
+    def num(x):  # NaN has no JSON number
+        return float(x) if x == x else None
+
+    rows = []
+    for s, scale in enumerate(scales):
+        rows.append({
+            "scale": scale,
+            "status": {n: int(res.counts[s, j]) for j, n in enumerate(LAG_STATUS_NAMES)},
+            "violated": [int(v) for v in res.violations[:, s]],
+            "servers": [{
+                "server": fs.server_names[i],
+                "status": LAG_STATUS_NAMES[res.status[s, i]],
+                "firstViolation": (float(res.times[res.first_violation[s, i]])
+                                   if res.first_violation[s, i] >= 0 else None),
+                "ttft": [num(x) for x in res.ttft[:, s, i]],
+                "itl": [num(x) for x in res.itl[:, s, i]],
+                "blocked": [num(x) for x in res.blocked[:, s, i]],
+            } for i in range(len(fs.server_names))
+                if res.status[s, i] != LAG_OK or res.first_violation[s, i] >= 0],
+        })
+    if args.json:
+        print(json.dumps({"backend": backend, "servers": len(fs.server_names),
+                          "times": [float(t) for t in res.times], "lag": rows}, indent=2))
+        return 0
+    for r in rows:
+        print(f"load scale {r['scale']:g}: "
+              + ", ".join(f"{n} {c}" for n, c in r["status"].items() if c)
+              + "; servers over their SLO at "
+              + ", ".join(f"{t:g}s: {v}" for t, v in zip(res.times, r["violated"])))
+        for b in r["servers"]:
+            first = "-" if b["firstViolation"] is None else f"{b['firstViolation']:g}s"
+            ttft = " ".join("nan" if x is None else f"{x:.1f}" for x in b["ttft"])
+            print(f"  {b['server']:<24} {b['status']:<12} SLO broken from {first:<6} ttft ms {ttft}")
+    print(f"({len(fs.server_names)} servers, backend {backend}; the current allocation is held "
+          "while the load steps from the base load to each scale)")
+    return 0
+
+
 def _cmd_plan_hold(args) -> int:
     """Hold analysis: the current allocation, unchanged, at each load scale."""
     from .engine import HOLD_OK, HOLD_STATUS_NAMES, FastSweep, SweepEngine
@@ -600,6 +663,10 @@ def main() -> None:
     pp.add_argument("--rollout", action="store_true",
                     help="forecast rollout: --scales are consecutive steps, each reconciled "
                          "against the allocation the step before it left behind")
+    pp.add_argument("--lag-times", default=None, metavar="SECONDS",
+                    help="with --hold: lag analysis, the transient latency of the held "
+                         "allocation at these checkpoint times after the load steps from the "
+                         "base load to each scale, e.g. 15,30,60")
     pp.add_argument("--hold", action="store_true",
                     help="hold analysis: the current allocation is not resized; per load scale "
                          "the SLO verdict of every server, the replicas short by accelerator")

@@ -32,7 +32,8 @@ import numpy as np
 from ..config import SaturationPolicy
 from ..core import create_allocation
 from ..core.system import System
-from ..ops.sweep import PLAN_MAX_S, run_greedy_native
+from ..ops.sweep import (LAG_MAX_N, LAG_MAX_T, PLAN_MAX_S, lag_intervals, lag_task_table,
+                         run_greedy_native)
 from .native_ctx import CELL_KEYS, NativeCtx
 from .snapshot import FLAG_CUR_EMPTY, FLAG_CUR_SAME, FLAG_HAS_CUR
 
@@ -189,6 +190,49 @@ class HoldResult:
     counts: np.ndarray  # int64 [S, 6]: servers per status
     deficit_by_acc: np.ndarray  # int64 [S, n_acc]: sum of max(needed - held, 0), needed >= 0
     cells: Optional[dict] = None  # per-cell arrays [S, n_cells] of the same, plus cell metadata
+
+
+# Verdict of one (scenario, server) slice of a lag analysis (FastSweep.lag), in
+# order of precedence NOT_HELD, IDLE, INVALID, NO_REPLICAS, TOO_WIDE, BUDGET, OK.
+LAG_OK = 0  # evaluated at every checkpoint
+LAG_NOT_HELD = 1  # the allocation names no accelerator the server has a cell on
+LAG_IDLE = 2  # no output tokens, or no load before and during the lag
+LAG_INVALID = 3  # degenerate service rates: no model of the cell
+LAG_NO_REPLICAS = 4  # a loaded cell held with zero replicas
+LAG_TOO_WIDE = 5  # N above LAG_MAX_N, what the widest kernel instantiation holds
+LAG_BUDGET = 6  # more than max_steps uniformization steps over the checkpoints
+LAG_STATUS_NAMES = ("OK", "NOT_HELD", "IDLE", "INVALID", "NO_REPLICAS", "TOO_WIDE", "BUDGET")
+_LAG_FLOATS = ("ttft", "itl", "wait", "blocked", "rho", "in_system")  # device row order
+# Cap on the uniformization steps of one slice over all its checkpoints; it
+# bounds the run time of one block. A slice above it is LAG_BUDGET, never
+# clipped. Measured on MI355X (profiles/bench_lag.json): the widest class takes
+# 0.64 us per step (the flagship run's slowest task: N = 789, 10101 steps,
+# 6.5 ms), so the cap keeps any single task near 26 ms.
+LAG_MAX_STEPS = 40_000
+
+
+@dataclass
+class LagResult:
+    """Lag analysis: the transient response of a held fleet (FastSweep.lag).
+    Per-checkpoint arrays are [T, S, n_servers], the others [S, n_servers]."""
+
+    ttft: np.ndarray  # float32 msec; NaN where the status has no evaluation
+    itl: np.ndarray  # float32 msec
+    wait: np.ndarray  # float32 msec: mean queueing wait of an accepted request
+    blocked: np.ndarray  # float32: probability that the queue is full
+    rho: np.ndarray  # float32
+    in_system: np.ndarray  # float32: mean requests in the system
+    violated: np.ndarray  # bool: ttft or itl above its (non-zero) target
+    status: np.ndarray  # int32, one of LAG_*
+    first_violation: np.ndarray  # int32: first violated checkpoint, -1 for none
+    held_replicas: np.ndarray  # int32
+    acc_idx: np.ndarray  # int32: the held accelerator, -1 where NOT_HELD
+    steps: np.ndarray  # int32: uniformization steps of the slice, 0 without a model
+    times: np.ndarray  # float64 [T] seconds
+    arrival: np.ndarray  # float32 [S, n_servers]: the loads during the lag
+    from_arrival: np.ndarray  # float32 [n_servers]: the load before it
+    counts: np.ndarray  # int64 [S, 7]: servers per status
+    violations: np.ndarray  # int64 [T, S]: servers violated per checkpoint
 
 
 # Longest forecast one rollout() takes, and the steps one device pass of it
@@ -1135,6 +1179,174 @@ class FastSweep:
         if counts is None:
             counts, deficit = _hold_sums(rec, n_acc)
         return HoldResult(arrival=scen, counts=counts, deficit_by_acc=deficit, cells=cells, **rec)
+
+    def lag(self, scales=None, arrival=None, allocation=None, times=(15, 30, 60),
+            from_arrival=None, max_steps: int = LAG_MAX_STEPS) -> LagResult:
+        """The TRANSIENT response of a fixed allocation: the latency curve
+        inside an actuation lag, where hold() can only say OK or infinite.
+
+        The load steps from ``from_arrival`` ([n_servers] req/min, default the
+        base load) to each of the S scenarios (``scales`` or ``arrival`` as for
+        hold()) while ``allocation`` (as for hold()) stays. Per (scenario,
+        server) the held cell's M/M/1/K chain starts in its stationary
+        distribution at the old per-replica rate and evolves under the new one,
+        which may be 0 (drain) or above the service rate (overload: the finite
+        queue fills). ``times``: 1..16 strictly increasing checkpoints in
+        seconds. Per checkpoint: ttft, itl, wait, blocked (queue full), rho,
+        in_system, and ``violated`` (fp32 ttft / itl above a non-zero target).
+
+        Status per slice, in this order: LAG_NOT_HELD and LAG_IDLE (floats as
+        hold() reports them), LAG_INVALID, LAG_NO_REPLICAS, LAG_TOO_WIDE (N >
+        LAG_MAX_N), LAG_BUDGET (more than ``max_steps`` uniformization steps;
+        never clipped) — floats NaN — else LAG_OK. Chain analyzer only. A lag
+        pass stages no tick and changes nothing any other call returns."""
+        from ..analyzer import (Configuration, DecodeParms, PrefillParms, RequestSize,
+                                ServiceParms)
+        from ..analyzer.lag import lag_latency, lag_steps, lag_transient
+        from ..analyzer.queue import build_service_rates
+
+        if getattr(self.system, "analyzer_mode", "mm1k") == "mg1":
+            raise ValueError("lag() needs the chain analyzer: the M/G/1 evaluator has no "
+                             "transient form")
+        scen = self._plan_scenarios(scales, arrival, who="lag()")
+        n_scen, n_srv = scen.shape
+        acc, rep = self._hold_allocation(allocation, n_scen)
+        try:
+            ts = np.atleast_1d(np.asarray(times, dtype=np.float64))
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"times is not numeric: {e}") from None
+        if ts.ndim != 1 or not 1 <= len(ts) <= LAG_MAX_T:
+            raise ValueError(f"lag() takes 1..{LAG_MAX_T} checkpoint times, got shape {ts.shape}")
+        dt = lag_intervals(ts)
+        if not (np.isfinite(ts).all() and (dt > 0).all()):
+            raise ValueError("times must be finite, positive and strictly increasing")
+        if from_arrival is None:
+            arr0 = np.asarray(self._base_load()[0], dtype=np.float32)
+        else:
+            try:
+                arr0 = np.asarray(from_arrival, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"from_arrival is not numeric: {e}") from None
+            if arr0.shape != (n_srv,) or not np.isfinite(arr0).all() or (arr0 < 0).any():
+                raise ValueError(f"from_arrival must be [{n_srv}] finite non-negative rates")
+            arr0 = arr0.astype(np.float32)
+        max_steps = int(max_steps)
+        if not 0 <= max_steps <= np.iinfo(np.int32).max:
+            raise ValueError("max_steps must be a non-negative int32")
+
+        n_t = len(ts)
+        shape = (n_t, n_scen, n_srv)
+        rec = {k: np.zeros(shape, dtype=np.float32) for k in _LAG_FLOATS}
+        violated = np.zeros(shape, dtype=bool)
+        status = np.full((n_scen, n_srv), LAG_NOT_HELD, dtype=np.int32)
+        steps = np.zeros((n_scen, n_srv), dtype=np.int32)
+        _, in_tok, out_tok = self._base_load()
+        st = self._stat
+        cell_of = np.full((n_srv, max(len(self.acc_names), 1)), -1, dtype=np.int64)
+        cell_of[self.cell_server, self.cell_acc_idx] = np.arange(self.n_cells)
+        models = {}  # cell -> (fp32 rates or None, N, service parms, request size)
+
+        def model(k, i):
+            if k not in models:
+                n_max = int(st["override"][k]) if st["override"][k] > 0 else max(
+                    int(st["perf_max_batch_cfg"][k]) * int(st["at_tokens"][k]) // int(out_tok[i]),
+                    1)
+                cfg = Configuration(n_max, 10 * n_max, ServiceParms(
+                    PrefillParms(float(st["gamma"][k]), float(st["delta"][k])),
+                    DecodeParms(float(st["alpha"][k]), float(st["beta"][k]))))
+                req = RequestSize(int(in_tok[i]), int(out_tok[i]))
+                rates = build_service_rates(cfg, req)
+                if not np.all(np.isfinite(rates)) or np.any(rates <= 0):
+                    rates = None
+                models[k] = (rates, n_max, cfg.service_parms, req)
+            return models[k]
+
+        tasks = []  # (s, i, k, lam0, lam1, total steps)
+        for s in range(n_scen):
+            for i in range(n_srv):
+                k = int(cell_of[i, acc[s, i]]) if acc[s, i] >= 0 else -1
+                if k < 0:
+                    continue
+                held = int(rep[s, i])
+                tps = float(st["t_tps"][k])
+                n_out = int(out_tok[i])
+                rate0, rate1 = ((float(a) / 60.0 if tps == 0.0 else tps / float(n_out))
+                                if n_out else 0.0 for a in (arr0[i], scen[s, i]))
+                if n_out == 0 or (rate0 == 0.0 and rate1 == 0.0):
+                    status[s, i] = LAG_IDLE
+                    if st["min_replicas"][k] != 0:
+                        rec["itl"][:, s, i] = np.float32(st["alpha"][k]) + np.float32(st["beta"][k])
+                        rec["ttft"][:, s, i] = (np.float32(st["gamma"][k])
+                                                + np.float32(st["delta"][k]))
+                    continue
+                for f in _LAG_FLOATS:
+                    rec[f][:, s, i] = np.nan
+                rates, n_max, _, _ = model(k, i)
+                if rates is None:
+                    status[s, i] = LAG_INVALID
+                elif held == 0:
+                    status[s, i] = LAG_NO_REPLICAS
+                elif n_max > LAG_MAX_N:
+                    status[s, i] = LAG_TOO_WIDE
+                else:
+                    lam0, lam1 = rate0 / held / 1000.0, rate1 / held / 1000.0
+                    total = float(lag_steps(lam1 + float(rates.max()), dt))
+                    if total > max_steps:
+                        status[s, i] = LAG_BUDGET
+                        steps[s, i] = int(min(total, 2147483000.0))
+                    else:
+                        status[s, i] = LAG_OK
+                        tasks.append((s, i, k, lam0, lam1, total))
+
+        if tasks and self.backend == "gpu":
+            ss, ii, kk = (np.array([t[j] for t in tasks], dtype=np.int64) for j in range(3))
+            n_of = np.array([models[k][1] for k in kk], dtype=np.int32)
+            fields = {"in_tok": in_tok[ii], "out_tok": out_tok[ii], "N": n_of,
+                      "slot": (ss * n_srv + ii).astype(np.int32),
+                      "lam0": np.array([t[3] for t in tasks]),
+                      "lam1": np.array([t[4] for t in tasks])}
+            for f in ("alpha", "beta", "gamma", "delta", "t_ttft", "t_itl"):
+                fields[f] = st[f][kk]
+            # cost proxy K * lam1 * t_T, the steps standing in for the last two
+            table, counts, _ = lag_task_table(fields, n_of * np.array([t[5] for t in tasks]))
+            g = getattr(self, "_gpu", None)
+            if g is None:
+                g = self._gpu = NativeCtx(n_srv, self._stat, self.cell_server,
+                                          self.cell_acc_idx, self.seg_start, self.device)
+            of, ov, osteps = g.lag(table, counts, dt, n_scen * n_srv, max_steps)
+            for r, f in enumerate(_LAG_FLOATS):
+                rec[f][:, ss, ii] = of[r].reshape(shape)[:, ss, ii]
+            violated[:, ss, ii] = ov.reshape(shape)[:, ss, ii] != 0
+            steps[ss, ii] = osteps.reshape(n_scen, n_srv)[ss, ii]
+            # the host chose OK against max_steps from its own count of the
+            # steps; a device that counts differently would report NaN records
+            # (or none) under a status that says OK
+            want = np.array([t[5] for t in tasks], dtype=np.int64)
+            if not np.array_equal(steps[ss, ii], want):
+                from ..ops.sweep import HipKernelError
+
+                raise HipKernelError("wva_ctx_lag: the device's step counts differ from the "
+                                     "host's (lag_window and wva_lag_window are out of step)")
+        else:
+            for s, i, k, lam0, lam1, total in tasks:
+                rates, n_max, parms, req = models[k]
+                raw = lag_transient(rates, lam0, lam1, dt)
+                ttft, itl, rho = lag_latency(raw, parms, req, n_max)
+                rec["ttft"][:, s, i], rec["itl"][:, s, i], rec["rho"][:, s, i] = ttft, itl, rho
+                rec["wait"][:, s, i], rec["blocked"][:, s, i] = raw[:, 4], raw[:, 0]
+                rec["in_system"][:, s, i] = raw[:, 2]
+                t_ttft, t_itl = st["t_ttft"][k], st["t_itl"][k]
+                violated[:, s, i] = ((t_ttft != 0) & (ttft > t_ttft)) | (
+                    (t_itl != 0) & (itl > t_itl))
+                steps[s, i] = int(total)
+        first = np.where(violated.any(axis=0), violated.argmax(axis=0), -1).astype(np.int32)
+        counts = np.stack([(status == c).sum(axis=1) for c in range(len(LAG_STATUS_NAMES))],
+                          axis=1).astype(np.int64)
+        return LagResult(
+            violated=violated, status=status, first_violation=first, held_replicas=rep,
+            acc_idx=np.where(status == LAG_NOT_HELD, -1, acc).astype(np.int32), steps=steps,
+            times=ts, arrival=scen, from_arrival=arr0, counts=counts,
+            violations=violated.sum(axis=2).astype(np.int64), **rec)
 
     def _hold_allocation(self, allocation, n_scen: int):
         """Validate hold()'s allocation and return (acc_idx, num_replicas) as

@@ -545,6 +545,25 @@ class NativeCtx:
             _copy_out(out[3], ctypes.c_uint64, (n_scen, n_acc)).astype(np.int64),
         )
 
+    def lag(self, table: np.ndarray, counts: np.ndarray, dt: np.ndarray, n_slots: int,
+            max_steps: int):
+        """wva_ctx_lag on a task table (ops/sweep.py lag_task_table), its
+        per-class counts and the interval lengths (msec): fp32 [6, T, n_slots]
+        (ttft, itl, wait, blocked, rho, in_system), uint8 [T, n_slots] violated
+        and int32 [n_slots] steps, meaningful at the tasks' slots only. Needs
+        no staged tick and changes nothing a reconcile or a plan reads."""
+        n_times = len(dt)
+        out = [ctypes.c_void_p() for _ in range(3)]
+        rc = self._lib.wva_ctx_lag(
+            self.ctx, len(table), table.ctypes.data, counts.ctypes.data, n_times, dt.ctypes.data,
+            n_slots, int(max_steps), *[ctypes.byref(p) for p in out],
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_lag failed: {rc}")
+        return (_copy_out(out[0], ctypes.c_float, (6, n_times, n_slots)),
+                _copy_out(out[1], ctypes.c_uint8, (n_times, n_slots)),
+                _copy_out(out[2], ctypes.c_int32, (n_slots,)))
+
     def plan_cells(self, n_scen: int) -> dict:
         """Per-cell outputs [S, n_cells] of the planning pass that just ran."""
         cells = {k: np.empty((n_scen, self.n_cells), dtype=d)

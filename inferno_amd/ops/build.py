@@ -24,6 +24,7 @@ NATIVE_SRCS = [
 # context runtime is part of HIP_SRC's translation unit
 NATIVE_HDRS = [
     os.path.join(OPS_DIR, "hip", "wva_ctx.inc"),
+    os.path.join(OPS_DIR, "hip", "wva_lag.inc"),
     os.path.join(OPS_DIR, "native", "wva_stage.h"),
     os.path.join(OPS_DIR, "native", "wva_arena.h"),
 ]

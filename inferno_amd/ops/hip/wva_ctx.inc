@@ -153,6 +153,12 @@ struct WvaCtx {
   int hold_cap;      // scenarios the buffers hold (0 = not allocated)
   void *hold_dev;    // device i32 [S][n_cells]: -1 not held, >= 0 held replicas
   void *hold_pin;    // its pinned source
+  // lag analysis (wva_ctx_lag): the task table with the interval lengths and
+  // the records, one device and one pinned allocation made on first use, grown
+  // to the largest pass seen, carved up per pass, freed in destroy
+  void *lag_dev;
+  void *lag_pin;
+  size_t lag_cap;  // bytes each of them holds (0 = not allocated)
   // forecast rollout (wva_ctx_rollout): the per-server current allocation the
   // chain starts from and ends with, three rows of n_srv words (cur_acc,
   // cur_rep, cur_cost). Allocated on first use, freed in destroy.
@@ -219,7 +225,8 @@ extern "C" int wva_abi(const char *name) {
                WVA_ABI(WVA_PLAN_MAX_S), WVA_ABI(WVA_N_SMALL),   WVA_ABI(WVA_N_MED),
                WVA_ABI(WVA_TICK_STALE), WVA_ABI(WVA_DYN_ROWS),  WVA_ABI(WVA_REC_ROWS),
                WVA_ABI(WVA_CTX_SLOTS),  WVA_ABI(WVA_MAX_BUCKETS), WVA_ABI(WVA_TICK_WIDE_WAVES),
-               WVA_ABI(WVA_TICK_MAX_WAVES)};
+               WVA_ABI(WVA_TICK_MAX_WAVES), WVA_ABI(WVA_LAG_MAX_T), WVA_ABI(WVA_LAG_MAX_N),
+               WVA_ABI(WVA_LAG_CLASSES)};
 #undef WVA_ABI
   if (name == nullptr) return -1;
   for (const auto &e : table)
@@ -1088,6 +1095,17 @@ static int wva_hold_reserve(WvaCtx *c, int n_scen) {
   return 0;
 }
 
+// (re)allocate the lag analysis' arena for `bytes` on each side; on failure
+// nothing is held and reconciles and the plans keep working
+static int wva_lag_reserve(WvaCtx *c, size_t bytes) {
+  if (bytes <= c->lag_cap) return 0;
+  wva_arena_free(c->lag_dev, c->lag_pin);
+  c->lag_cap = 0;
+  if (!wva_arena_alloc(c, bytes, bytes, false, &c->lag_dev, &c->lag_pin)) return -41;
+  c->lag_cap = bytes;
+  return 0;
+}
+
 // the rollout's current-allocation rows; on failure nothing is held and
 // reconciles and plans keep working
 static int wva_roll_reserve(WvaCtx *c) {
@@ -1740,6 +1758,88 @@ extern "C" int wva_ctx_hold(void *ctx, int n_scen, int n_acc, const float *scen_
 }
 
 // ---------------------------------------------------------------------------
+// One lag-analysis pass (wva_lag.inc): the transient response of n_tasks held
+// (cell, scenario) slices at n_times checkpoints. tasks: host WvaLagTask
+// [n_tasks], grouped by kernel class in class order (widest first),
+// class_count[WVA_LAG_CLASSES] of each; dt: host [n_times] interval lengths
+// (msec); n_slots = scenarios x servers, the extent of the records. One upload
+// (table and dt share a segment), one launch per class present — the first on
+// s0, the others on the side streams behind the upload event, joined back —
+// one download, one synchronise. The out pointers name pinned buffers valid
+// until the next lag pass: fp32 [6][n_times][n_slots] (ttft, itl, wait,
+// blocked, rho, in_system), u8 [n_times][n_slots] violated, i32 [n_slots]
+// steps; only the tasks' slots are written. The pass reads nothing a tick
+// staged: the buckets, the fused tick's task table, done[], the sizing memo
+// and the captured graph are not touched. -41: the arena could not be
+// allocated (the context is intact).
+extern "C" int wva_ctx_lag(void *ctx, int n_tasks, const void *tasks, const int *class_count,
+                           int n_times, const double *dt, int n_slots, int max_steps,
+                           const void **out_f, const void **out_violated,
+                           const void **out_steps) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || tasks == nullptr || class_count == nullptr || dt == nullptr) return -31;
+  if (n_tasks < 1 || n_times < 1 || n_times > WVA_LAG_MAX_T || n_slots < 1 || max_steps < 0)
+    return -31;
+  int at = 0;
+  for (int k = 0; k < WVA_LAG_CLASSES; ++k) {
+    if (class_count[k] < 0 || class_count[k] > n_tasks - at) return -31;
+    const int rc = wva_lag_check((const WvaLagTask *)tasks + at, class_count[k], k, n_slots);
+    if (rc != 0) return rc;
+    at += class_count[k];
+  }
+  if (at != n_tasks) return -31;
+  enum { L_IN, L_F, L_VIOL, L_STEPS, L_N };
+  const size_t b_tasks = (size_t)n_tasks * sizeof(WvaLagTask);
+  const size_t sizes[L_N] = {b_tasks + (size_t)n_times * sizeof(double),
+                             (size_t)WVA_LAG_FLOATS * n_times * n_slots * sizeof(float),
+                             (size_t)n_times * n_slots, (size_t)n_slots * sizeof(int)};
+  size_t off[L_N];
+  const size_t bytes = wva_arena_layout(sizes, L_N, off);
+  int rc = wva_lag_reserve(c, bytes);
+  if (rc != 0) return rc;
+  WvaDeviceGuard on_dev(c->dev_dyn);
+  char *d = (char *)c->lag_dev, *h = (char *)c->lag_pin;
+  memcpy(h + off[L_IN], tasks, b_tasks);
+  memcpy(h + off[L_IN] + b_tasks, dt, (size_t)n_times * sizeof(double));
+  if (hipMemcpyAsync(d + off[L_IN], h + off[L_IN], sizes[L_IN], hipMemcpyHostToDevice, c->s0) !=
+      hipSuccess)
+    return -32;
+  WvaLagArgs a = {};
+  a.tasks = (const WvaLagTask *)(d + off[L_IN]);
+  a.dt = (const double *)(d + off[L_IN] + b_tasks);
+  a.n_times = n_times;
+  a.n_slots = n_slots;
+  a.max_steps = max_steps;
+  a.out_f = (float *)(d + off[L_F]);
+  a.violated = (uint8_t *)(d + off[L_VIOL]);
+  a.steps = (int *)(d + off[L_STEPS]);
+  if (hipEventRecord(c->e_up, c->s0) != hipSuccess) return -10;
+  int used = 0;  // streams in use: class launches in table order, widest first
+  at = 0;
+  for (int k = 0; k < WVA_LAG_CLASSES; ++k) {
+    if (class_count[k] == 0) continue;
+    hipStream_t s = used == 0 ? c->s0 : c->side[used - 1];
+    if (used > 0 && hipStreamWaitEvent(s, c->e_up, 0) != hipSuccess) return -11;
+    rc = wva_lag_dispatch(k, class_count[k], at, a, s);
+    if (rc != 0) return rc;
+    if (used > 0 && hipEventRecord(c->e_b[used - 1], s) != hipSuccess) return -12;
+    at += class_count[k];
+    ++used;
+  }
+  for (int i = 1; i < used; ++i)
+    if (hipStreamWaitEvent(c->s0, c->e_b[i - 1], 0) != hipSuccess) return -14;
+  // the three records are consecutive segments: one copy
+  if (hipMemcpyAsync(h + off[L_F], d + off[L_F], bytes - off[L_F], hipMemcpyDeviceToHost,
+                     c->s0) != hipSuccess)
+    return -33;
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -34;
+  if (out_f) *out_f = h + off[L_F];
+  if (out_violated) *out_violated = h + off[L_VIOL];
+  if (out_steps) *out_steps = h + off[L_STEPS];
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // Forecast ensembles: n_paths rollouts of n_steps ticks from one start
 // allocation, delivered in passes of whole paths, then the order statistics
 // across the paths. Ensemble row e * n_steps + s is tick s of path e.
@@ -1931,6 +2031,7 @@ extern "C" void wva_ctx_destroy(void *ctx) {
   wva_hold_release(c);
   wva_lim_release(c);
   wva_arena_free(c->roll_dev, c->roll_pin);
+  wva_arena_free(c->lag_dev, c->lag_pin);
   wva_ens_release(c);
   if (c->lim_static != nullptr) (void)hipFree(c->lim_static);
   free(c->topo);

@@ -3716,6 +3716,10 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_greedy(
                                 capacity, wsi, wsd, pf, pi, px, totals, s_cap);
 }
 
+// Lag analysis (wva_lag_t: the transient response of a held fleet), a sibling
+// of the kernels above with its own task table and launcher.
+#include "wva_lag.inc"
+
 // The native reconcile context (WvaCtx: the per-tick pipeline and the planning
 // passes behind the wva_ctx_* C ABI) launches the kernels above; it is host
 // code of this translation unit.

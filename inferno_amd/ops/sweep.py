@@ -28,6 +28,12 @@ _ABI = {
     "WVA_REC_ROWS": 10,  # rows of the winner-record block
     "WVA_MAX_BUCKETS": 5,  # buckets a context holds (choose_buckets' regimes)
 }
+# the lag analysis' constants (ops/hip/wva_lag.inc), checked the same way
+_LAG_ABI = {
+    "WVA_LAG_MAX_T": 16,  # checkpoints of a lag analysis
+    "WVA_LAG_MAX_N": 1117,  # largest N the widest wva_lag_t instantiation holds
+    "WVA_LAG_CLASSES": 4,  # wva_lag_t instantiations
+}
 MAX_N = _ABI["WVA_MAX_N"]
 # XL LDS tier: fits CDNA4's 160 KiB LDS with the >64KB dynamic-LDS opt-in;
 # override to MAX_N to force such cells to GMEM
@@ -46,6 +52,11 @@ TICK_STALE = _ABI["WVA_TICK_STALE"]
 DYN_ROWS = _ABI["WVA_DYN_ROWS"]
 REC_ROWS = _ABI["WVA_REC_ROWS"]
 MAX_BUCKETS = _ABI["WVA_MAX_BUCKETS"]
+LAG_MAX_T = _LAG_ABI["WVA_LAG_MAX_T"]
+LAG_MAX_N = _LAG_ABI["WVA_LAG_MAX_N"]
+# wva_lag_t<NT, C> instantiations in launch order (widest first): lane l holds C
+# states in registers, so a class takes 11 N + 1 <= NT * C
+LAG_CLASSES = ((512, 24), (256, 12), (64, 12), (64, 2))
 
 
 def choose_buckets(batch_n):
@@ -146,6 +157,19 @@ def gmem_slab_bytes(max_n: int, nt: int) -> int:
     return chunk * nt * 4 + nt * ksub * 8
 
 
+def _lag_task_dtype():
+    import numpy as np
+
+    return np.dtype([("in_tok", "<i4"), ("out_tok", "<i4"), ("N", "<i4"), ("slot", "<i4"),
+                     ("alpha", "<f4"), ("beta", "<f4"), ("gamma", "<f4"), ("delta", "<f4"),
+                     ("t_ttft", "<f4"), ("t_itl", "<f4"), ("pad", "<i4", (2,)),
+                     ("lam0", "<f8"), ("lam1", "<f8")])
+
+
+# one (held cell, scenario) slice of a lag pass: WvaLagTask, 64 bytes
+LAG_TASK_DTYPE = _lag_task_dtype()
+assert LAG_TASK_DTYPE.itemsize == 64
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -168,7 +192,7 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     lib.wva_abi.restype = ctypes.c_int
     lib.wva_abi.argtypes = [ctypes.c_char_p]
-    for name, mirror in _ABI.items():
+    for name, mirror in list(_ABI.items()) + list(_LAG_ABI.items()):
         native = lib.wva_abi(name.encode())
         if native != mirror:
             raise HipKernelError(
@@ -349,6 +373,26 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][6] status counts
         ctypes.POINTER(ctypes.c_void_p),  # out: pinned u64 [n_scen][n_acc] deficits
     ]
+    # lag analysis (engine/fastpath.py FastSweep.lag)
+    lib.wva_ctx_lag.restype = ctypes.c_int
+    lib.wva_ctx_lag.argtypes = [
+        ctypes.c_void_p,
+        ctypes.c_int,  # n_tasks
+        ctypes.c_void_p,  # host LAG_TASK_DTYPE [n_tasks], grouped by class
+        ctypes.c_void_p,  # host i32 [4] tasks per class
+        ctypes.c_int,  # n_times (1..16)
+        ctypes.c_void_p,  # host fp64 [n_times] interval lengths (msec)
+        ctypes.c_int,  # n_slots = scenarios * servers
+        ctypes.c_int,  # max_steps
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned fp32 [6][n_times][n_slots]
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned u8 [n_times][n_slots] violated
+        ctypes.POINTER(ctypes.c_void_p),  # out: pinned i32 [n_slots] steps
+    ]
+    lib.wva_lag_probe_launch.restype = ctypes.c_int
+    lib.wva_lag_probe_launch.argtypes = (
+        [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        + [ctypes.c_void_p] * 5
+    )
     lib.wva_ctx_plan_cells.restype = ctypes.c_int
     lib.wva_ctx_plan_cells.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
     # capacity-limited planning (FastSweep.plan(capacity=...))
@@ -566,6 +610,87 @@ def run_tail_probe(arrays: dict, lam, t, quantiles=(), device: str = "cuda"):
     torch.cuda.synchronize()
     return (d_tail.cpu().numpy()[:, :n_pairs], d_lamq.cpu().numpy()[:, :n_q],
             d_ind.cpu().numpy()[:, :n_q])
+
+
+def lag_task_table(fields: dict, cost):
+    """The task table of a lag pass (WvaLagTask records): ``fields`` holds one
+    array per LAG_TASK_DTYPE field (``pad`` aside), ``cost`` the tasks' cost
+    proxy. Tasks are grouped by the narrowest class that holds their N, classes
+    in launch order, and sorted by descending cost within a class. Returns
+    (table, int32 [4] tasks per class, the permutation applied)."""
+    import numpy as np
+
+    n = np.asarray(fields["N"], dtype=np.int64)
+    if len(n) and (n.min() < 1 or n.max() > LAG_MAX_N):
+        raise HipKernelError(f"lag tasks must have 1 <= N <= {LAG_MAX_N}")
+    cls = np.zeros(len(n), dtype=np.int64)
+    for k, (nt, c) in enumerate(LAG_CLASSES):
+        cls[11 * n + 1 <= nt * c] = k  # later classes are narrower
+    order = np.lexsort((-np.asarray(cost, dtype=np.float64), cls))
+    table = np.zeros(len(n), dtype=LAG_TASK_DTYPE)
+    for name in LAG_TASK_DTYPE.names:
+        if name != "pad":
+            table[name] = np.asarray(fields[name])[order]
+    counts = np.bincount(cls, minlength=len(LAG_CLASSES)).astype(np.int32)
+    return table, counts, order
+
+
+def lag_intervals(times) -> "object":
+    """Interval lengths in msec (float64 [T]) of checkpoint times in seconds."""
+    import numpy as np
+
+    t = np.asarray(times, dtype=np.float64)
+    return np.ascontiguousarray(np.diff(np.concatenate(([0.0], t))) * 1000.0)
+
+
+def run_lag_probe(arrays: dict, lam0, lam1, times, max_steps: int = 1 << 22,
+                  device: str = "cuda"):
+    """One-shot probe of the lag kernel (wva_lag_t), for tests and tools.
+
+    ``arrays``: per-cell CPU tensors or arrays in_tok, out_tok, batch_n, alpha,
+    beta, gamma, delta; ``lam0`` / ``lam1`` (req/msec per replica, float64
+    [n_cells]) the rates before and during the lag; ``times`` the checkpoints
+    in seconds. Every cell is one task, run by the class its N selects.
+    Returns (raw float64 [n_cells, T, 5]: blocked, in_servers, in_system, tput,
+    wait — before the fp32 rounding of the public outputs; steps int32
+    [n_cells], -1 for degenerate rates). A cell above ``max_steps`` has NaN
+    functionals and its step count."""
+    import numpy as np
+    import torch
+
+    if not torch.cuda.is_available():
+        raise HipKernelError("run_lag_probe requires a GPU")
+    lib = load_library()
+    n_cells = len(arrays["batch_n"])
+    dt = lag_intervals(times)
+    n_times = len(dt)
+    if not 1 <= n_times <= LAG_MAX_T or not (dt > 0).all():
+        raise ValueError(f"times must be 1..{LAG_MAX_T} strictly increasing positive seconds")
+    fields = {k: np.asarray(arrays[k]) for k in ("in_tok", "out_tok", "alpha", "beta", "gamma",
+                                                  "delta")}
+    fields["N"] = np.asarray(arrays["batch_n"])
+    fields["slot"] = np.arange(n_cells, dtype=np.int32)
+    fields["t_ttft"] = fields["t_itl"] = np.zeros(n_cells, dtype=np.float32)
+    fields["lam0"] = np.asarray(lam0, dtype=np.float64).reshape(n_cells)
+    fields["lam1"] = np.asarray(lam1, dtype=np.float64).reshape(n_cells)
+    table, counts, order = lag_task_table(fields, fields["N"])
+    d_tasks = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(device)
+    d_dt = torch.from_numpy(dt).to(device)
+    d_f = torch.empty((6, n_times, n_cells), dtype=torch.float32, device=device)
+    d_viol = torch.empty((n_times, n_cells), dtype=torch.uint8, device=device)
+    d_steps = torch.empty(n_cells, dtype=torch.int32, device=device)
+    d_raw = torch.empty((n_cells, n_times, 5), dtype=torch.float64, device=device)
+    rc = lib.wva_lag_probe_launch(
+        table.ctypes.data, _ptr(d_tasks), counts.ctypes.data, n_times, _ptr(d_dt), n_cells,
+        int(max_steps), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), _ptr(d_f),
+        _ptr(d_viol), _ptr(d_steps), _ptr(d_raw),
+    )
+    if rc != 0:
+        raise HipKernelError(f"wva_lag_probe_launch failed: {rc}")
+    torch.cuda.synchronize()
+    raw = np.empty((n_cells, n_times, 5))
+    raw[order] = d_raw.cpu().numpy()  # rows are in task order
+    return raw, d_steps.cpu().numpy()
 
 
 def run_greedy_native(cand_value, cand_acc_type, cand_units, cand_replicas,
