@@ -292,7 +292,9 @@ struct ChainGeom {
                            // (fp32: the rates themselves are fp32 per the
                            // reference; one extra rounding per factor is
                            // reset at every 32-state anchor, keeping the
-                           // sub-chunk product within ~1e-6 relative — and
+                           // sub-chunk product within ~1e-6 relative
+                           // (bound 3.7e-6, measured 8.5e-9 on the chain
+                           // statistics: tests/test_chain_probe_cpu.py) — and
                            // it halves the LDS footprint, doubling the
                            // blocks/CU for large-N cells)
   const double *S_anchor;  // [NT*ksub] log-prefix at anchors
@@ -1340,6 +1342,39 @@ __device__ __forceinline__ bool wva_build_geom(const WvaCell &c, int tid, int an
   return bad_rate;
 }
 
+// Step (4) of wva_cell_body as three helpers, for the chain probe
+// (wva_chain_probe_t) only. wva_cell_body and wva_hold_body keep their own
+// text: built from these helpers every sweep, plan and tick kernel came out
+// with other registers and scratch (docs/design/kernels.md, "Chain probe").
+// Keep the two in step.
+// s(1) and s(N) in fp32: the rate-range bounds (ref queueanalyzer.go:117-119)
+__device__ __forceinline__ void wva_rate_bounds(const WvaCell &c, float &s1, float &sN) {
+  const int num_decode = wva_num_decode(c);
+  float prefill1 = (c.in_tok == 0) ? 0.0f : (c.gamma + c.delta * (float)c.in_tok);
+  s1 = 1.0f / (prefill1 + (float)num_decode * (c.alpha + c.beta));
+  float prefillN = (c.in_tok == 0) ? 0.0f : (c.gamma + c.delta * (float)c.in_tok * (float)c.N);
+  sN = (float)c.N / (prefillN + (float)num_decode * (c.alpha + c.beta * (float)c.N));
+}
+// degenerate perf parameters (zero/negative service times): any_bad is the
+// cell-wide maximum of wva_build_geom's per-lane flag
+__device__ __forceinline__ bool wva_rates_degenerate(double any_bad, float s1, float sN) {
+  return any_bad > 0.0 || !(s1 > 0.0f) || !(sN > 0.0f) || !isfinite(s1) || !isfinite(sN);
+}
+// the model's scalars behind the guard (the geometry m.g is wva_build_geom's)
+__device__ __forceinline__ void wva_model_fill(WvaModel &m, float s1, float sN, int N,
+                                               int analyzer_mode, float cv2, double *smem,
+                                               int tid) {
+  m.logsN = log((double)sN);
+  m.Kstates = 11 * N;
+  m.mode = analyzer_mode;
+  m.cv2d = (double)cv2;
+  m.mu = (double)sN;
+  m.lam_min = (double)s1 * WVA_EPSILON;
+  m.lam_max = (double)sN * (1.0 - WVA_EPSILON);
+  m.scratch = smem;
+  m.tid = tid;
+}
+
 // ---------------------------------------------------------------------------
 // K1: allocate-sweep. wva_cell_body is the computation of ONE cell by NT
 // threads, separate from the block that runs it: `cell` is the cell, `tid` the
@@ -2324,6 +2359,123 @@ __global__ void WVA_NO_PK_F32 __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
   }
 }
 
+// One-shot probe of the PRODUCTION chain path, for tests and tools: the
+// geometry of wva_build_geom<NT, GMEM> (fp32 reciprocals), the model set-up of
+// wva_cell_body, and on it chain_eval<NT, 1>, chain_eval<NT, 2>, dual_bisect<NT>
+// and wva_size_cell<NT>, called as the kernels call them. No memo, no outputs
+// of the sweep. Per cell, all fp64:
+//   ev1[i][4]      chain_eval<NT, 1>(lam[i]): throughput, wait, serv, in_servers,
+//                  stored by thread 0;
+//   ev2[i][2][4]   ONE chain_eval<NT, 2> call: half 0 at lamA[i], half 1 at
+//                  lamB[i], each half's four stored by its first thread;
+//   per target pair k: dual_bisect's lam_star[k][2] and ind[k][2], then
+//                  wva_size_cell's verdict[k] and tput[k] (NaN when false).
+// A rate outside (0, s(N)] stores NaN without an evaluation (a pair: both
+// halves, when either rate is outside): the geometric tail is defined for
+// r <= 1, and exp(Q log r) overflows above it at large N. Every branch depends
+// on the cell or on a value every thread loads from the same address, so the
+// barrier counts of a multi-wave cell match. Degenerate rates: NaN everywhere,
+// indicators -2, verdict 0.
+struct WvaChainProbeArgs {
+  int n_lam;
+  const double *lam;  // device, [n_cells][n_lam] (req/msec)
+  double *ev1;        // device, [n_cells][n_lam][4]
+  int n_pair;
+  const double *lam_a;  // device, [n_cells][n_pair]
+  const double *lam_b;  // device, [n_cells][n_pair]
+  double *ev2;          // device, [n_cells][n_pair][2][4]
+  int n_tgt;
+  const float *t_ttft;  // device, [n_cells][n_tgt] (msec; 0: inactive)
+  const float *t_itl;   // device, [n_cells][n_tgt]
+  double *lam_star;     // device, [n_cells][n_tgt][2] (req/msec)
+  int *ind;             // device, [n_cells][n_tgt][2]
+  int *verdict;         // device, [n_cells][n_tgt]
+  double *tput;         // device, [n_cells][n_tgt] (req/msec)
+};
+__device__ __forceinline__ void wva_chain_probe_store(double *dst, const ChainOut &o) {
+  dst[0] = o.throughput;
+  dst[1] = o.wait;
+  dst[2] = o.serv;
+  dst[3] = o.in_servers;
+}
+template <int NT, bool GMEM>
+__global__ void WVA_NO_PK_F32 __launch_bounds__(NT, WVA_PLAN_MIN_WAVES)
+    wva_chain_probe_t(WvaCellsIn in, WvaCellsOut, int n_blocks, const int *cell_ids, int max_n,
+                      int, float, float *g_inv, double *g_anchor, WvaMemoRec *, unsigned *,
+                      WvaChainProbeArgs p) {
+  extern __shared__ double smem[];
+  if ((int)blockIdx.x >= n_blocks) return;
+  const int cell = cell_ids ? cell_ids[blockIdx.x] : (int)blockIdx.x;
+  const int tid = (int)threadIdx.x;
+  WvaCell c = {};
+  c.cell = cell;
+  c.in_tok = in.in_tok[cell];
+  c.out_tok = in.out_tok[cell];
+  c.N = in.batch_n[cell];
+  c.alpha = in.alpha[cell];
+  c.beta = in.beta[cell];
+  c.gamma = in.gamma[cell];
+  c.delta = in.delta[cell];
+  c.t_tps = in.t_tps[cell];
+  const size_t l0 = (size_t)cell * (size_t)p.n_lam, p0 = (size_t)cell * (size_t)p.n_pair,
+               k0 = (size_t)cell * (size_t)p.n_tgt;
+  const ChainOut none = {NAN, NAN, NAN, NAN};
+
+  WvaModel m;
+  const bool bad_rate =
+      wva_build_geom<NT, GMEM>(c, tid, 0, smem, blockIdx.x, max_n, g_inv, g_anchor, m.g);
+  float s1, sN;
+  wva_rate_bounds(c, s1, sN);
+  const double any_bad = red_max_p<NT, 1>(bad_rate ? 1.0 : 0.0, smem);
+  if (wva_rates_degenerate(any_bad, s1, sN)) {
+    if (tid == 0) {
+      for (int i = 0; i < p.n_lam; ++i) wva_chain_probe_store(p.ev1 + (l0 + i) * 4, none);
+      for (int i = 0; i < 2 * p.n_pair; ++i) wva_chain_probe_store(p.ev2 + (2 * p0 + i) * 4, none);
+      for (int k = 0; k < p.n_tgt; ++k) {
+        p.lam_star[(k0 + k) * 2] = p.lam_star[(k0 + k) * 2 + 1] = NAN;
+        p.ind[(k0 + k) * 2] = p.ind[(k0 + k) * 2 + 1] = -2;
+        p.verdict[k0 + k] = 0;
+        p.tput[k0 + k] = NAN;
+      }
+    }
+    return;
+  }
+  wva_model_fill(m, s1, sN, c.N, 0, 1.0f, smem, tid);
+
+  for (int i = 0; i < p.n_lam; ++i) {
+    const double lam = p.lam[l0 + i];  // same address on every thread: uniform
+    ChainOut o = none;
+    if (lam > 0.0 && lam <= m.mu)
+      o = chain_eval<NT, 1>(lam, m.g, m.logsN, c.N, m.Kstates, m.scratch);
+    if (tid == 0) wva_chain_probe_store(p.ev1 + (l0 + i) * 4, o);
+  }
+  constexpr int W = NT / 2;
+  const int h = tid / W;
+  for (int i = 0; i < p.n_pair; ++i) {
+    const double la = p.lam_a[p0 + i], lb = p.lam_b[p0 + i];
+    ChainOut o = none;
+    if (la > 0.0 && la <= m.mu && lb > 0.0 && lb <= m.mu)
+      o = chain_eval<NT, 2>(h == 0 ? la : lb, m.g, m.logsN, c.N, m.Kstates, m.scratch);
+    if (tid % W == 0) wva_chain_probe_store(p.ev2 + ((p0 + i) * 2 + h) * 4, o);
+  }
+  for (int k = 0; k < p.n_tgt; ++k) {
+    const float t_ttft = p.t_ttft[k0 + k], t_itl = p.t_itl[k0 + k];
+    double lam_star[2];
+    int inds[2];
+    dual_bisect<NT>(t_ttft, t_itl, c, m, lam_star, inds);
+    double tput = NAN;
+    const bool ok = wva_size_cell<NT>(t_ttft, t_itl, c, m, tput);
+    if (tid == 0) {
+      p.lam_star[(k0 + k) * 2] = lam_star[0];
+      p.lam_star[(k0 + k) * 2 + 1] = lam_star[1];
+      p.ind[(k0 + k) * 2] = inds[0];
+      p.ind[(k0 + k) * 2 + 1] = inds[1];
+      p.verdict[k0 + k] = ok ? 1 : 0;
+      p.tput[k0 + k] = ok ? tput : NAN;
+    }
+  }
+}
+
 // winners' wait_tail: per (server, slice) the per-cell value at the winning
 // cell of wva_plan_reduce's record (pi row 3), NaN without a winner
 __global__ void wva_tail_gather(const int *pi, const float *wait_tail, int n_srv, int n_cells,
@@ -2419,12 +2571,13 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
                               const WvaTokArgs *tok = nullptr,
                               const WvaHoldArgs *hold = nullptr,
                               const WvaTailArgs *tail = nullptr,
-                              const WvaProbeArgs *probe = nullptr) {
+                              const WvaProbeArgs *probe = nullptr,
+                              const WvaChainProbeArgs *chain = nullptr) {
   if (n_blocks <= 0) return 0;
   const bool gmem = g_inv != nullptr && g_anchor != nullptr;
   if (max_n < 1) return -2;
   // the percentile kernels model the chain only
-  if ((tail != nullptr || probe != nullptr) && analyzer_mode != 0) return -6;
+  if ((tail != nullptr || probe != nullptr || chain != nullptr) && analyzer_mode != 0) return -6;
   if (!gmem && max_n > WVA_XL_MAX_N) return -2;
   if (gmem && max_n > WVA_HUGE_MAX_N) return -4;
   // the spill path keeps only the header in LDS
@@ -2442,6 +2595,19 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
     return 0;
   };
   int rc = -3;
+  // The chain probe is instantiated in the probe build only (WVA_CHAIN_PROBE,
+  // a second library from this file): its instantiations add callers to
+  // chain_eval and dual_bisect, and with them in the module every other
+  // kernel comes out with other registers and scratch
+  // (docs/design/kernels.md, "Chain probe").
+#ifdef WVA_CHAIN_PROBE
+#define WVA_LAUNCH_LAST(NTV, GM)                            \
+  chain == nullptr ? launch(&wva_sweep_t<NTV, GM>)         \
+                   : launch(&wva_chain_probe_t<NTV, GM>, *chain)
+#else
+  if (chain != nullptr) return -7;  // not the probe build
+#define WVA_LAUNCH_LAST(NTV, GM) launch(&wva_sweep_t<NTV, GM>)
+#endif
 #define WVA_LAUNCH(NTV, GM)                                        \
   rc = probe != nullptr  ? launch(&wva_tail_probe_t<NTV, GM>, *probe) \
        : tail != nullptr ? launch(&wva_tail_plan_t<NTV, GM>, *tail) \
@@ -2449,7 +2615,7 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
        : tok != nullptr  ? launch(&wva_tok_plan_t<NTV, GM>, *tok)  \
        : slo != nullptr  ? launch(&wva_slo_plan_t<NTV, GM>, *slo)  \
        : plan != nullptr ? launch(&wva_plan_t<NTV, GM>, *plan)     \
-                         : launch(&wva_sweep_t<NTV, GM>)
+       : WVA_LAUNCH_LAST(NTV, GM)
   if (gmem) {
     switch (nt) {
       case 256: WVA_LAUNCH(256, true); break;
@@ -2467,6 +2633,7 @@ static int wva_sweep_dispatch(int n_blocks, int max_n, int nt, const int *cell_i
     }
   }
 #undef WVA_LAUNCH
+#undef WVA_LAUNCH_LAST
   if (rc != 0) return rc;
   return (int)hipGetLastError();
 }
@@ -2526,6 +2693,36 @@ extern "C" int wva_tail_probe_launch(
                             WvaCellsOut{}, (float *)g_inv, (double *)g_anchor, nullptr, nullptr,
                             nullptr, nullptr, nullptr, nullptr, nullptr, &pa);
 }
+
+// One bucket of the chain probe (wva_chain_probe_t), dispatched as a sweep
+// bucket is: any of the five widths on the LDS tier, 256 or 1024 threads with
+// slabs. All pointers are device pointers; of the sweep's per-cell arrays only
+// these are read. Present in the probe build only.
+#ifdef WVA_CHAIN_PROBE
+extern "C" int wva_chain_probe_launch(
+    int n_blocks, int max_n, int nt, const int *cell_ids, void *stream, const int *in_tok,
+    const int *out_tok, const int *batch_n, const float *alpha, const float *beta,
+    const float *gamma, const float *delta, const float *t_tps, int n_lam, const double *lam,
+    double *ev1, int n_pair, const double *lam_a, const double *lam_b, double *ev2, int n_tgt,
+    const float *t_ttft, const float *t_itl, double *lam_star, int *ind, int *verdict,
+    double *tput, void *g_inv, void *g_anchor) {
+  if (n_lam < 0 || n_pair < 0 || n_tgt < 0) return -2;
+  WvaCellsIn in = {};
+  in.in_tok = in_tok;
+  in.out_tok = out_tok;
+  in.batch_n = batch_n;
+  in.alpha = alpha;
+  in.beta = beta;
+  in.gamma = gamma;
+  in.delta = delta;
+  in.t_tps = t_tps;
+  const WvaChainProbeArgs pa = {n_lam, lam,    ev1,   n_pair,   lam_a, lam_b,   ev2,
+                                n_tgt, t_ttft, t_itl, lam_star, ind,   verdict, tput};
+  return wva_sweep_dispatch(n_blocks, max_n, nt, cell_ids, 0, 1.0f, (hipStream_t)stream, in,
+                            WvaCellsOut{}, (float *)g_inv, (double *)g_anchor, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &pa);
+}
+#endif
 
 extern "C" int wva_device_count(int *count) { return (int)hipGetDeviceCount(count); }
 

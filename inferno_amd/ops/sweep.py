@@ -12,7 +12,7 @@ import os
 from dataclasses import dataclass
 from typing import Optional
 
-from .build import LIB_PATH, build, needs_build
+from .build import LIB_PATH, build, build_probe, needs_build
 
 # Mirrors of the native library's constants, by their C names. load_library()
 # checks every one against wva_abi() once, so a drift fails loudly at load.
@@ -610,6 +610,113 @@ def run_tail_probe(arrays: dict, lam, t, quantiles=(), device: str = "cuda"):
     torch.cuda.synchronize()
     return (d_tail.cpu().numpy()[:, :n_pairs], d_lamq.cpu().numpy()[:, :n_q],
             d_ind.cpu().numpy()[:, :n_q])
+
+
+_probe_lib: Optional[ctypes.CDLL] = None
+
+
+def load_probe_library() -> ctypes.CDLL:
+    """dlopen the probe build (ops/build.py): the kernel library's sources with
+    the chain probe instantiated, a library of its own so that the kernels the
+    engine runs are compiled without it. Built on first use if missing or stale."""
+    global _probe_lib
+    if _probe_lib is None:
+        lib = ctypes.CDLL(build_probe())
+        lib.wva_chain_probe_launch.restype = ctypes.c_int
+        lib.wva_chain_probe_launch.argtypes = (
+            [ctypes.c_int] * 3 + [ctypes.c_void_p] * 10 + [ctypes.c_int] + [ctypes.c_void_p] * 2
+            + [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 8
+        )
+        _probe_lib = lib
+    return _probe_lib
+
+
+def run_chain_probe(arrays: dict, lam=None, lam_pairs=None, targets=None, nt=None, gmem=None,
+                    device: str = "cuda"):
+    """One-shot probe of the production chain path (wva_chain_probe_t), for
+    tests and tools: chain_eval on the fp32-reciprocal geometry, whole block and
+    half-blocks, and the dual bisection with the sizing on top of it.
+
+    ``arrays``: the sweep's per-cell CPU tensors (in_tok, out_tok, batch_n,
+    alpha, beta, gamma, delta, t_tps are read). ``lam``: float64 [n_cells, P]
+    rates (req/msec) of whole-block evaluations. ``lam_pairs``: float64
+    [n_cells, R, 2], one half-block call per pair (half 0 takes [..., 0]).
+    ``targets``: float32 [n_cells, T, 2] (TTFT, ITL) target pairs (msec, 0 =
+    inactive). Any of the three may be None.
+
+    ``nt`` and ``gmem`` both None: cells go to the block width and geometry tier
+    choose_buckets gives their N. Else every cell runs in one launch of ``nt``
+    threads (64, 128, 256, 512, 1024; default 256) with the geometry in LDS, or
+    with ``gmem`` in global-memory slabs (256 or 1024 threads).
+
+    Returns a dict of numpy arrays: ev1 [n_cells, P, 4] and ev2 [n_cells, R, 2, 4]
+    (throughput req/msec, wait msec, serv msec, in_servers; NaN where a rate is
+    outside (0, s(N)]), lam_star [n_cells, T, 2] (req/msec), ind [n_cells, T, 2]
+    (-1 below, 0 within, +1 above; -2 degenerate rates), verdict [n_cells, T]
+    (wva_size_cell's: 1 feasible) and tput [n_cells, T] (req/msec, NaN when
+    infeasible)."""
+    import numpy as np
+    import torch
+
+    if not torch.cuda.is_available():
+        raise HipKernelError("run_chain_probe requires a GPU")
+    lib = load_probe_library()
+    n_cells = int(arrays["in_tok"].shape[0])
+    batch_n = arrays["batch_n"].numpy()
+    if n_cells < 1 or batch_n.min() < 1:
+        raise ValueError("run_chain_probe needs cells with N >= 1")
+
+    def arg(a, dtype, last):
+        a = np.zeros((n_cells, 0) + last) if a is None else a
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.ndim != 2 + len(last) or a.shape[0] != n_cells or a.shape[2:] != last:
+            raise ValueError(f"expected [{n_cells}, n{''.join(f', {d}' for d in last)}]")
+        return a
+
+    lam = arg(lam, np.float64, ())
+    pairs = arg(lam_pairs, np.float64, (2,))
+    tgt = arg(targets, np.float32, (2,))
+    n_lam, n_pair, n_tgt = lam.shape[1], pairs.shape[1], tgt.shape[1]
+    if nt is None and gmem is None:
+        buckets = choose_buckets(batch_n)
+    else:
+        nt, gmem = 256 if nt is None else int(nt), bool(gmem)
+        if nt not in ((256, 1024) if gmem else (64, 128, 256, 512, 1024)):
+            raise ValueError(f"no chain probe of {nt} threads{' with slabs' if gmem else ''}")
+        bmax = int(batch_n.max())
+        if bmax > (HUGE_MAX_N if gmem else _ABI["WVA_XL_MAX_N"]):
+            raise ValueError(f"N = {bmax} does not fit the tier")
+        buckets = [(nt, None, bmax, n_cells, gmem)]
+    keys = ("in_tok", "out_tok", "batch_n", "alpha", "beta", "gamma", "delta", "t_tps")
+    dev = {k: arrays[k].to(device) for k in keys}
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+    d_lam, d_la, d_lb = up(lam), up(pairs[:, :, 0]), up(pairs[:, :, 1])
+    d_tt, d_ti = up(tgt[:, :, 0]), up(tgt[:, :, 1])
+    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64,  # noqa: E731
+                                    device=device)
+    d_ev1, d_ev2 = nan(n_cells, max(n_lam, 1), 4), nan(n_cells, max(n_pair, 1), 2, 4)
+    d_star, d_tput = nan(n_cells, max(n_tgt, 1), 2), nan(n_cells, max(n_tgt, 1))
+    d_ind = torch.full((n_cells, max(n_tgt, 1), 2), -2, dtype=torch.int32, device=device)
+    d_ok = torch.zeros((n_cells, max(n_tgt, 1)), dtype=torch.int32, device=device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    keep = []
+    for b_nt, ids, bmax, count, b_gmem in buckets:
+        ids_t = torch.from_numpy(ids).to(device) if ids is not None else None
+        slabs = alloc_gmem_slabs(count, bmax, b_nt, device) if b_gmem else (None, None)
+        keep.append((ids_t, slabs))
+        rc = lib.wva_chain_probe_launch(
+            count, bmax, b_nt, _ptr(ids_t) if ids_t is not None else None, stream,
+            *[_ptr(dev[k]) for k in keys], n_lam, _ptr(d_lam), _ptr(d_ev1),
+            n_pair, _ptr(d_la), _ptr(d_lb), _ptr(d_ev2),
+            n_tgt, _ptr(d_tt), _ptr(d_ti), _ptr(d_star), _ptr(d_ind), _ptr(d_ok), _ptr(d_tput),
+            _ptr(slabs[0]) if b_gmem else None, _ptr(slabs[1]) if b_gmem else None,
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_chain_probe_launch(nt={b_nt}) failed: {rc}")
+    torch.cuda.synchronize()
+    host = lambda t, n: t.cpu().numpy()[:, :n]  # noqa: E731
+    return dict(ev1=host(d_ev1, n_lam), ev2=host(d_ev2, n_pair), lam_star=host(d_star, n_tgt),
+                ind=host(d_ind, n_tgt), verdict=host(d_ok, n_tgt), tput=host(d_tput, n_tgt))
 
 
 def lag_task_table(fields: dict, cost):
