@@ -1,6 +1,6 @@
 """Measure the lag analysis on the flagship 512-model fleet.
 
-  python examples/bench_lag.py [--reps 5] [--out profiles/bench_lag.json]
+  python examples/bench_lag.py [--reps 5] [--max-n N] [--out profiles/bench_lag.json]
 
 The allocation is the 1x plan's winners; S = 4 load scales spread over 1x..4x;
 times = (15, 30, 60) s. Before anything is timed the GPU result is compared with
@@ -9,7 +9,10 @@ the CPU golden on a sample of slices. Then it records ms per FastSweep.lag call
 (the same call with the device pass replaced by nothing is not available, so
 the table building is timed on its own), the status histogram, the total
 steps, the state updates per second, and the time of the slowest single task
-(run alone through the probe). Needs a GPU; prints one JSON line.
+(run alone through the probe). With --max-n above LAG_MAX_N the cells up to
+that N go through the tiled kernels: the sample then also holds the cheapest
+wide slices, and the wide tasks, tiles and launches are counted. Needs a GPU;
+prints one JSON line.
 """
 from __future__ import annotations
 
@@ -32,6 +35,7 @@ def main() -> int:
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--sample", type=int, default=12)
     p.add_argument("--max-steps", type=int, default=None)
+    p.add_argument("--max-n", type=int, default=None)
     p.add_argument("--out", default="")
     args = p.parse_args()
 
@@ -42,7 +46,8 @@ def main() -> int:
         return 2
     from inferno_amd.core.system import System
     from inferno_amd.engine import LAG_MAX_STEPS, LAG_OK, LAG_STATUS_NAMES, FastSweep
-    from inferno_amd.ops.sweep import run_lag_probe
+    from inferno_amd.ops.sweep import (LAG_MAX_N, LAG_WIDE_HALO, LAG_WIDE_STRIDE, run_lag_probe,
+                                       run_lag_wide_probe)
     from inferno_amd.utils.synthetic import make_fleet_spec
 
     max_steps = LAG_MAX_STEPS if args.max_steps is None else args.max_steps
@@ -59,16 +64,28 @@ def main() -> int:
     scales = [float(s) for s in np.geomspace(1.0, 4.0, 4)]
     times = (15.0, 30.0, 60.0)
     kw = dict(scales=scales, allocation=alloc, times=times, max_steps=max_steps)
+    if args.max_n is not None:
+        kw["max_n"] = args.max_n
 
     res = fs.lag(**kw)  # warm: context, buffers
     ok = np.argwhere(res.status == LAG_OK)
     # ---- the GPU against the golden on a sample of slices (cheapest first)
     order = ok[np.argsort(res.steps[ok[:, 0], ok[:, 1]])][:: max(len(ok) // args.sample, 1)]
-    servers = sorted({int(i) for _, i in order[: args.sample]})
+    n_of = {}
+    for s, i in ok:
+        k = int(np.nonzero((fs.cell_server == i) & (fs.cell_acc_idx == res.acc_idx[s, i]))[0][0])
+        n_of[(s, i)] = (k, int(fs._stat["override"][k]) if fs._stat["override"][k] > 0 else max(
+            int(fs._stat["perf_max_batch_cfg"][k]) * int(fs._stat["at_tokens"][k])
+            // int(fs._base_load()[2][i]), 1))
+    servers = {int(i) for _, i in order[: args.sample]}
+    # the wide slices with the fewest state updates: the golden walks every state
+    wide = sorted((t for t in n_of if n_of[t][1] > LAG_MAX_N),
+                  key=lambda t: int(res.steps[t]) * n_of[t][1])
+    servers = sorted(servers | {int(i) for _, i in wide[:2]})
     sub_acc = np.full_like(alloc[0], -1)
     sub_acc[servers] = alloc[0][servers]
     gold = fleets["cpu"].lag(scales=scales, allocation=(sub_acc, alloc[1]), times=times,
-                             max_steps=max_steps)
+                             **{k: kw[k] for k in ("max_steps", "max_n") if k in kw})
     worst = 0.0
     for f in ("ttft", "itl", "wait", "blocked", "rho", "in_system"):
         a, b = getattr(gold, f)[:, :, servers], getattr(res, f)[:, :, servers]
@@ -86,12 +103,6 @@ def main() -> int:
         call_ms.append((time.perf_counter() - t0) * 1e3)
     total_steps = int(res.steps[res.status == LAG_OK].sum())
     # state updates: every step moves the K + 1 states of its task
-    n_of = {}
-    for s, i in ok:
-        k = int(np.nonzero((fs.cell_server == i) & (fs.cell_acc_idx == res.acc_idx[s, i]))[0][0])
-        n_of[(s, i)] = (k, int(fs._stat["override"][k]) if fs._stat["override"][k] > 0 else max(
-            int(fs._stat["perf_max_batch_cfg"][k]) * int(fs._stat["at_tokens"][k])
-            // int(fs._base_load()[2][i]), 1))
     updates = sum(int(res.steps[s, i]) * (11 * n + 1) for (s, i), (_, n) in n_of.items())
 
     # ---- the slowest single task, alone on the device through the probe
@@ -110,11 +121,12 @@ def main() -> int:
                out_tok=np.array([out_tok[i_max]], dtype=np.int32),
                batch_n=np.array([n], dtype=np.int32))
     lam = (np.array([rate(base[i_max])]), np.array([rate(res.arrival[s_max, i_max])]))
-    run_lag_probe(one, lam[0], lam[1], times, max_steps=max_steps)
+    probe = run_lag_wide_probe if n > LAG_MAX_N else run_lag_probe
+    probe(one, lam[0], lam[1], times, max_steps=max_steps)
     task_ms = []
     for _ in range(args.reps):
         t0 = time.perf_counter()
-        _, probe_steps = run_lag_probe(one, lam[0], lam[1], times, max_steps=max_steps)
+        _, probe_steps = probe(one, lam[0], lam[1], times, max_steps=max_steps)
         task_ms.append((time.perf_counter() - t0) * 1e3)
     out = {
         "fleet": f"{args.models} models, {len(fs.server_names)} servers", "scales": scales,
@@ -128,6 +140,15 @@ def main() -> int:
                          "us_per_step": statistics.median(task_ms) * 1e3 / int(probe_steps[0])},
         "gpu_vs_golden_max_rel": worst, "golden_sample_servers": len(servers),
     }
+    if wide:
+        slots = [-(-(11 * n_of[t][1] + 1) // 24) * 24 for t in wide]
+        tiles = [-(-g // LAG_WIDE_STRIDE) for g in slots]
+        # a task's segments never cross a checkpoint: up to len(times) - 1 more
+        seg_launches = max(-(-int(res.steps[t]) // LAG_WIDE_HALO) for t in wide)
+        w_updates = sum(int(res.steps[t]) * (11 * n_of[t][1] + 1) for t in wide)
+        out["wide"] = {"tasks": len(wide), "tiles": int(sum(tiles)), "halo": LAG_WIDE_HALO,
+                       "stride": LAG_WIDE_STRIDE, "step_launches_at_least": int(seg_launches),
+                       "state_updates": w_updates}
     line = json.dumps(out)
     print(line)
     if args.out:

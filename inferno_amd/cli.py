@@ -512,7 +512,8 @@ def _cmd_plan_lag(args) -> int:
     backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
     fs = FastSweep(system, backend=backend)
     try:
-        res = fs.lag(scales=scales, times=times)
+        kw = {} if args.lag_max_n is None else {"max_n": args.lag_max_n}
+        res = fs.lag(scales=scales, times=times, **kw)
     except ValueError as e:
         print(f"plan: {e}", file=sys.stderr)
         return 2
@@ -667,6 +668,9 @@ def main() -> None:
                     help="with --hold: lag analysis, the transient latency of the held "
                          "allocation at these checkpoint times after the load steps from the "
                          "base load to each scale, e.g. 15,30,60")
+    pp.add_argument("--lag-max-n", type=int, default=None, metavar="N",
+                    help="with --lag-times: analyse cells up to this batch size (above 1117 "
+                         "through the tiled kernels, at most 32768); wider cells are TOO_WIDE")
     pp.add_argument("--hold", action="store_true",
                     help="hold analysis: the current allocation is not resized; per load scale "
                          "the SLO verdict of every server, the replicas short by accelerator")

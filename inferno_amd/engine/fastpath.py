@@ -32,7 +32,8 @@ import numpy as np
 from ..config import SaturationPolicy
 from ..core import create_allocation
 from ..core.system import System
-from ..ops.sweep import (LAG_MAX_N, LAG_MAX_T, PLAN_MAX_S, lag_intervals, lag_task_table,
+from ..ops.sweep import (LAG_MAX_N, LAG_MAX_T, LAG_WIDE_MAX_N, PLAN_MAX_S, lag_intervals,
+                         lag_task_table, lag_wide_schedule, LAG_WIDE_HALO, LAG_WIDE_STRIDE,
                          run_greedy_native)
 from .native_ctx import CELL_KEYS, NativeCtx
 from .snapshot import FLAG_CUR_EMPTY, FLAG_CUR_SAME, FLAG_HAS_CUR
@@ -199,7 +200,7 @@ LAG_NOT_HELD = 1  # the allocation names no accelerator the server has a cell on
 LAG_IDLE = 2  # no output tokens, or no load before and during the lag
 LAG_INVALID = 3  # degenerate service rates: no model of the cell
 LAG_NO_REPLICAS = 4  # a loaded cell held with zero replicas
-LAG_TOO_WIDE = 5  # N above LAG_MAX_N, what the widest kernel instantiation holds
+LAG_TOO_WIDE = 5  # N above lag()'s max_n (default LAG_MAX_N, the widest one-block kernel)
 LAG_BUDGET = 6  # more than max_steps uniformization steps over the checkpoints
 LAG_STATUS_NAMES = ("OK", "NOT_HELD", "IDLE", "INVALID", "NO_REPLICAS", "TOO_WIDE", "BUDGET")
 _LAG_FLOATS = ("ttft", "itl", "wait", "blocked", "rho", "in_system")  # device row order
@@ -1181,7 +1182,8 @@ class FastSweep:
         return HoldResult(arrival=scen, counts=counts, deficit_by_acc=deficit, cells=cells, **rec)
 
     def lag(self, scales=None, arrival=None, allocation=None, times=(15, 30, 60),
-            from_arrival=None, max_steps: int = LAG_MAX_STEPS) -> LagResult:
+            from_arrival=None, max_steps: int = LAG_MAX_STEPS,
+            max_n: int = LAG_MAX_N) -> LagResult:
         """The TRANSIENT response of a fixed allocation: the latency curve
         inside an actuation lag, where hold() can only say OK or infinite.
 
@@ -1197,7 +1199,8 @@ class FastSweep:
 
         Status per slice, in this order: LAG_NOT_HELD and LAG_IDLE (floats as
         hold() reports them), LAG_INVALID, LAG_NO_REPLICAS, LAG_TOO_WIDE (N >
-        LAG_MAX_N), LAG_BUDGET (more than ``max_steps`` uniformization steps;
+        ``max_n``; above LAG_MAX_N and up to LAG_WIDE_MAX_N the GPU backend runs
+        the tiled kernels, the CPU backend the same golden), LAG_BUDGET (more than ``max_steps`` uniformization steps;
         never clipped) — floats NaN — else LAG_OK. Chain analyzer only. A lag
         pass stages no tick and changes nothing any other call returns."""
         from ..analyzer import (Configuration, DecodeParms, PrefillParms, RequestSize,
@@ -1233,6 +1236,9 @@ class FastSweep:
         max_steps = int(max_steps)
         if not 0 <= max_steps <= np.iinfo(np.int32).max:
             raise ValueError("max_steps must be a non-negative int32")
+        max_n = int(max_n)
+        if not 1 <= max_n <= LAG_WIDE_MAX_N:
+            raise ValueError(f"max_n must be in 1..{LAG_WIDE_MAX_N}")
 
         n_t = len(ts)
         shape = (n_t, n_scen, n_srv)
@@ -1286,7 +1292,7 @@ class FastSweep:
                     status[s, i] = LAG_INVALID
                 elif held == 0:
                     status[s, i] = LAG_NO_REPLICAS
-                elif n_max > LAG_MAX_N:
+                elif n_max > max_n:
                     status[s, i] = LAG_TOO_WIDE
                 else:
                     lam0, lam1 = rate0 / held / 1000.0, rate1 / held / 1000.0
@@ -1299,34 +1305,46 @@ class FastSweep:
                         tasks.append((s, i, k, lam0, lam1, total))
 
         if tasks and self.backend == "gpu":
-            ss, ii, kk = (np.array([t[j] for t in tasks], dtype=np.int64) for j in range(3))
-            n_of = np.array([models[k][1] for k in kk], dtype=np.int32)
-            fields = {"in_tok": in_tok[ii], "out_tok": out_tok[ii], "N": n_of,
-                      "slot": (ss * n_srv + ii).astype(np.int32),
-                      "lam0": np.array([t[3] for t in tasks]),
-                      "lam1": np.array([t[4] for t in tasks])}
-            for f in ("alpha", "beta", "gamma", "delta", "t_ttft", "t_itl"):
-                fields[f] = st[f][kk]
-            # cost proxy K * lam1 * t_T, the steps standing in for the last two
-            table, counts, _ = lag_task_table(fields, n_of * np.array([t[5] for t in tasks]))
             g = getattr(self, "_gpu", None)
             if g is None:
                 g = self._gpu = NativeCtx(n_srv, self._stat, self.cell_server,
                                           self.cell_acc_idx, self.seg_start, self.device)
-            of, ov, osteps = g.lag(table, counts, dt, n_scen * n_srv, max_steps)
-            for r, f in enumerate(_LAG_FLOATS):
-                rec[f][:, ss, ii] = of[r].reshape(shape)[:, ss, ii]
-            violated[:, ss, ii] = ov.reshape(shape)[:, ss, ii] != 0
-            steps[ss, ii] = osteps.reshape(n_scen, n_srv)[ss, ii]
-            # the host chose OK against max_steps from its own count of the
-            # steps; a device that counts differently would report NaN records
-            # (or none) under a status that says OK
-            want = np.array([t[5] for t in tasks], dtype=np.int64)
-            if not np.array_equal(steps[ss, ii], want):
-                from ..ops.sweep import HipKernelError
+            is_wide = np.array([models[t[2]][1] > LAG_MAX_N for t in tasks])
+            for part in (~is_wide, is_wide):  # the one-block classes, then the tiled path
+                sel = [t for t, p in zip(tasks, part) if p]
+                if not sel:
+                    continue
+                ss, ii, kk = (np.array([t[j] for t in sel], dtype=np.int64) for j in range(3))
+                n_of = np.array([models[k][1] for k in kk], dtype=np.int32)
+                fields = {"in_tok": in_tok[ii], "out_tok": out_tok[ii], "N": n_of,
+                          "slot": (ss * n_srv + ii).astype(np.int32),
+                          "lam0": np.array([t[3] for t in sel]),
+                          "lam1": np.array([t[4] for t in sel])}
+                for f in ("alpha", "beta", "gamma", "delta", "t_ttft", "t_itl"):
+                    fields[f] = st[f][kk]
+                want = np.array([t[5] for t in sel], dtype=np.int64)
+                if part is is_wide:
+                    lam_unif = fields["lam1"] + np.array([float(models[k][0].max()) for k in kk])
+                    table, wide, segs, tiles, _ = lag_wide_schedule(
+                        fields, lam_unif, dt, LAG_WIDE_STRIDE, LAG_WIDE_HALO)
+                    of, ov, osteps = g.lag_wide(table, wide, segs, tiles, dt, n_scen * n_srv,
+                                                max_steps, LAG_WIDE_STRIDE, LAG_WIDE_HALO)
+                else:
+                    # cost proxy K * lam1 * t_T, the steps standing in for the last two
+                    table, counts, _ = lag_task_table(fields, n_of * want)
+                    of, ov, osteps = g.lag(table, counts, dt, n_scen * n_srv, max_steps)
+                for r, f in enumerate(_LAG_FLOATS):
+                    rec[f][:, ss, ii] = of[r].reshape(shape)[:, ss, ii]
+                violated[:, ss, ii] = ov.reshape(shape)[:, ss, ii] != 0
+                steps[ss, ii] = osteps.reshape(n_scen, n_srv)[ss, ii]
+                # the host chose OK against max_steps from its own count of the
+                # steps; a device that counts differently would report NaN records
+                # (or none) under a status that says OK
+                if not np.array_equal(steps[ss, ii], want):
+                    from ..ops.sweep import HipKernelError
 
-                raise HipKernelError("wva_ctx_lag: the device's step counts differ from the "
-                                     "host's (lag_window and wva_lag_window are out of step)")
+                    raise HipKernelError("wva_ctx_lag: the device's step counts differ from the "
+                                         "host's (lag_window and wva_lag_window are out of step)")
         else:
             for s, i, k, lam0, lam1, total in tasks:
                 rates, n_max, parms, req = models[k]

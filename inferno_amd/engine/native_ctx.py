@@ -564,6 +564,24 @@ class NativeCtx:
                 _copy_out(out[1], ctypes.c_uint8, (n_times, n_slots)),
                 _copy_out(out[2], ctypes.c_int32, (n_slots,)))
 
+    def lag_wide(self, table: np.ndarray, wide: np.ndarray, segs: np.ndarray, tiles: np.ndarray,
+                 dt: np.ndarray, n_slots: int, max_steps: int, stride: int, halo: int):
+        """wva_ctx_lag_wide on the schedule of ops/sweep.py lag_wide_schedule
+        (``wide`` is written to: the slab offsets). Returns what lag() returns,
+        meaningful at the wide tasks' slots only, and changes as little."""
+        n_times = len(dt)
+        out = [ctypes.c_void_p() for _ in range(3)]
+        rc = self._lib.wva_ctx_lag_wide(
+            self.ctx, table.ctypes.data, wide.ctypes.data, segs.ctypes.data, tiles.ctypes.data,
+            dt.ctypes.data, len(table), len(segs), len(tiles), n_times, n_slots, int(max_steps),
+            int(stride), int(halo), *[ctypes.byref(p) for p in out],
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_lag_wide failed: {rc}")
+        return (_copy_out(out[0], ctypes.c_float, (6, n_times, n_slots)),
+                _copy_out(out[1], ctypes.c_uint8, (n_times, n_slots)),
+                _copy_out(out[2], ctypes.c_int32, (n_slots,)))
+
     def plan_cells(self, n_scen: int) -> dict:
         """Per-cell outputs [S, n_cells] of the planning pass that just ran."""
         cells = {k: np.empty((n_scen, self.n_cells), dtype=d)

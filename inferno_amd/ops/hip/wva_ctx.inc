@@ -159,6 +159,11 @@ struct WvaCtx {
   void *lag_dev;
   void *lag_pin;
   size_t lag_cap;  // bytes each of them holds (0 = not allocated)
+  // wide lag (wva_ctx_lag_wide): its own pair, because the device side also
+  // holds the slabs of a round and the pinned side only tables and records
+  void *lagw_dev = nullptr;
+  void *lagw_pin = nullptr;
+  size_t lagw_dev_cap = 0, lagw_pin_cap = 0;  // bytes each holds
   // forecast rollout (wva_ctx_rollout): the per-server current allocation the
   // chain starts from and ends with, three rows of n_srv words (cur_acc,
   // cur_rep, cur_cost). Allocated on first use, freed in destroy.
@@ -226,7 +231,8 @@ extern "C" int wva_abi(const char *name) {
                WVA_ABI(WVA_TICK_STALE), WVA_ABI(WVA_DYN_ROWS),  WVA_ABI(WVA_REC_ROWS),
                WVA_ABI(WVA_CTX_SLOTS),  WVA_ABI(WVA_MAX_BUCKETS), WVA_ABI(WVA_TICK_WIDE_WAVES),
                WVA_ABI(WVA_TICK_MAX_WAVES), WVA_ABI(WVA_LAG_MAX_T), WVA_ABI(WVA_LAG_MAX_N),
-               WVA_ABI(WVA_LAG_CLASSES)};
+               WVA_ABI(WVA_LAG_CLASSES), WVA_ABI(WVA_LAG_WIDE_MAX_N),
+               WVA_ABI(WVA_LAG_WIDE_HALO)};
 #undef WVA_ABI
   if (name == nullptr) return -1;
   for (const auto &e : table)
@@ -1106,6 +1112,19 @@ static int wva_lag_reserve(WvaCtx *c, size_t bytes) {
   return 0;
 }
 
+// the same for the wide lag pass, whose two sides differ in size
+static int wva_lag_wide_reserve(WvaCtx *c, size_t dev_bytes, size_t pin_bytes) {
+  if (dev_bytes <= c->lagw_dev_cap && pin_bytes <= c->lagw_pin_cap) return 0;
+  dev_bytes = dev_bytes > c->lagw_dev_cap ? dev_bytes : c->lagw_dev_cap;
+  pin_bytes = pin_bytes > c->lagw_pin_cap ? pin_bytes : c->lagw_pin_cap;
+  wva_arena_free(c->lagw_dev, c->lagw_pin);
+  c->lagw_dev_cap = c->lagw_pin_cap = 0;
+  if (!wva_arena_alloc(c, dev_bytes, pin_bytes, false, &c->lagw_dev, &c->lagw_pin)) return -41;
+  c->lagw_dev_cap = dev_bytes;
+  c->lagw_pin_cap = pin_bytes;
+  return 0;
+}
+
 // the rollout's current-allocation rows; on failure nothing is held and
 // reconciles and plans keep working
 static int wva_roll_reserve(WvaCtx *c) {
@@ -1839,6 +1858,49 @@ extern "C" int wva_ctx_lag(void *ctx, int n_tasks, const void *tasks, const int 
   return 0;
 }
 
+// One wide lag pass (wva_lag.inc, "Wide lag"): the held slices with
+// WVA_LAG_MAX_N < N <= WVA_LAG_WIDE_MAX_N, tiled over blocks and segments. The
+// four tables are the host schedule of ops/sweep.py lag_wide_schedule (tasks by
+// descending segment count); `wide` is written to (the slab offsets). One
+// upload, per round of tasks whose slabs fit WVA_LAG_WIDE_SLAB_CAP one init
+// launch and per segment index one step launch and, where a checkpoint closed,
+// one fin launch, all stream-ordered on s0; one download, one synchronise.
+// The out pointers are as for wva_ctx_lag, valid until the next wide pass.
+// Like the narrow pass it touches none of the buckets, the fused tick's
+// table, done[], the memo, the captured graph. -2: inconsistent tables;
+// -41: the arena could not be allocated (the context is intact).
+extern "C" int wva_ctx_lag_wide(void *ctx, const void *tasks, void *wide, const void *segs,
+                                const void *tiles, const double *dt, int n_tasks, int n_segs,
+                                int n_tiles, int n_times, int n_slots, int max_steps, int stride,
+                                int halo, const void **out_f, const void **out_violated,
+                                const void **out_steps) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr || max_steps < 0) return -31;
+  WvaLagWideIn in = {(const WvaLagTask *)tasks, (WvaLagWideTask *)wide, (const WvaLagSeg *)segs,
+                     (const WvaLagTile *)tiles, dt, n_tasks, n_segs, n_tiles, n_times, n_slots,
+                     stride, halo, max_steps};
+  size_t slab = 0, off[WVA_LW_N];
+  int rc = wva_lag_wide_plan(in, WVA_LAG_WIDE_SLAB_CAP, &slab);
+  if (rc != 0) return rc;
+  const size_t bytes = wva_lag_wide_layout(in, slab, false, off);
+  rc = wva_lag_wide_reserve(c, bytes, off[WVA_LW_PART]);
+  if (rc != 0) return rc;
+  WvaDeviceGuard on_dev(c->dev_dyn);
+  char *d = (char *)c->lagw_dev, *h = (char *)c->lagw_pin;
+  wva_lag_wide_stage(in, off, h);
+  if (hipMemcpyAsync(d, h, off[WVA_LW_F], hipMemcpyHostToDevice, c->s0) != hipSuccess) return -32;
+  rc = wva_lag_wide_launch(in, off, d, false, c->s0);
+  if (rc != 0) return rc;
+  if (hipMemcpyAsync(h + off[WVA_LW_F], d + off[WVA_LW_F], off[WVA_LW_PART] - off[WVA_LW_F],
+                     hipMemcpyDeviceToHost, c->s0) != hipSuccess)
+    return -33;
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -34;
+  if (out_f) *out_f = h + off[WVA_LW_F];
+  if (out_violated) *out_violated = h + off[WVA_LW_VIOL];
+  if (out_steps) *out_steps = h + off[WVA_LW_STEPS];
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // Forecast ensembles: n_paths rollouts of n_steps ticks from one start
 // allocation, delivered in passes of whole paths, then the order statistics
@@ -2032,6 +2094,7 @@ extern "C" void wva_ctx_destroy(void *ctx) {
   wva_lim_release(c);
   wva_arena_free(c->roll_dev, c->roll_pin);
   wva_arena_free(c->lag_dev, c->lag_pin);
+  wva_arena_free(c->lagw_dev, c->lagw_pin);
   wva_ens_release(c);
   if (c->lim_static != nullptr) (void)hipFree(c->lim_static);
   free(c->topo);

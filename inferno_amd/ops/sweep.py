@@ -33,6 +33,8 @@ _LAG_ABI = {
     "WVA_LAG_MAX_T": 16,  # checkpoints of a lag analysis
     "WVA_LAG_MAX_N": 1117,  # largest N the widest wva_lag_t instantiation holds
     "WVA_LAG_CLASSES": 4,  # wva_lag_t instantiations
+    "WVA_LAG_WIDE_MAX_N": 32768,  # largest N of the tiled path (the XL ceiling)
+    "WVA_LAG_WIDE_HALO": 768,  # its production halo T, in slots
 }
 MAX_N = _ABI["WVA_MAX_N"]
 # XL LDS tier: fits CDNA4's 160 KiB LDS with the >64KB dynamic-LDS opt-in;
@@ -57,6 +59,14 @@ LAG_MAX_N = _LAG_ABI["WVA_LAG_MAX_N"]
 # wva_lag_t<NT, C> instantiations in launch order (widest first): lane l holds C
 # states in registers, so a class takes 11 N + 1 <= NT * C
 LAG_CLASSES = ((512, 24), (256, 12), (64, 12), (64, 2))
+# the tiled path above LAG_MAX_N (wva_lag_tile_t<512, 24>): a tile loads
+# LAG_WIDE_W slots, T of them halo on each side, and owns S = W - 2 T
+LAG_WIDE_MAX_N = _LAG_ABI["WVA_LAG_WIDE_MAX_N"]
+LAG_WIDE_C = 24
+LAG_WIDE_W = 512 * LAG_WIDE_C
+LAG_WIDE_HALO = _LAG_ABI["WVA_LAG_WIDE_HALO"]
+LAG_WIDE_STRIDE = LAG_WIDE_W - 2 * LAG_WIDE_HALO
+LAG_SEG_FIRST, LAG_SEG_LAST, LAG_SEG_FINAL = 1, 2, 4
 
 
 def choose_buckets(batch_n):
@@ -166,9 +176,22 @@ def _lag_task_dtype():
                      ("lam0", "<f8"), ("lam1", "<f8")])
 
 
+def _lag_wide_dtypes():
+    import numpy as np
+
+    return (np.dtype([("Lam", "<f8"), ("slab", "<i8"), ("tile0", "<i4"), ("n_tiles", "<i4"),
+                      ("seg0", "<i4"), ("n_seg", "<i4")]),
+            np.dtype([("x", "<f8"), ("first", "<i4"), ("count", "<i4"), ("jlo", "<i4"),
+                      ("jhi", "<i4"), ("flags", "<i4"), ("j", "<i4")]),
+            np.dtype([("task", "<i4"), ("b", "<i4")]))
+
+
 # one (held cell, scenario) slice of a lag pass: WvaLagTask, 64 bytes
 LAG_TASK_DTYPE = _lag_task_dtype()
 assert LAG_TASK_DTYPE.itemsize == 64
+# the wide path's per-task record, segment and tile: WvaLagWideTask, WvaLagSeg, WvaLagTile
+LAG_WIDE_DTYPE, LAG_SEG_DTYPE, LAG_TILE_DTYPE = _lag_wide_dtypes()
+assert (LAG_WIDE_DTYPE.itemsize, LAG_SEG_DTYPE.itemsize, LAG_TILE_DTYPE.itemsize) == (32, 32, 8)
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -392,6 +415,19 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
     lib.wva_lag_probe_launch.argtypes = (
         [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         + [ctypes.c_void_p] * 5
+    )
+    # wide lag (FastSweep.lag(max_n=...)): the four tables of lag_wide_schedule,
+    # dt, their five lengths and extents, max_steps, stride, halo
+    lib.wva_ctx_lag_wide.restype = ctypes.c_int
+    lib.wva_ctx_lag_wide.argtypes = (
+        [ctypes.c_void_p] * 6 + [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_void_p)] * 3
+    )
+    lib.wva_lag_wide_probe_launch.restype = ctypes.c_int
+    lib.wva_lag_wide_probe_launch.argtypes = (
+        [ctypes.c_void_p] * 5 + [ctypes.c_int] * 8 + [ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_size_t,
+                                                      ctypes.POINTER(ctypes.c_size_t),
+                                                      ctypes.POINTER(ctypes.c_size_t)]
     )
     lib.wva_ctx_plan_cells.restype = ctypes.c_int
     lib.wva_ctx_plan_cells.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
@@ -798,6 +834,131 @@ def run_lag_probe(arrays: dict, lam0, lam1, times, max_steps: int = 1 << 22,
     raw = np.empty((n_cells, n_times, 5))
     raw[order] = d_raw.cpu().numpy()  # rows are in task order
     return raw, d_steps.cpu().numpy()
+
+
+def lag_segments(j_lo, j_hi, x, halo: int):
+    """The segments of one task: each interval's j_hi steps cut into runs of at
+    most ``halo`` steps that never cross a checkpoint. ``j_lo``, ``j_hi``, ``x``
+    are per interval (lag_window of x = Lam dt). LAG_SEG_DTYPE records."""
+    import numpy as np
+
+    rows = []
+    for j, (lo, hi) in enumerate(zip(j_lo, j_hi)):
+        lo, hi = int(lo), int(hi)
+        for first in range(0, hi, halo):
+            count = min(halo, hi - first)
+            last = first + count == hi
+            flags = ((LAG_SEG_FIRST if first == 0 else 0) | (LAG_SEG_LAST if last else 0)
+                     | (LAG_SEG_FINAL if last and j == len(j_hi) - 1 else 0))
+            rows.append((float(x[j]), first, count, lo, hi, flags, j))
+    return np.array(rows, dtype=LAG_SEG_DTYPE)
+
+
+def lag_wide_schedule(fields: dict, lam_unif, dt, stride: int = LAG_WIDE_STRIDE,
+                      halo: int = LAG_WIDE_HALO):
+    """The host schedule of a wide lag pass. ``fields`` as for lag_task_table
+    (every N in LAG_MAX_N + 1 .. LAG_WIDE_MAX_N), ``lam_unif`` the tasks'
+    uniformization rates, ``dt`` the interval lengths (msec). Tasks are ordered
+    by descending segment count, so that launch l (segment l of every task that
+    has one) covers a prefix of the tasks and of the tile table. Returns (task
+    table, wide table, segments, tiles, the permutation applied)."""
+    import numpy as np
+
+    from ..analyzer.lag import lag_window
+
+    n = np.asarray(fields["N"], dtype=np.int64)
+    if len(n) == 0 or n.min() <= LAG_MAX_N or n.max() > LAG_WIDE_MAX_N:
+        raise HipKernelError(f"wide lag tasks must have {LAG_MAX_N} < N <= {LAG_WIDE_MAX_N}")
+    c = LAG_WIDE_C
+    if stride % c or halo % c or halo < c or stride < c or stride + 2 * halo > LAG_WIDE_W:
+        raise ValueError(f"stride and halo must be multiples of {c} with "
+                         f"stride + 2 halo <= {LAG_WIDE_W}")
+    lam_unif = np.asarray(lam_unif, dtype=np.float64)
+    dt = np.asarray(dt, dtype=np.float64)
+    segs = []
+    for lam in lam_unif:
+        x = lam * dt
+        lo, hi = lag_window(x)
+        segs.append(lag_segments(lo, hi, x, halo))
+    n_seg = np.array([len(s) for s in segs], dtype=np.int64)
+    order = np.argsort(-n_seg, kind="stable")
+    table = np.zeros(len(n), dtype=LAG_TASK_DTYPE)
+    for name in LAG_TASK_DTYPE.names:
+        if name != "pad":
+            table[name] = np.asarray(fields[name])[order]
+    slots = -(-(11 * n[order] + 1) // c) * c
+    wide = np.zeros(len(n), dtype=LAG_WIDE_DTYPE)
+    wide["Lam"] = lam_unif[order]
+    wide["n_tiles"] = -(-slots // stride)
+    wide["tile0"] = np.concatenate(([0], np.cumsum(wide["n_tiles"])[:-1]))
+    wide["n_seg"] = n_seg[order]
+    wide["seg0"] = np.concatenate(([0], np.cumsum(wide["n_seg"])[:-1]))
+    tiles = np.zeros(int(wide["n_tiles"].sum()), dtype=LAG_TILE_DTYPE)
+    tiles["task"] = np.repeat(np.arange(len(n)), wide["n_tiles"])
+    tiles["b"] = np.arange(len(tiles)) - np.repeat(wide["tile0"], wide["n_tiles"])
+    return table, wide, np.concatenate([segs[i] for i in order]), tiles, order
+
+
+def run_lag_wide_probe(arrays: dict, lam0, lam1, times, stride: int = LAG_WIDE_STRIDE,
+                       halo: int = LAG_WIDE_HALO, max_steps: int = 1 << 22,
+                       device: str = "cuda"):
+    """One-shot probe of the tiled lag path (wva_lag_wide_init, wva_lag_tile_t,
+    wva_lag_wide_fin), the sibling of run_lag_probe with the tile stride and
+    halo as arguments. Every cell (LAG_MAX_N < N <= LAG_WIDE_MAX_N) is one
+    task. Returns (raw float64 [n_cells, T, 5], steps int32 [n_cells])."""
+    import numpy as np
+    import torch
+
+    if not torch.cuda.is_available():
+        raise HipKernelError("run_lag_wide_probe requires a GPU")
+    lib = load_library()
+    n_cells = len(arrays["batch_n"])
+    dt = lag_intervals(times)
+    n_times = len(dt)
+    if not 1 <= n_times <= LAG_MAX_T or not (dt > 0).all():
+        raise ValueError(f"times must be 1..{LAG_MAX_T} strictly increasing positive seconds")
+    fields = {k: np.asarray(arrays[k]) for k in ("in_tok", "out_tok", "alpha", "beta", "gamma",
+                                                  "delta")}
+    fields["N"] = np.asarray(arrays["batch_n"])
+    fields["slot"] = np.arange(n_cells, dtype=np.int32)
+    fields["t_ttft"] = fields["t_itl"] = np.zeros(n_cells, dtype=np.float32)
+    fields["lam0"] = np.asarray(lam0, dtype=np.float64).reshape(n_cells)
+    fields["lam1"] = np.asarray(lam1, dtype=np.float64).reshape(n_cells)
+    lam_unif = fields["lam1"] + np.array([_lag_smax(fields, i) for i in range(n_cells)])
+    table, wide, segs, tiles, order = lag_wide_schedule(fields, lam_unif, dt, stride, halo)
+    need = ctypes.c_size_t()
+    offs = (ctypes.c_size_t * 4)()
+    args = (table.ctypes.data, wide.ctypes.data, segs.ctypes.data, tiles.ctypes.data,
+            dt.ctypes.data, len(table), len(segs), len(tiles), n_times, n_cells, int(max_steps),
+            int(stride), int(halo), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    rc = lib.wva_lag_wide_probe_launch(*args, None, 0, ctypes.byref(need), offs)
+    if rc != 0:
+        raise HipKernelError(f"wva_lag_wide_probe_launch failed: {rc}")
+    dev = torch.empty(need.value, dtype=torch.uint8, device=device)
+    rc = lib.wva_lag_wide_probe_launch(*args, _ptr(dev), need.value, ctypes.byref(need), offs)
+    if rc != 0:
+        raise HipKernelError(f"wva_lag_wide_probe_launch failed: {rc}")
+    host = dev[offs[0]:offs[3] + n_cells * n_times * 40].cpu().numpy()
+    at = lambda i, n, t: host[offs[i] - offs[0]:offs[i] - offs[0] + n].view(t)  # noqa: E731
+    raw = np.empty((n_cells, n_times, 5))
+    raw[order] = at(3, n_cells * n_times * 40, np.float64).reshape(n_cells, n_times, 5)
+    return raw, at(2, n_cells * 4, np.int32).copy()
+
+
+def _lag_smax(fields: dict, i: int) -> float:
+    """The largest fp32 service rate of task i of ``fields`` (the analyzer's
+    build_service_rates, which wva_rate_exact matches to the bit)."""
+    from ..analyzer import (Configuration, DecodeParms, PrefillParms, RequestSize,
+                            ServiceParms)
+    from ..analyzer.queue import build_service_rates
+
+    n = int(fields["N"][i])
+    cfg = Configuration(n, 10 * n, ServiceParms(
+        PrefillParms(float(fields["gamma"][i]), float(fields["delta"][i])),
+        DecodeParms(float(fields["alpha"][i]), float(fields["beta"][i]))))
+    rates = build_service_rates(cfg, RequestSize(int(fields["in_tok"][i]),
+                                                 int(fields["out_tok"][i])))
+    return float(rates.max())
 
 
 def run_greedy_native(cand_value, cand_acc_type, cand_units, cand_replicas,
