@@ -1,0 +1,148 @@
+"""Measure the lag path on the flagship 512-model fleet.
+
+  python examples/bench_lag_path.py [--reps 5] [--ticks 32] [--out profiles/bench_lag_path.json]
+
+The forecast is --ticks ticks of --tick-seconds (a ramp 1x..3x and back), the
+allocation the rollout's own winners, one tick late (delay=1). Before anything
+is timed the GPU result is compared with the CPU golden on a sample of servers.
+Then it records ms per FastSweep.lag_path call (median of --reps calls, each
+returning synchronised), the tasks (runs), chunks and launches of the pass, the
+total steps, the state updates per second, and the heaviest record of any chunk
+(N x steps) run alone through the probe. Needs a GPU; prints one JSON line.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main() -> int:
+    p = argparse.ArgumentParser()
+    p.add_argument("--models", type=int, default=512)
+    p.add_argument("--reps", type=int, default=5)
+    p.add_argument("--seed", type=int, default=1234)
+    p.add_argument("--ticks", type=int, default=32)
+    p.add_argument("--tick-seconds", type=float, default=60.0)
+    p.add_argument("--sample", type=int, default=8)
+    p.add_argument("--out", default="")
+    args = p.parse_args()
+
+    import torch
+
+    if not torch.cuda.is_available():
+        print("bench_lag_path needs a GPU", file=sys.stderr)
+        return 2
+    from inferno_amd.core.system import System
+    from inferno_amd.engine import LAG_MAX_STEPS, LAG_OK, LAG_STATUS_NAMES, FastSweep
+    from inferno_amd.ops.sweep import run_lag_path_probe
+    from inferno_amd.utils.synthetic import make_fleet_spec
+
+    spec = make_fleet_spec(args.models, seed=args.seed)
+    fleets = {}
+    for backend in ("gpu", "cpu"):
+        system, _ = System.from_spec(spec)
+        for acc in system.accelerators.values():
+            acc.calculate()
+        fleets[backend] = FastSweep(system, backend=backend)
+    fs = fleets["gpu"]
+    half = args.ticks // 2
+    scales = [float(s) for s in np.concatenate([np.linspace(1.0, 3.0, half),
+                                                np.linspace(3.0, 1.0, args.ticks - half)])]
+    roll = fs.rollout(scales=scales)
+    kw = dict(scales=scales, allocation=(roll.winners.acc_idx, roll.winners.num_replicas),
+              delay=1, tick_seconds=args.tick_seconds)
+    res = fs.lag_path(**kw)  # warm: context, buffers
+    shape = fs.lag_path_pass
+    ok = res.status == LAG_OK
+
+    # ---- the GPU against the golden on the servers with the fewest state updates
+    recs, table = shape["records"], shape["table"]
+    n_of = np.zeros(len(fs.server_names), dtype=np.int64)
+    n_of[table["slot"]] = table["N"]
+    work = (res.steps * ok).sum(axis=0) * n_of
+    servers = [int(i) for i in np.argsort(np.where(work > 0, work, np.inf))[: args.sample]
+               if work[i] > 0]
+    sub = np.full_like(roll.winners.acc_idx, -1)
+    sub[:, servers] = roll.winners.acc_idx[:, servers]
+    start = fs._hold_allocation(None, 1)
+    start_acc = np.full_like(start[0][0], -1)
+    start_acc[servers] = start[0][0][servers]
+    gold = fleets["cpu"].lag_path(**{**kw, "allocation": (sub, roll.winners.num_replicas)},
+                                  start_allocation=(start_acc, start[1][0]))
+    worst = 0.0
+    for f in ("ttft", "itl", "wait", "blocked", "rho", "in_system"):
+        a, b = getattr(gold, f)[:, servers], getattr(res, f)[:, servers]
+        assert np.array_equal(np.isnan(a), np.isnan(b)), f
+        m = ~np.isnan(a)
+        worst = max(worst, float((np.abs(a[m] - b[m]) / np.maximum(np.abs(a[m]), 1.0)).max()))
+    assert np.array_equal(gold.steps[:, servers], res.steps[:, servers])
+    assert worst <= 2e-6, worst  # two fp32 roundings of quantities that agree to 1e-12
+
+    # ---- ms per call
+    call_ms = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        fs.lag_path(**kw)
+        call_ms.append((time.perf_counter() - t0) * 1e3)
+    total_steps = int(res.steps[ok].sum())
+    updates = int(((res.steps * ok).sum(axis=0) * (11 * n_of + 1)).sum())
+
+    # ---- the heaviest record of any chunk, alone on the device through the probe
+    cost = [int(table["N"][r["task"]]) * int(res.steps[r["tick0"]:r["tick0"] + r["n"],
+                                                       table["slot"][r["task"]]].sum())
+            for r in recs]
+    r = recs[int(np.argmax(cost))]
+    t = table[r["task"]]
+    i, sl = int(t["slot"]), slice(int(r["tick0"]), int(r["tick0"] + r["n"]))
+    one = {f: np.array([t[f]], dtype=np.float32) for f in ("alpha", "beta", "gamma", "delta")}
+    one.update(in_tok=np.array([t["in_tok"]], dtype=np.int32),
+               out_tok=np.array([t["out_tok"]], dtype=np.int32),
+               batch_n=np.array([t["N"]], dtype=np.int32))
+    k = int(np.nonzero((fs.cell_server == i) & (fs.cell_acc_idx == res.acc_idx[sl, i][0]))[0][0])
+    tps = float(fs._stat["t_tps"][k])
+    rate = (res.arrival[sl, i].astype(np.float64) / 60.0 if tps == 0.0
+            else np.full(int(r["n"]), tps / float(t["out_tok"])))
+    lam = rate / res.held_replicas[sl, i] / 1000.0
+    probe = lambda: run_lag_path_probe(one, ["empty"], lam[None], np.ones((1, len(lam))),  # noqa: E731
+                                       args.tick_seconds, max_steps=LAG_MAX_STEPS)
+    probe()
+    task_ms = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        _, probe_steps, _ = probe()
+        task_ms.append((time.perf_counter() - t0) * 1e3)
+    assert np.array_equal(probe_steps[0], res.steps[sl, i])
+    out = {
+        "fleet": f"{args.models} models, {len(fs.server_names)} servers", "ticks": args.ticks,
+        "tick_seconds": args.tick_seconds, "delay": 1, "max_steps": LAG_MAX_STEPS,
+        "ms_per_call_median": statistics.median(call_ms), "ms_per_call": call_ms,
+        "status": {n_: int(res.counts[:, j].sum()) for j, n_ in enumerate(LAG_STATUS_NAMES)},
+        "tasks": shape["tasks"], "chunks": shape["chunks"], "launches": shape["launches"],
+        "records": len(recs), "total_steps": total_steps,
+        "state_updates_per_s": updates / (statistics.median(call_ms) * 1e-3),
+        "heaviest_record": {"N": int(t["N"]), "ticks": int(r["n"]),
+                            "steps": int(probe_steps.sum()),
+                            "ms_median_incl_launch_and_copies": statistics.median(task_ms),
+                            "us_per_step": statistics.median(task_ms) * 1e3
+                            / int(probe_steps.sum())},
+        "gpu_vs_golden_max_rel": worst, "golden_sample_servers": len(servers),
+    }
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

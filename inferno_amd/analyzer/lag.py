@@ -120,6 +120,68 @@ def lag_transient(rates: np.ndarray, lam0: float, lam1: float, dt_ms) -> np.ndar
     return out
 
 
+def lag_path_transient(rates: np.ndarray, start, lam, keep, dt_ms: float) -> np.ndarray:
+    """Raw functionals [S, 5] (LAG_FUNCS) at the ends of S consecutive
+    intervals of ``dt_ms`` msec each, interval j under arrival rate ``lam[j]``
+    (req/msec). ``start`` is ("stationary", lam0) or "empty" (all mass in
+    state 0). At the start of interval j the vector is mixed with the empty
+    state, p <- keep[j] p + (1 - keep[j]) e_0 (a scale-out; 1: no change).
+    Per interval: lag_transient's uniformization at Lam_j = lam[j] + max s,
+    the same window and step count (lag_window), non-negative terms only.
+    ops/hip/wva_lag_path.inc is the device form of exactly this."""
+    s = np.asarray(rates, dtype=np.float64)
+    n_max = len(s)
+    k_max = 11 * n_max
+    q_len = k_max - n_max
+    s_max = float(s.max())
+    s_state = np.concatenate(([0.0], s, np.full(q_len, s[-1])))  # death rate of state n
+    in_srv = np.minimum(np.arange(k_max + 1), n_max).astype(np.float64)
+    in_sys = np.arange(k_max + 1, dtype=np.float64)
+    departures = np.arange(1, q_len + 1, dtype=np.float64)
+    if isinstance(start, str):
+        if start != "empty":
+            raise ValueError(f"start must be 'empty' or ('stationary', lam0), got {start!r}")
+        v = stationary(rates, 0.0)
+    else:
+        kind, lam0 = start
+        if kind != "stationary":
+            raise ValueError(f"start must be 'empty' or ('stationary', lam0), got {start!r}")
+        v = stationary(rates, float(lam0))
+    lam = np.asarray(lam, dtype=np.float64)
+    keep = np.asarray(keep, dtype=np.float64)
+    out = np.empty((len(lam), len(LAG_FUNCS)))
+    for j in range(len(lam)):
+        lam_unif = float(lam[j]) + s_max
+        dn = s_state / lam_unif
+        up = np.full(k_max + 1, float(lam[j]) / lam_unif)
+        up[k_max] = 0.0
+        stay = np.maximum(1.0 - up - dn, 0.0)
+
+        def step(v):
+            nv = v * stay
+            nv[1:] += v[:-1] * up[:-1]
+            nv[:-1] += v[1:] * dn[1:]
+            return nv
+
+        v = v * float(keep[j])
+        v[0] += 1.0 - float(keep[j])
+        x = lam_unif * float(dt_ms)
+        lo, hi = (int(b) for b in lag_window(x))
+        for _ in range(lo):
+            v = step(v)
+        w = math.exp(pois_log_pmf(float(lo), x))
+        acc = w * v
+        for k in range(lo + 1, hi + 1):
+            v = step(v)
+            w *= x / k
+            acc += w * v
+        v = acc
+        blocked = float(v[k_max])
+        wait = float(np.dot(v[n_max:k_max], departures)) / (1.0 - blocked) / float(s[-1])
+        out[j] = (blocked, np.dot(v, in_srv), np.dot(v, in_sys), np.dot(v[1:], s_state[1:]), wait)
+    return out
+
+
 def lag_latency(raw: np.ndarray, parms, req, n_max: int):
     """(ttft, itl, rho) per checkpoint from raw functionals [T, 5], with the
     analyzer's definitions: serv = in_servers / tput (0 when nothing departs),

@@ -137,6 +137,14 @@ def cmd_plan(args) -> int:
                              "over sampled load paths; it does not combine with --rollout, "
                              "--hold, --slo-scales, --token-scales, --limited or --capacity")
         return _cmd_plan_ensemble(args)
+    if getattr(args, "lag_path", False):
+        if (limited or args.slo_scales is not None or args.token_scales is not None
+                or args.rollout or args.hold or args.lag_times is not None):
+            raise SystemExit("plan: --lag-path rolls the forecast out itself and follows it "
+                             "with the allocation late; it does not combine with --rollout, "
+                             "--hold, --lag-times, --slo-scales, --token-scales, --limited or "
+                             "--capacity")
+        return _cmd_plan_lag_path(args)
     if args.lag_times is not None:
         if not args.hold:
             raise SystemExit("plan: --lag-times goes with --hold (the allocation that is held)")
@@ -556,6 +564,63 @@ def _cmd_plan_lag(args) -> int:
     return 0
 
 
+def _cmd_plan_lag_path(args) -> int:
+    """Lag path: the forecast rolled out, then followed by its own decisions
+    --lag-delay ticks late; per tick what users see at its end."""
+    from .engine import LAG_OK, LAG_STATUS_NAMES, FastSweep, SweepEngine
+
+    if args.scales is None:
+        raise SystemExit("plan: --lag-path needs --scales (the forecast, one factor per tick)")
+    scales = _parse_scales(args.scales)
+    system, _ = _load_system(args.spec)
+    backend = SweepEngine(backend=args.backend).backend  # resolves "auto"
+    fs = FastSweep(system, backend=backend)
+    try:
+        roll = fs.rollout(scales=scales)
+        res = fs.lag_path(scales=scales, delay=args.lag_delay, tick_seconds=args.tick_seconds,
+                          allocation=(roll.winners.acc_idx, roll.winners.num_replicas))
+    except ValueError as e:
+        print(f"plan: {e}", file=sys.stderr)
+        return 2
+
+    def num(x):  # NaN has no JSON number
+        return float(x) if x == x else None
+
+    ticks = [{
+        "tick": j,
+        "scale": scale,
+        "status": {n: int(res.counts[j, c]) for c, n in enumerate(LAG_STATUS_NAMES)},
+        "violated": int(res.violations[j]),
+    } for j, scale in enumerate(scales)]
+    servers = [{
+        "server": fs.server_names[i],
+        "firstViolation": int(res.first_violation[i]) if res.first_violation[i] >= 0 else None,
+        "ticksViolated": int(res.ticks_violated[i]),
+        "status": [LAG_STATUS_NAMES[c] for c in res.status[:, i]],
+        "ttft": [num(x) for x in res.ttft[:, i]],
+        "itl": [num(x) for x in res.itl[:, i]],
+        "blocked": [num(x) for x in res.blocked[:, i]],
+    } for i in range(len(fs.server_names))
+        if (res.status[:, i] != LAG_OK).any() or res.first_violation[i] >= 0]
+    if args.json:
+        print(json.dumps({"backend": backend, "servers": len(fs.server_names),
+                          "tickSeconds": res.tick_seconds, "delay": args.lag_delay,
+                          "lagPath": ticks, "serversOfNote": servers}, indent=2))
+        return 0
+    for t in ticks:
+        print(f"tick {t['tick']:>3} (scale {t['scale']:g}): "
+              + ", ".join(f"{n} {c}" for n, c in t["status"].items() if c)
+              + f"; servers over their SLO at its end: {t['violated']}")
+    for b in servers:
+        first = "-" if b["firstViolation"] is None else f"tick {b['firstViolation']}"
+        ttft = " ".join("nan" if x is None else f"{x:.1f}" for x in b["ttft"])
+        print(f"  {b['server']:<24} SLO broken from {first:<8} in {b['ticksViolated']} ticks; "
+              f"ttft ms {ttft}")
+    print(f"({len(fs.server_names)} servers, backend {backend}; ticks of {res.tick_seconds:g} s, "
+          f"the allocation {args.lag_delay} tick(s) behind the rollout's decisions)")
+    return 0
+
+
 def _cmd_plan_hold(args) -> int:
     """Hold analysis: the current allocation, unchanged, at each load scale."""
     from .engine import HOLD_OK, HOLD_STATUS_NAMES, FastSweep, SweepEngine
@@ -664,6 +729,14 @@ def main() -> None:
     pp.add_argument("--rollout", action="store_true",
                     help="forecast rollout: --scales are consecutive steps, each reconciled "
                          "against the allocation the step before it left behind")
+    pp.add_argument("--lag-path", action="store_true",
+                    help="lag path: --scales are consecutive ticks; the rollout's decisions "
+                         "take effect --lag-delay ticks late and every server's queue is "
+                         "carried from tick to tick: per tick, what users see at its end")
+    pp.add_argument("--lag-delay", type=int, default=1, metavar="TICKS",
+                    help="with --lag-path: ticks between a decision and its effect (default 1)")
+    pp.add_argument("--tick-seconds", type=float, default=60.0, metavar="SECONDS",
+                    help="with --lag-path: length of a tick (default 60)")
     pp.add_argument("--lag-times", default=None, metavar="SECONDS",
                     help="with --hold: lag analysis, the transient latency of the held "
                          "allocation at these checkpoint times after the load steps from the "

@@ -236,6 +236,31 @@ class LagResult:
     violations: np.ndarray  # int64 [T, S]: servers violated per checkpoint
 
 
+@dataclass
+class LagPathResult:
+    """Lag path: the transient response along a forecast (FastSweep.lag_path).
+    Per-tick arrays are [S, n_servers]; the state at the END of tick j."""
+
+    ttft: np.ndarray  # float32 msec; NaN where the status has no evaluation
+    itl: np.ndarray  # float32 msec
+    wait: np.ndarray  # float32 msec: mean queueing wait of an accepted request
+    blocked: np.ndarray  # float32: probability that the queue is full
+    rho: np.ndarray  # float32
+    in_system: np.ndarray  # float32: mean requests in the system (per replica)
+    violated: np.ndarray  # bool: ttft or itl above its (non-zero) target
+    status: np.ndarray  # int32, one of LAG_*
+    steps: np.ndarray  # int32: uniformization steps of the tick, 0 outside a run
+    held_replicas: np.ndarray  # int32: the replicas in force
+    acc_idx: np.ndarray  # int32: the accelerator in force, -1 where NOT_HELD
+    first_violation: np.ndarray  # int32 [n_servers]: first violated tick, -1 for none
+    ticks_violated: np.ndarray  # int32 [n_servers]
+    counts: np.ndarray  # int64 [S, 7]: servers per status
+    violations: np.ndarray  # int64 [S]: servers violated per tick
+    tick_seconds: float
+    arrival: np.ndarray  # float32 [S, n_servers]
+    from_arrival: np.ndarray  # float32 [n_servers]: the load before tick 0
+
+
 # Longest forecast one rollout() takes, and the steps one device pass of it
 # holds (at most PLAN_MAX_S): longer forecasts run as consecutive passes, each
 # starting from the allocation the one before it ended with.
@@ -1365,6 +1390,240 @@ class FastSweep:
             acc_idx=np.where(status == LAG_NOT_HELD, -1, acc).astype(np.int32), steps=steps,
             times=ts, arrival=scen, from_arrival=arr0, counts=counts,
             violations=violated.sum(axis=2).astype(np.int64), **rec)
+
+    def lag_path(self, scales=None, arrival=None, allocation=None, delay: int = 1,
+                 start_allocation=None, from_arrival=None, tick_seconds: float = 60.0,
+                 max_steps: int = LAG_MAX_STEPS) -> LagPathResult:
+        """The transient response ALONG a forecast: what users see, tick by
+        tick, while an allocation that is ``delay`` ticks late follows the load.
+        lag() takes one load step from a stationary start; here the state of
+        every server is carried from tick to tick, so the queue that filled
+        during tick 3 is still there at the start of tick 4.
+
+        ``scales`` or ``arrival``: S consecutive ticks of ``tick_seconds`` each
+        (as for rollout(), 1 <= S <= ROLLOUT_MAX_STEPS). ``allocation`` =
+        (acc_idx, num_replicas), both [S, n_servers] (a negative accelerator:
+        holds nothing, as in hold()); the allocation in force during tick j is
+        row j - delay, and ``start_allocation`` ([n_servers] pair, default the
+        current allocation as hold() reads it) for j < delay. ``from_arrival``
+        ([n_servers], default the base load) is the load before tick 0.
+
+        Model of one server. The per-replica rate of tick j is formed as lag()
+        forms it, from arrival[j] and the replicas in force. The tick axis
+        splits into runs: maximal sequences of consecutive ticks that name the
+        same accelerator, on which the server has a cell with a valid model and
+        N <= LAG_MAX_N, with R > 0. A tick outside a run has lag()'s status by
+        lag()'s precedence (LAG_NOT_HELD, LAG_IDLE, LAG_INVALID,
+        LAG_NO_REPLICAS, LAG_TOO_WIDE) and lag()'s floats for it; LAG_IDLE only
+        without output tokens or when the server has no load in
+        ``from_arrival`` and in every tick — a zero-arrival tick inside a run is
+        an ordinary drain interval. A run that begins at tick 0 on the start
+        allocation's accelerator with R_start > 0 starts from the stationary
+        distribution at from_arrival / R_start (lag()'s p(0)); every other run
+        starts empty: new replicas on a new accelerator have no queue. A
+        replica change takes effect at the tick boundary (the start allocation
+        -> tick 0 included): scale-out R_old -> R_new mixes in empty replicas,
+        p <- f p + (1 - f) e_0 with f = R_old / R_new in fp64; scale-in leaves p
+        as it is (the removed replicas leave with their requests). Each tick is
+        one interval at its own rate with lag()'s uniformization, window and
+        functionals; the state at the END of tick j gives ttft, itl, wait,
+        blocked, rho, in_system and violated[j] (fp32 targets). A tick whose own
+        step count exceeds ``max_steps`` truncates its run: it and the rest of
+        the run are LAG_BUDGET, nothing is clipped.
+
+        Limits: cells with N > LAG_MAX_N stay LAG_TOO_WIDE (the tiled kernels
+        carry no state between calls), and there are no time-averaged
+        functionals inside a tick. Chain analyzer only. On the GPU the ticks
+        run in chunks of at most 16 whose step sums stay within ``max_steps``
+        per block, the state carried between the launches on the device. The
+        pass stages no tick and changes nothing any other call returns."""
+        from ..analyzer.lag import lag_latency, lag_path_transient, lag_window
+        from ..ops.sweep import (LAG_PATH_EMPTY, LAG_PATH_STATIONARY, HipKernelError,
+                                 lag_path_schedule)
+
+        if getattr(self.system, "analyzer_mode", "mm1k") == "mg1":
+            raise ValueError("lag_path() needs the chain analyzer: the M/G/1 evaluator has no "
+                             "transient form")
+        scen = self._plan_scenarios(scales, arrival, ROLLOUT_MAX_STEPS, "lag_path()", "ticks")
+        n_t, n_srv = scen.shape
+        if allocation is None:
+            raise ValueError("lag_path() needs allocation=(acc_idx, num_replicas) per tick")
+        acc, rep = self._hold_allocation(allocation, n_t)
+        acc0, rep0 = (a[0] for a in self._hold_allocation(start_allocation, 1))
+        try:
+            bad_delay = int(delay) != delay or int(delay) < 0
+        except (TypeError, ValueError):
+            bad_delay = True
+        if bad_delay:
+            raise ValueError(f"delay must be a non-negative integer, got {delay!r}")
+        delay = int(delay)
+        try:
+            dt = float(tick_seconds) * 1000.0
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"tick_seconds is not numeric: {e}") from None
+        if not (np.isfinite(dt) and dt > 0):
+            raise ValueError("tick_seconds must be finite and positive")
+        if from_arrival is None:
+            arr0 = np.asarray(self._base_load()[0], dtype=np.float32)
+        else:
+            try:
+                arr0 = np.asarray(from_arrival, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"from_arrival is not numeric: {e}") from None
+            if arr0.shape != (n_srv,) or not np.isfinite(arr0).all() or (arr0 < 0).any():
+                raise ValueError(f"from_arrival must be [{n_srv}] finite non-negative rates")
+            arr0 = arr0.astype(np.float32)
+        max_steps = int(max_steps)
+        if not 0 <= max_steps <= np.iinfo(np.int32).max:
+            raise ValueError("max_steps must be a non-negative int32")
+        # the allocation in force: row j - delay, the start allocation before
+        lead = min(delay, n_t)
+        acc = np.concatenate([np.broadcast_to(acc0, (lead, n_srv)), acc[:n_t - lead]])
+        rep = np.concatenate([np.broadcast_to(rep0, (lead, n_srv)), rep[:n_t - lead]])
+
+        shape = (n_t, n_srv)
+        rec = {k: np.zeros(shape, dtype=np.float32) for k in _LAG_FLOATS}
+        violated = np.zeros(shape, dtype=bool)
+        status = np.full(shape, LAG_NOT_HELD, dtype=np.int32)
+        steps = np.zeros(shape, dtype=np.int32)
+        _, in_tok, out_tok = self._base_load()
+        st = self._stat
+        cell_of = np.full((n_srv, max(len(self.acc_names), 1)), -1, dtype=np.int64)
+        cell_of[self.cell_server, self.cell_acc_idx] = np.arange(self.n_cells)
+        models = {}
+        runs = []  # (i, k, first tick, start, lam0, lam [n], keep [n], steps [n])
+        for i in range(n_srv):
+            n_out = int(out_tok[i])
+            cells = np.where(acc[:, i] >= 0, cell_of[i, np.maximum(acc[:, i], 0)], -1)
+            held = cells >= 0
+            if not held.any():
+                continue
+            tps = st["t_tps"][np.maximum(cells, 0)].astype(np.float64)
+            # req/s per tick as lag() forms them: a TPS target replaces the arrival
+            rate0, rate = (np.where(tps == 0.0, a / 60.0, tps / max(n_out, 1)) * (n_out != 0)
+                           for a in (float(arr0[i]), scen[:, i].astype(np.float64)))
+            idle = n_out == 0 or not ((rate0[held] != 0).any() or (rate[held] != 0).any())
+            j = 0
+            while j < n_t:
+                k = int(cells[j])
+                if k < 0:
+                    j += 1
+                    continue
+                if idle:
+                    status[j, i] = LAG_IDLE
+                    if st["min_replicas"][k] != 0:
+                        rec["itl"][j, i] = np.float32(st["alpha"][k]) + np.float32(st["beta"][k])
+                        rec["ttft"][j, i] = np.float32(st["gamma"][k]) + np.float32(st["delta"][k])
+                    j += 1
+                    continue
+                for f in _LAG_FLOATS:
+                    rec[f][j, i] = np.nan
+                rates, n_max, _, _ = self._lag_model(models, k, int(in_tok[i]), n_out)
+                if rates is None or rep[j, i] == 0 or n_max > LAG_MAX_N:
+                    status[j, i] = (LAG_INVALID if rates is None else
+                                    LAG_NO_REPLICAS if rep[j, i] == 0 else LAG_TOO_WIDE)
+                    j += 1
+                    continue
+                end = j + 1  # the run: the same cell with replicas
+                while end < n_t and cells[end] == k and rep[end, i] > 0:
+                    end += 1
+                r = rep[j:end, i].astype(np.float64)
+                before = np.concatenate(([float(rep0[i]) if j == 0 and acc0[i] == acc[0, i]
+                                          else 0.0], r[:-1]))
+                keep = np.where((before > 0) & (r > before), before / r, 1.0)
+                lam = rate[j:end] / r / 1000.0
+                want = lag_window((lam + float(rates.max())) * dt)[1]
+                steps[j:end, i] = np.minimum(want, 2147483000.0).astype(np.int32)
+                for f in _LAG_FLOATS:
+                    rec[f][j:end, i] = np.nan
+                over = np.nonzero(want > max_steps)[0]
+                n_ok = int(over[0]) if len(over) else end - j
+                status[j:j + n_ok, i] = LAG_OK
+                status[j + n_ok:end, i] = LAG_BUDGET
+                if n_ok:
+                    stationary = before[0] > 0
+                    runs.append((i, k, j, LAG_PATH_STATIONARY if stationary else LAG_PATH_EMPTY,
+                                 float(rate0[j]) / before[0] / 1000.0 if stationary else 0.0,
+                                 lam[:n_ok], keep[:n_ok], want[:n_ok].astype(np.int64)))
+                j = end
+
+        if runs and self.backend == "gpu":
+            g = getattr(self, "_gpu", None)
+            if g is None:
+                g = self._gpu = NativeCtx(n_srv, self._stat, self.cell_server,
+                                          self.cell_acc_idx, self.seg_start, self.device)
+            ii, kk = (np.array([r[j] for r in runs], dtype=np.int64) for j in range(2))
+            fields = {"in_tok": in_tok[ii], "out_tok": out_tok[ii], "slot": ii.astype(np.int32),
+                      "N": np.array([models[k][1] for k in kk], dtype=np.int32),
+                      "lam0": np.array([r[4] for r in runs]),
+                      "start": np.array([r[3] for r in runs])}
+            for f in ("alpha", "beta", "gamma", "delta", "t_ttft", "t_itl"):
+                fields[f] = st[f][kk]
+            desc = np.zeros((n_srv, n_t, 2))
+            desc[:, :, 1] = 1.0
+            for i, _, j, _, _, lam, keep, _ in runs:
+                desc[i, j:j + len(lam), 0], desc[i, j:j + len(lam), 1] = lam, keep
+            table, recs, launches, bounds = lag_path_schedule(
+                fields, [r[2] for r in runs], [r[7] for r in runs], n_t, max_steps)
+            # for tools (examples/bench_lag_path.py): the shape of the pass that ran
+            self.lag_path_pass = {"tasks": len(table), "chunks": len(bounds) - 1,
+                                  "launches": len(launches), "records": recs, "table": table}
+            of, ov, osteps = g.lag_path(table, recs, desc, launches, n_t, n_srv, max_steps, dt)
+            for i, _, j, _, _, lam, _, want in runs:
+                sl = slice(j, j + len(lam))
+                for r, f in enumerate(_LAG_FLOATS):
+                    rec[f][sl, i] = of[r][sl, i]
+                violated[sl, i] = ov[sl, i] != 0
+                # the schedule and the OK verdicts come from the host's count
+                if not np.array_equal(osteps[sl, i], want):
+                    raise HipKernelError("wva_ctx_lag_path: the device's step counts differ from "
+                                         "the host's (lag_window and wva_lag_window are out of "
+                                         "step)")
+        else:
+            for i, k, j, start, lam0, lam, keep, _ in runs:
+                rates, n_max, parms, req = models[k]
+                raw = lag_path_transient(
+                    rates, ("stationary", lam0) if start == LAG_PATH_STATIONARY else "empty",
+                    lam, keep, dt)
+                sl = slice(j, j + len(lam))
+                ttft, itl, rho = lag_latency(raw, parms, req, n_max)
+                rec["ttft"][sl, i], rec["itl"][sl, i], rec["rho"][sl, i] = ttft, itl, rho
+                rec["wait"][sl, i], rec["blocked"][sl, i] = raw[:, 4], raw[:, 0]
+                rec["in_system"][sl, i] = raw[:, 2]
+                t_ttft, t_itl = st["t_ttft"][k], st["t_itl"][k]
+                violated[sl, i] = ((t_ttft != 0) & (ttft > t_ttft)) | ((t_itl != 0) & (itl > t_itl))
+        counts = np.stack([(status == c).sum(axis=1) for c in range(len(LAG_STATUS_NAMES))],
+                          axis=1).astype(np.int64)
+        return LagPathResult(
+            violated=violated, status=status, steps=steps, held_replicas=rep,
+            acc_idx=np.where(status == LAG_NOT_HELD, -1, acc).astype(np.int32),
+            first_violation=np.where(violated.any(axis=0), violated.argmax(axis=0),
+                                     -1).astype(np.int32),
+            ticks_violated=violated.sum(axis=0).astype(np.int32), counts=counts,
+            violations=violated.sum(axis=1).astype(np.int64), tick_seconds=dt / 1000.0,
+            arrival=scen, from_arrival=arr0, **rec)
+
+    def _lag_model(self, models: dict, k: int, in_tok: int, out_tok: int):
+        """lag()'s model of cell k at its server's token counts, cached in
+        ``models``: (fp32 service rates or None when degenerate, N, service
+        parms, request size)."""
+        if k not in models:
+            from ..analyzer import (Configuration, DecodeParms, PrefillParms, RequestSize,
+                                    ServiceParms)
+            from ..analyzer.queue import build_service_rates
+
+            st = self._stat
+            n_max = int(st["override"][k]) if st["override"][k] > 0 else max(
+                int(st["perf_max_batch_cfg"][k]) * int(st["at_tokens"][k]) // out_tok, 1)
+            cfg = Configuration(n_max, 10 * n_max, ServiceParms(
+                PrefillParms(float(st["gamma"][k]), float(st["delta"][k])),
+                DecodeParms(float(st["alpha"][k]), float(st["beta"][k]))))
+            req = RequestSize(in_tok, out_tok)
+            rates = build_service_rates(cfg, req)
+            if not np.all(np.isfinite(rates)) or np.any(rates <= 0):
+                rates = None
+            models[k] = (rates, n_max, cfg.service_parms, req)
+        return models[k]
 
     def _hold_allocation(self, allocation, n_scen: int):
         """Validate hold()'s allocation and return (acc_idx, num_replicas) as

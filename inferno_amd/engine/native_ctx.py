@@ -582,6 +582,24 @@ class NativeCtx:
                 _copy_out(out[1], ctypes.c_uint8, (n_times, n_slots)),
                 _copy_out(out[2], ctypes.c_int32, (n_slots,)))
 
+    def lag_path(self, table: np.ndarray, recs: np.ndarray, desc: np.ndarray,
+                 launches: np.ndarray, n_ticks: int, n_slots: int, max_steps: int, dt_ms: float):
+        """wva_ctx_lag_path on the schedule of ops/sweep.py lag_path_schedule and
+        the interval descriptors (float64 [n_slots, n_ticks, 2]: lam, keep):
+        fp32 [6, S, n_slots], uint8 [S, n_slots] violated and int32 [S, n_slots]
+        steps, meaningful at the tasks' ticks only. Changes as little as lag()."""
+        out = [ctypes.c_void_p() for _ in range(3)]
+        rc = self._lib.wva_ctx_lag_path(
+            self.ctx, table.ctypes.data, recs.ctypes.data, desc.ctypes.data, launches.ctypes.data,
+            len(table), len(recs), len(launches), n_ticks, n_slots, int(max_steps), float(dt_ms),
+            *[ctypes.byref(p) for p in out],
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_lag_path failed: {rc}")
+        return (_copy_out(out[0], ctypes.c_float, (6, n_ticks, n_slots)),
+                _copy_out(out[1], ctypes.c_uint8, (n_ticks, n_slots)),
+                _copy_out(out[2], ctypes.c_int32, (n_ticks, n_slots)))
+
     def plan_cells(self, n_scen: int) -> dict:
         """Per-cell outputs [S, n_cells] of the planning pass that just ran."""
         cells = {k: np.empty((n_scen, self.n_cells), dtype=d)

@@ -31,6 +31,7 @@ NATIVE_SRCS = [
 NATIVE_HDRS = [
     os.path.join(OPS_DIR, "hip", "wva_ctx.inc"),
     os.path.join(OPS_DIR, "hip", "wva_lag.inc"),
+    os.path.join(OPS_DIR, "hip", "wva_lag_path.inc"),
     os.path.join(OPS_DIR, "native", "wva_stage.h"),
     os.path.join(OPS_DIR, "native", "wva_arena.h"),
 ]

@@ -164,6 +164,11 @@ struct WvaCtx {
   void *lagw_dev = nullptr;
   void *lagw_pin = nullptr;
   size_t lagw_dev_cap = 0, lagw_pin_cap = 0;  // bytes each holds
+  // lag paths (wva_ctx_lag_path): the same split, the device side also holds
+  // the carry slab of a round
+  void *lagp_dev = nullptr;
+  void *lagp_pin = nullptr;
+  size_t lagp_dev_cap = 0, lagp_pin_cap = 0;
   // forecast rollout (wva_ctx_rollout): the per-server current allocation the
   // chain starts from and ends with, three rows of n_srv words (cur_acc,
   // cur_rep, cur_cost). Allocated on first use, freed in destroy.
@@ -1901,6 +1906,61 @@ extern "C" int wva_ctx_lag_wide(void *ctx, const void *tasks, void *wide, const 
   return 0;
 }
 
+// One lag-path pass (wva_lag_path.inc): the transient response of n_tasks runs
+// along n_ticks ticks of dt msec. The four tables are the host schedule of
+// ops/sweep.py lag_path_schedule: tasks (one per run, with its carry offset),
+// records (the ticks of a task one launch covers) in launch order, the
+// interval descriptors [n_slots][n_ticks] of {lam, keep}, and the launches
+// (rec0, count, class, round) by round, chunk and class, widest first. One
+// upload; class k on stream k (s0, then the side streams) with the event
+// fork/join once per round; one download, one synchronise. The out pointers
+// name pinned buffers valid until the next lag-path pass: fp32
+// [6][n_ticks][n_slots], u8 [n_ticks][n_slots] violated, i32
+// [n_ticks][n_slots] steps; only the tasks' ticks are written. Like
+// wva_ctx_lag it touches none of the buckets, the fused tick's table, done[],
+// the memo, the captured graph. -2: inconsistent tables; -41: the arena could
+// not be allocated (the context is intact).
+extern "C" int wva_ctx_lag_path(void *ctx, const void *tasks, const void *recs,
+                                const double *desc, const int *launches, int n_tasks,
+                                int n_recs, int n_launches, int n_ticks, int n_slots,
+                                int max_steps, double dt, const void **out_f,
+                                const void **out_violated, const void **out_steps) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr) return -31;
+  WvaLagPathIn in = {(const WvaLagPathTask *)tasks, (const WvaLagPathRec *)recs, desc,
+                     (const WvaLagPathLaunch *)launches, n_tasks, n_recs, n_launches, n_ticks,
+                     n_slots, max_steps, dt};
+  size_t slab = 0, off[WVA_LP_N];
+  int rc = wva_lag_path_plan(in, WVA_LAG_WIDE_SLAB_CAP, &slab);
+  if (rc != 0) return rc;
+  const size_t bytes = wva_lag_path_layout(in, slab, false, off);
+  const size_t pin_bytes = off[WVA_LP_CARRY];
+  if (bytes > c->lagp_dev_cap || pin_bytes > c->lagp_pin_cap) {
+    const size_t dev_want = bytes > c->lagp_dev_cap ? bytes : c->lagp_dev_cap;
+    const size_t pin_want = pin_bytes > c->lagp_pin_cap ? pin_bytes : c->lagp_pin_cap;
+    wva_arena_free(c->lagp_dev, c->lagp_pin);
+    c->lagp_dev_cap = c->lagp_pin_cap = 0;
+    if (!wva_arena_alloc(c, dev_want, pin_want, false, &c->lagp_dev, &c->lagp_pin)) return -41;
+    c->lagp_dev_cap = dev_want;
+    c->lagp_pin_cap = pin_want;
+  }
+  WvaDeviceGuard on_dev(c->dev_dyn);
+  char *d = (char *)c->lagp_dev, *h = (char *)c->lagp_pin;
+  wva_lag_path_stage(in, off, h);
+  if (hipMemcpyAsync(d, h, off[WVA_LP_F], hipMemcpyHostToDevice, c->s0) != hipSuccess) return -32;
+  hipStream_t stream[WVA_LAG_CLASSES] = {c->s0, c->side[0], c->side[1], c->side[2]};
+  rc = wva_lag_path_launch(in, off, d, false, stream, c->e_up, c->e_b);
+  if (rc != 0) return rc;
+  if (hipMemcpyAsync(h + off[WVA_LP_F], d + off[WVA_LP_F], off[WVA_LP_RAW] - off[WVA_LP_F],
+                     hipMemcpyDeviceToHost, c->s0) != hipSuccess)
+    return -33;
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -34;
+  if (out_f) *out_f = h + off[WVA_LP_F];
+  if (out_violated) *out_violated = h + off[WVA_LP_VIOL];
+  if (out_steps) *out_steps = h + off[WVA_LP_STEPS];
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // Forecast ensembles: n_paths rollouts of n_steps ticks from one start
 // allocation, delivered in passes of whole paths, then the order statistics
@@ -2095,6 +2155,7 @@ extern "C" void wva_ctx_destroy(void *ctx) {
   wva_arena_free(c->roll_dev, c->roll_pin);
   wva_arena_free(c->lag_dev, c->lag_pin);
   wva_arena_free(c->lagw_dev, c->lagw_pin);
+  wva_arena_free(c->lagp_dev, c->lagp_pin);
   wva_ens_release(c);
   if (c->lim_static != nullptr) (void)hipFree(c->lim_static);
   free(c->topo);

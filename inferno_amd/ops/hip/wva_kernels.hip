@@ -3917,6 +3917,10 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_greedy(
 // of the kernels above with its own task table and launcher.
 #include "wva_lag.inc"
 
+// Lag paths (wva_lag_path_t: the transient response along a forecast, the state
+// carried from tick to tick and from launch to launch), a sibling of wva_lag_t.
+#include "wva_lag_path.inc"
+
 // The native reconcile context (WvaCtx: the per-tick pipeline and the planning
 // passes behind the wva_ctx_* C ABI) launches the kernels above; it is host
 // code of this translation unit.

@@ -193,6 +193,25 @@ assert LAG_TASK_DTYPE.itemsize == 64
 LAG_WIDE_DTYPE, LAG_SEG_DTYPE, LAG_TILE_DTYPE = _lag_wide_dtypes()
 assert (LAG_WIDE_DTYPE.itemsize, LAG_SEG_DTYPE.itemsize, LAG_TILE_DTYPE.itemsize) == (32, 32, 8)
 
+
+
+def _lag_path_dtypes():
+    import numpy as np
+
+    return (np.dtype([("in_tok", "<i4"), ("out_tok", "<i4"), ("N", "<i4"), ("slot", "<i4"),
+                      ("alpha", "<f4"), ("beta", "<f4"), ("gamma", "<f4"), ("delta", "<f4"),
+                      ("t_ttft", "<f4"), ("t_itl", "<f4"), ("pad", "<i4", (2,)),
+                      ("lam0", "<f8"), ("carry", "<i8")]),
+            np.dtype([("task", "<i4"), ("tick0", "<i4"), ("n", "<i4"), ("flags", "<i4")]))
+
+
+# a lag path's run and the ticks of it one launch covers: WvaLagPathTask, WvaLagPathRec
+LAG_PATH_TASK_DTYPE, LAG_PATH_REC_DTYPE = _lag_path_dtypes()
+assert (LAG_PATH_TASK_DTYPE.itemsize, LAG_PATH_REC_DTYPE.itemsize) == (64, 16)
+# WvaLagPathRec.flags: how the vector starts, and whether it is stored at the end
+LAG_PATH_STATIONARY, LAG_PATH_EMPTY, LAG_PATH_CARRY, LAG_PATH_STORE = 0, 1, 2, 4
+LAG_PATH_SLAB_CAP = 1 << 30  # bytes of carry of one round (WVA_LAG_WIDE_SLAB_CAP)
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -426,6 +445,20 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
     lib.wva_lag_wide_probe_launch.argtypes = (
         [ctypes.c_void_p] * 5 + [ctypes.c_int] * 8 + [ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.c_size_t,
+                                                      ctypes.POINTER(ctypes.c_size_t),
+                                                      ctypes.POINTER(ctypes.c_size_t)]
+    )
+    # lag paths (FastSweep.lag_path): the four tables of lag_path_schedule, their
+    # lengths and extents, max_steps, dt
+    lib.wva_ctx_lag_path.restype = ctypes.c_int
+    lib.wva_ctx_lag_path.argtypes = (
+        [ctypes.c_void_p] * 5 + [ctypes.c_int] * 6 + [ctypes.c_double]
+        + [ctypes.POINTER(ctypes.c_void_p)] * 3
+    )
+    lib.wva_lag_path_probe_launch.restype = ctypes.c_int
+    lib.wva_lag_path_probe_launch.argtypes = (
+        [ctypes.c_void_p] * 4 + [ctypes.c_int] * 6 + [ctypes.c_double, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_size_t,
                                                       ctypes.POINTER(ctypes.c_size_t),
                                                       ctypes.POINTER(ctypes.c_size_t)]
     )
@@ -943,6 +976,143 @@ def run_lag_wide_probe(arrays: dict, lam0, lam1, times, stride: int = LAG_WIDE_S
     raw = np.empty((n_cells, n_times, 5))
     raw[order] = at(3, n_cells * n_times * 40, np.float64).reshape(n_cells, n_times, 5)
     return raw, at(2, n_cells * 4, np.int32).copy()
+
+
+def lag_path_schedule(fields: dict, tick0, tick_steps, n_ticks: int, max_steps: int,
+                      slab_cap: int = LAG_PATH_SLAB_CAP):
+    """The host schedule of a lag-path pass. Task t is one run: ``fields`` holds
+    one array per LAG_PATH_TASK_DTYPE field (``pad`` and ``carry`` aside) and
+    ``start`` (LAG_PATH_STATIONARY or LAG_PATH_EMPTY); the run covers the ticks
+    ``tick0[t]`` .. ``tick0[t] + len(tick_steps[t])`` and ``tick_steps[t]`` are
+    their step counts (lag_window), none above ``max_steps``.
+
+    The tick axis is cut into chunks common to all tasks, greedily from the
+    left: a chunk ends before the tick that would push any task's step sum in
+    it above ``max_steps`` or the chunk beyond LAG_MAX_T ticks, so every block
+    stays inside the run time LAG_MAX_STEPS bounds. A task that crosses a chunk
+    boundary gets a carry slab (the states of its class, 8 bytes each); tasks
+    run in rounds whose slabs fit ``slab_cap`` together. Returns (task table,
+    records in launch order, launches int32 [n, 4]: rec0, count, class, round
+    by (round, chunk, class) with the records of a launch by descending cost,
+    chunk bounds int64 [n_chunks + 1])."""
+    import numpy as np
+
+    n = np.asarray(fields["N"], dtype=np.int64)
+    n_tasks = len(n)
+    if n_tasks == 0 or n.min() < 1 or n.max() > LAG_MAX_N:
+        raise HipKernelError(f"lag path tasks must have 1 <= N <= {LAG_MAX_N}")
+    tick0 = np.asarray(tick0, dtype=np.int64)
+    steps = np.zeros((n_tasks, n_ticks), dtype=np.int64)
+    for t, row in enumerate(tick_steps):
+        if len(row) < 1 or tick0[t] < 0 or tick0[t] + len(row) > n_ticks:
+            raise ValueError("a run lies outside the tick axis")
+        steps[t, tick0[t]:tick0[t] + len(row)] = row
+    if steps.max() > max_steps:
+        raise ValueError("a tick above max_steps cannot be scheduled")
+    bounds, run = [0], np.zeros(n_tasks, dtype=np.int64)
+    for j in range(n_ticks):
+        nxt = run + steps[:, j]
+        if j > bounds[-1] and (j - bounds[-1] >= LAG_MAX_T or nxt.max() > max_steps):
+            bounds.append(j)
+            nxt = steps[:, j]
+        run = nxt
+    bounds = np.array(bounds + [n_ticks], dtype=np.int64)
+    cls = np.zeros(n_tasks, dtype=np.int64)
+    for k, (nt, c) in enumerate(LAG_CLASSES):
+        cls[11 * n + 1 <= nt * c] = k  # later classes are narrower
+    table = np.zeros(n_tasks, dtype=LAG_PATH_TASK_DTYPE)
+    for name in LAG_PATH_TASK_DTYPE.names:
+        if name not in ("pad", "carry"):
+            table[name] = np.asarray(fields[name])
+    table["carry"] = -1
+    start = np.asarray(fields["start"], dtype=np.int64)
+    rows = []  # (round, chunk, class, -cost, task, tick0, n, flags)
+    rnd, used = 0, 0
+    for t in range(n_tasks):
+        t0, t1 = int(tick0[t]), int(tick0[t]) + len(tick_steps[t])
+        c0 = int(np.searchsorted(bounds, t0, side="right")) - 1
+        c1 = int(np.searchsorted(bounds, t1, side="left"))  # chunks c0 .. c1 - 1
+        if c1 - c0 > 1:
+            words = LAG_CLASSES[cls[t]][0] * LAG_CLASSES[cls[t]][1]
+            if used and (used + words) * 8 > slab_cap:
+                rnd, used = rnd + 1, 0
+            table["carry"][t] = used
+            used += words
+        for ch in range(c0, c1):
+            a, b = max(t0, int(bounds[ch])), min(t1, int(bounds[ch + 1]))
+            flags = (int(start[t]) if a == t0 else LAG_PATH_CARRY) | (LAG_PATH_STORE if b < t1
+                                                                        else 0)
+            rows.append((rnd, ch, int(cls[t]), -int(n[t]) * int(steps[t, a:b].sum()), t, a,
+                         b - a, flags))
+    rows.sort()
+    recs = np.zeros(len(rows), dtype=LAG_PATH_REC_DTYPE)
+    launches = []
+    for i, (r, ch, k, _, t, a, cnt, flags) in enumerate(rows):
+        recs[i] = (t, a, cnt, flags)
+        if i and rows[i - 1][:3] == (r, ch, k):
+            launches[-1][1] += 1
+        else:
+            launches.append([i, 1, k, r])
+    return table, recs, np.array(launches, dtype=np.int32).reshape(-1, 4), bounds
+
+
+def run_lag_path_probe(arrays: dict, start, lam, keep, tick_seconds: float,
+                       max_steps: int = 1 << 22, device: str = "cuda"):
+    """One-shot probe of the lag-path kernel (wva_lag_path_t), for tests and
+    tools, in the style of run_lag_probe. ``arrays`` as there; every cell is
+    one run over all S ticks of ``tick_seconds``: ``start[i]`` is "empty" or
+    ("stationary", lam0), ``lam`` and ``keep`` (float64 [n_cells, S]) its
+    per-tick rate (req/msec per replica) and scale-out factor. ``max_steps``
+    drives the chunking (lag_path_schedule), so a small one sends the state
+    through the carry. Returns (raw float64 [n_cells, S, 5] as run_lag_probe,
+    steps int32 [n_cells, S], the chunk bounds)."""
+    import numpy as np
+    import torch
+
+    from ..analyzer.lag import lag_window
+
+    if not torch.cuda.is_available():
+        raise HipKernelError("run_lag_path_probe requires a GPU")
+    lib = load_library()
+    n_cells = len(arrays["batch_n"])
+    lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(n_cells, -1)
+    keep = np.ascontiguousarray(keep, dtype=np.float64).reshape(n_cells, -1)
+    n_ticks = lam.shape[1]
+    dt = float(tick_seconds) * 1000.0
+    if n_ticks < 1 or keep.shape != lam.shape or not dt > 0 or not np.isfinite(dt):
+        raise ValueError("lam and keep must be [n_cells, S >= 1], tick_seconds finite and > 0")
+    if not ((lam >= 0).all() and (keep >= 0).all() and (keep <= 1).all()):
+        raise ValueError("lam must be non-negative and keep in [0, 1]")
+    fields = {k: np.asarray(arrays[k]) for k in ("in_tok", "out_tok", "alpha", "beta", "gamma",
+                                                  "delta")}
+    fields["N"] = np.asarray(arrays["batch_n"])
+    fields["slot"] = np.arange(n_cells, dtype=np.int32)
+    fields["t_ttft"] = fields["t_itl"] = np.zeros(n_cells, dtype=np.float32)
+    fields["lam0"] = np.array([0.0 if isinstance(s, str) else float(s[1]) for s in start])
+    fields["start"] = np.array([LAG_PATH_EMPTY if isinstance(s, str) else LAG_PATH_STATIONARY
+                                for s in start])
+    smax = np.array([_lag_smax(fields, i) for i in range(n_cells)])
+    want = lag_window((lam + smax[:, None]) * dt)[1].astype(np.int64)
+    table, recs, launches, bounds = lag_path_schedule(
+        fields, np.zeros(n_cells, dtype=np.int64), list(want), n_ticks, int(max_steps))
+    desc = np.ascontiguousarray(np.stack([lam, keep], axis=2))
+    need = ctypes.c_size_t()
+    offs = (ctypes.c_size_t * 4)()
+    args = (table.ctypes.data, recs.ctypes.data, desc.ctypes.data, launches.ctypes.data,
+            len(table), len(recs), len(launches), n_ticks, n_cells, int(max_steps), dt,
+            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    rc = lib.wva_lag_path_probe_launch(*args, None, 0, ctypes.byref(need), offs)
+    if rc != 0:
+        raise HipKernelError(f"wva_lag_path_probe_launch failed: {rc}")
+    dev = torch.empty(need.value, dtype=torch.uint8, device=device)
+    rc = lib.wva_lag_path_probe_launch(*args, _ptr(dev), need.value, ctypes.byref(need), offs)
+    if rc != 0:
+        raise HipKernelError(f"wva_lag_path_probe_launch failed: {rc}")
+    cells = n_cells * n_ticks
+    host = dev[offs[0]:offs[3] + cells * 40].cpu().numpy()
+    at = lambda i, n, t: host[offs[i] - offs[0]:offs[i] - offs[0] + n].view(t)  # noqa: E731
+    raw = at(3, cells * 40, np.float64).reshape(n_cells, n_ticks, 5).copy()
+    return raw, at(2, cells * 4, np.int32).reshape(n_ticks, n_cells).T.copy(), bounds
 
 
 def _lag_smax(fields: dict, i: int) -> float:
