@@ -1,6 +1,7 @@
 """Measure the lag path on the flagship 512-model fleet.
 
-  python examples/bench_lag_path.py [--reps 5] [--ticks 32] [--out profiles/bench_lag_path.json]
+  python examples/bench_lag_path.py [--reps 5] [--ticks 32] [--max-n N]
+                                    [--out profiles/bench_lag_path.json]
 
 The forecast is --ticks ticks of --tick-seconds (a ramp 1x..3x and back), the
 allocation the rollout's own winners, one tick late (delay=1). Before anything
@@ -8,7 +9,11 @@ is timed the GPU result is compared with the CPU golden on a sample of servers.
 Then it records ms per FastSweep.lag_path call (median of --reps calls, each
 returning synchronised), the tasks (runs), chunks and launches of the pass, the
 total steps, the state updates per second, and the heaviest record of any chunk
-(N x steps) run alone through the probe. Needs a GPU; prints one JSON line.
+(N x steps) run alone through the probe. With --max-n above LAG_MAX_N the wide
+runs take part (the tiled path kernels): the golden sample gains the cheapest
+wide server, and the wide pass' tasks, tiles, segments, launches and state
+updates per second (over the time the call takes beyond a default call, timed
+in the same run) are recorded. Needs a GPU; prints one JSON line.
 """
 from __future__ import annotations
 
@@ -32,6 +37,7 @@ def main() -> int:
     p.add_argument("--ticks", type=int, default=32)
     p.add_argument("--tick-seconds", type=float, default=60.0)
     p.add_argument("--sample", type=int, default=8)
+    p.add_argument("--max-n", type=int, default=None)
     p.add_argument("--out", default="")
     args = p.parse_args()
 
@@ -42,7 +48,8 @@ def main() -> int:
         return 2
     from inferno_amd.core.system import System
     from inferno_amd.engine import LAG_MAX_STEPS, LAG_OK, LAG_STATUS_NAMES, FastSweep
-    from inferno_amd.ops.sweep import run_lag_path_probe
+    from inferno_amd.ops.sweep import (LAG_MAX_N, LAG_WIDE_HALO, LAG_WIDE_STRIDE,
+                                       run_lag_path_probe)
     from inferno_amd.utils.synthetic import make_fleet_spec
 
     spec = make_fleet_spec(args.models, seed=args.seed)
@@ -59,6 +66,9 @@ def main() -> int:
     roll = fs.rollout(scales=scales)
     kw = dict(scales=scales, allocation=(roll.winners.acc_idx, roll.winners.num_replicas),
               delay=1, tick_seconds=args.tick_seconds)
+    base_kw = dict(kw)
+    if args.max_n is not None:
+        kw["max_n"] = args.max_n
     res = fs.lag_path(**kw)  # warm: context, buffers
     shape = fs.lag_path_pass
     ok = res.status == LAG_OK
@@ -67,9 +77,15 @@ def main() -> int:
     recs, table = shape["records"], shape["table"]
     n_of = np.zeros(len(fs.server_names), dtype=np.int64)
     n_of[table["slot"]] = table["N"]
+    wide_table = shape.get("wide_table")
+    if wide_table is not None:
+        n_of[wide_table["slot"]] = wide_table["N"]
     work = (res.steps * ok).sum(axis=0) * n_of
     servers = [int(i) for i in np.argsort(np.where(work > 0, work, np.inf))[: args.sample]
                if work[i] > 0]
+    if wide_table is not None:  # and the cheapest wide server: the golden walks every state
+        w_work = np.where(n_of > LAG_MAX_N, work, 0)
+        servers.append(int(np.argmin(np.where(w_work > 0, w_work, np.inf))))
     sub = np.full_like(roll.winners.acc_idx, -1)
     sub[:, servers] = roll.winners.acc_idx[:, servers]
     start = fs._hold_allocation(None, 1)
@@ -86,12 +102,30 @@ def main() -> int:
     assert np.array_equal(gold.steps[:, servers], res.steps[:, servers])
     assert worst <= 2e-6, worst  # two fp32 roundings of quantities that agree to 1e-12
 
-    # ---- ms per call
+    # ---- ms per call (and of the wide pass' native call alone, inside it)
+    native_ms = []
+    if wide_table is not None:
+        inner = fs._gpu.lag_path_wide
+
+        def timed(*a):
+            t0 = time.perf_counter()
+            r = inner(*a)
+            native_ms.append((time.perf_counter() - t0) * 1e3)
+            return r
+
+        fs._gpu.lag_path_wide = timed
     call_ms = []
     for _ in range(args.reps):
         t0 = time.perf_counter()
         fs.lag_path(**kw)
         call_ms.append((time.perf_counter() - t0) * 1e3)
+    base_ms = []
+    if wide_table is not None:
+        fs.lag_path(**base_kw)
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            fs.lag_path(**base_kw)
+            base_ms.append((time.perf_counter() - t0) * 1e3)
     total_steps = int(res.steps[ok].sum())
     updates = int(((res.steps * ok).sum(axis=0) * (11 * n_of + 1)).sum())
 
@@ -135,6 +169,21 @@ def main() -> int:
                             / int(probe_steps.sum())},
         "gpu_vs_golden_max_rel": worst, "golden_sample_servers": len(servers),
     }
+    if wide_table is not None:
+        wide_ms = statistics.median(call_ms) - statistics.median(base_ms)
+        out["max_n"] = args.max_n
+        chain = int((res.steps * ok)[:, n_of > LAG_MAX_N].sum(axis=0).max())
+        out["wide"] = {"tasks": shape["wide_tasks"], "tiles": shape["wide_tiles"],
+                       "segments": shape["wide_segments"], "launches": shape["wide_launches"],
+                       "step_launches": shape["wide_step_launches"],
+                       "longest_server_steps": chain,
+                       "native_pass_ms_median": statistics.median(native_ms),
+                       "us_per_step_of_longest_server": statistics.median(native_ms) * 1e3 / chain,
+                       "halo": LAG_WIDE_HALO, "stride": LAG_WIDE_STRIDE,
+                       "state_updates": shape["wide_updates"],
+                       "default_call_ms_median": statistics.median(base_ms),
+                       "wide_part_ms": wide_ms,
+                       "state_updates_per_s": shape["wide_updates"] / (wide_ms * 1e-3)}
     line = json.dumps(out)
     print(line)
     if args.out:

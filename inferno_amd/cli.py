@@ -577,8 +577,9 @@ def _cmd_plan_lag_path(args) -> int:
     fs = FastSweep(system, backend=backend)
     try:
         roll = fs.rollout(scales=scales)
+        kw = {} if args.lag_max_n is None else {"max_n": args.lag_max_n}
         res = fs.lag_path(scales=scales, delay=args.lag_delay, tick_seconds=args.tick_seconds,
-                          allocation=(roll.winners.acc_idx, roll.winners.num_replicas))
+                          allocation=(roll.winners.acc_idx, roll.winners.num_replicas), **kw)
     except ValueError as e:
         print(f"plan: {e}", file=sys.stderr)
         return 2
@@ -742,7 +743,7 @@ def main() -> None:
                          "allocation at these checkpoint times after the load steps from the "
                          "base load to each scale, e.g. 15,30,60")
     pp.add_argument("--lag-max-n", type=int, default=None, metavar="N",
-                    help="with --lag-times: analyse cells up to this batch size (above 1117 "
+                    help="with --lag-times or --lag-path: analyse cells up to this batch size (above 1117 "
                          "through the tiled kernels, at most 32768); wider cells are TOO_WIDE")
     pp.add_argument("--hold", action="store_true",
                     help="hold analysis: the current allocation is not resized; per load scale "

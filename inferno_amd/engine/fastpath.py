@@ -1393,7 +1393,7 @@ class FastSweep:
 
     def lag_path(self, scales=None, arrival=None, allocation=None, delay: int = 1,
                  start_allocation=None, from_arrival=None, tick_seconds: float = 60.0,
-                 max_steps: int = LAG_MAX_STEPS) -> LagPathResult:
+                 max_steps: int = LAG_MAX_STEPS, max_n: int = LAG_MAX_N) -> LagPathResult:
         """The transient response ALONG a forecast: what users see, tick by
         tick, while an allocation that is ``delay`` ticks late follows the load.
         lag() takes one load step from a stationary start; here the state of
@@ -1412,7 +1412,7 @@ class FastSweep:
         forms it, from arrival[j] and the replicas in force. The tick axis
         splits into runs: maximal sequences of consecutive ticks that name the
         same accelerator, on which the server has a cell with a valid model and
-        N <= LAG_MAX_N, with R > 0. A tick outside a run has lag()'s status by
+        N <= ``max_n``, with R > 0. A tick outside a run has lag()'s status by
         lag()'s precedence (LAG_NOT_HELD, LAG_IDLE, LAG_INVALID,
         LAG_NO_REPLICAS, LAG_TOO_WIDE) and lag()'s floats for it; LAG_IDLE only
         without output tokens or when the server has no load in
@@ -1431,15 +1431,22 @@ class FastSweep:
         step count exceeds ``max_steps`` truncates its run: it and the rest of
         the run are LAG_BUDGET, nothing is clipped.
 
-        Limits: cells with N > LAG_MAX_N stay LAG_TOO_WIDE (the tiled kernels
-        carry no state between calls), and there are no time-averaged
-        functionals inside a tick. Chain analyzer only. On the GPU the ticks
+        ``max_n`` (1..LAG_WIDE_MAX_N, default LAG_MAX_N): runs on cells with
+        LAG_MAX_N < N <= ``max_n`` are computed too, on the GPU by the tiled
+        path kernels (wva_lag_path_tile_t: the state in HBM between segments of
+        at most LAG_WIDE_HALO steps, so they need no chunks), on the CPU by the
+        same golden; the narrow runs go through the one-block pass as before.
+
+        Limits: cells with N > ``max_n`` (at most LAG_WIDE_MAX_N) stay
+        LAG_TOO_WIDE, the narrow and the wide pass run one after the other,
+        and there are no time-averaged functionals inside a tick. Chain
+        analyzer only. On the GPU the narrow runs' ticks
         run in chunks of at most 16 whose step sums stay within ``max_steps``
         per block, the state carried between the launches on the device. The
         pass stages no tick and changes nothing any other call returns."""
         from ..analyzer.lag import lag_latency, lag_path_transient, lag_window
         from ..ops.sweep import (LAG_PATH_EMPTY, LAG_PATH_STATIONARY, HipKernelError,
-                                 lag_path_schedule)
+                                 lag_path_schedule, lag_path_wide_schedule)
 
         if getattr(self.system, "analyzer_mode", "mm1k") == "mg1":
             raise ValueError("lag_path() needs the chain analyzer: the M/G/1 evaluator has no "
@@ -1476,6 +1483,9 @@ class FastSweep:
         max_steps = int(max_steps)
         if not 0 <= max_steps <= np.iinfo(np.int32).max:
             raise ValueError("max_steps must be a non-negative int32")
+        max_n = int(max_n)
+        if not 1 <= max_n <= LAG_WIDE_MAX_N:
+            raise ValueError(f"max_n must be in 1..{LAG_WIDE_MAX_N}")
         # the allocation in force: row j - delay, the start allocation before
         lead = min(delay, n_t)
         acc = np.concatenate([np.broadcast_to(acc0, (lead, n_srv)), acc[:n_t - lead]])
@@ -1519,7 +1529,7 @@ class FastSweep:
                 for f in _LAG_FLOATS:
                     rec[f][j, i] = np.nan
                 rates, n_max, _, _ = self._lag_model(models, k, int(in_tok[i]), n_out)
-                if rates is None or rep[j, i] == 0 or n_max > LAG_MAX_N:
+                if rates is None or rep[j, i] == 0 or n_max > max_n:
                     status[j, i] = (LAG_INVALID if rates is None else
                                     LAG_NO_REPLICAS if rep[j, i] == 0 else LAG_TOO_WIDE)
                     j += 1
@@ -1552,33 +1562,59 @@ class FastSweep:
             if g is None:
                 g = self._gpu = NativeCtx(n_srv, self._stat, self.cell_server,
                                           self.cell_acc_idx, self.seg_start, self.device)
-            ii, kk = (np.array([r[j] for r in runs], dtype=np.int64) for j in range(2))
-            fields = {"in_tok": in_tok[ii], "out_tok": out_tok[ii], "slot": ii.astype(np.int32),
-                      "N": np.array([models[k][1] for k in kk], dtype=np.int32),
-                      "lam0": np.array([r[4] for r in runs]),
-                      "start": np.array([r[3] for r in runs])}
-            for f in ("alpha", "beta", "gamma", "delta", "t_ttft", "t_itl"):
-                fields[f] = st[f][kk]
-            desc = np.zeros((n_srv, n_t, 2))
-            desc[:, :, 1] = 1.0
-            for i, _, j, _, _, lam, keep, _ in runs:
-                desc[i, j:j + len(lam), 0], desc[i, j:j + len(lam), 1] = lam, keep
-            table, recs, launches, bounds = lag_path_schedule(
-                fields, [r[2] for r in runs], [r[7] for r in runs], n_t, max_steps)
-            # for tools (examples/bench_lag_path.py): the shape of the pass that ran
-            self.lag_path_pass = {"tasks": len(table), "chunks": len(bounds) - 1,
-                                  "launches": len(launches), "records": recs, "table": table}
-            of, ov, osteps = g.lag_path(table, recs, desc, launches, n_t, n_srv, max_steps, dt)
-            for i, _, j, _, _, lam, _, want in runs:
-                sl = slice(j, j + len(lam))
-                for r, f in enumerate(_LAG_FLOATS):
-                    rec[f][sl, i] = of[r][sl, i]
-                violated[sl, i] = ov[sl, i] != 0
-                # the schedule and the OK verdicts come from the host's count
-                if not np.array_equal(osteps[sl, i], want):
-                    raise HipKernelError("wva_ctx_lag_path: the device's step counts differ from "
-                                         "the host's (lag_window and wva_lag_window are out of "
-                                         "step)")
+            # for tools (examples/bench_lag_path.py): the shape of the passes that ran
+            self.lag_path_pass = {"tasks": 0, "chunks": 0, "launches": 0, "wide_tasks": 0,
+                                  "wide_tiles": 0, "wide_segments": 0, "wide_launches": 0,
+                                  "wide_updates": 0}
+            is_wide = np.array([models[r[1]][1] > LAG_MAX_N for r in runs])
+            for part in (~is_wide, is_wide):  # the one-block classes, then the tiled path
+                sel = [r for r, p in zip(runs, part) if p]
+                if not sel:
+                    continue
+                ii, kk = (np.array([r[j] for r in sel], dtype=np.int64) for j in range(2))
+                fields = {"in_tok": in_tok[ii], "out_tok": out_tok[ii],
+                          "slot": ii.astype(np.int32),
+                          "N": np.array([models[k][1] for k in kk], dtype=np.int32),
+                          "lam0": np.array([r[4] for r in sel]),
+                          "start": np.array([r[3] for r in sel])}
+                for f in ("alpha", "beta", "gamma", "delta", "t_ttft", "t_itl"):
+                    fields[f] = st[f][kk]
+                if part is is_wide:
+                    table, wide, segs, tiles, desc, _ = lag_path_wide_schedule(
+                        fields, [r[2] for r in sel], [r[5] for r in sel], [r[6] for r in sel],
+                        [float(models[k][0].max()) for k in kk], dt, n_t, LAG_WIDE_STRIDE,
+                        LAG_WIDE_HALO, n_srv)
+                    of, ov, osteps, made = g.lag_path_wide(
+                        table, wide, segs, tiles, desc, n_t, n_srv, max_steps, LAG_WIDE_STRIDE,
+                        LAG_WIDE_HALO, dt)
+                    self.lag_path_pass.update(
+                        wide_tasks=len(table), wide_tiles=len(tiles), wide_segments=len(segs),
+                        wide_table=table,
+                        wide_launches=int(made.sum()), wide_step_launches=int(made[1]),
+                        # every step moves the K + 1 states of its task
+                        wide_updates=int(((11 * fields["N"].astype(np.int64) + 1)
+                                          * np.array([r[7].sum() for r in sel])).sum()))
+                else:
+                    desc = np.zeros((n_srv, n_t, 2))
+                    desc[:, :, 1] = 1.0
+                    for i, _, j, _, _, lam, keep, _ in sel:
+                        desc[i, j:j + len(lam), 0], desc[i, j:j + len(lam), 1] = lam, keep
+                    table, recs, launches, bounds = lag_path_schedule(
+                        fields, [r[2] for r in sel], [r[7] for r in sel], n_t, max_steps)
+                    self.lag_path_pass.update(tasks=len(table), chunks=len(bounds) - 1,
+                                              launches=len(launches), records=recs, table=table)
+                    of, ov, osteps = g.lag_path(table, recs, desc, launches, n_t, n_srv,
+                                                max_steps, dt)
+                for i, _, j, _, _, lam, _, want in sel:
+                    sl = slice(j, j + len(lam))
+                    for r, f in enumerate(_LAG_FLOATS):
+                        rec[f][sl, i] = of[r][sl, i]
+                    violated[sl, i] = ov[sl, i] != 0
+                    # the schedule and the OK verdicts come from the host's count
+                    if not np.array_equal(osteps[sl, i], want):
+                        raise HipKernelError("wva_ctx_lag_path: the device's step counts differ "
+                                             "from the host's (lag_window and wva_lag_window are "
+                                             "out of step)")
         else:
             for i, k, j, start, lam0, lam, keep, _ in runs:
                 rates, n_max, parms, req = models[k]

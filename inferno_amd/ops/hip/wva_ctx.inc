@@ -159,8 +159,9 @@ struct WvaCtx {
   void *lag_dev;
   void *lag_pin;
   size_t lag_cap;  // bytes each of them holds (0 = not allocated)
-  // wide lag (wva_ctx_lag_wide): its own pair, because the device side also
-  // holds the slabs of a round and the pinned side only tables and records
+  // wide lag (wva_ctx_lag_wide) and wide lag paths (wva_ctx_lag_path_wide),
+  // which never overlap: their own pair, because the device side also holds
+  // the slabs of a round and the pinned side only tables and records
   void *lagw_dev = nullptr;
   void *lagw_pin = nullptr;
   size_t lagw_dev_cap = 0, lagw_pin_cap = 0;  // bytes each holds
@@ -1958,6 +1959,55 @@ extern "C" int wva_ctx_lag_path(void *ctx, const void *tasks, const void *recs,
   if (out_f) *out_f = h + off[WVA_LP_F];
   if (out_violated) *out_violated = h + off[WVA_LP_VIOL];
   if (out_steps) *out_steps = h + off[WVA_LP_STEPS];
+  return 0;
+}
+
+// One wide lag-path pass (wva_lag_path_wide.inc): the runs on cells with
+// WVA_LAG_MAX_N < N <= WVA_LAG_WIDE_MAX_N, tiled over blocks and segments. The
+// tables are the host schedule of ops/sweep.py lag_path_wide_schedule (tasks by
+// descending segment count) and the interval descriptors; `wide` is written to
+// (the slab offsets). One upload, per round of tasks whose slabs fit
+// WVA_LAG_WIDE_SLAB_CAP one init launch and per segment index one step launch
+// and, where a tick closed, one fin launch, all stream-ordered on s0; one
+// download, one synchronise. The pass shares the wide lag pass' arena pair
+// (wva_lag_wide_reserve: both passes end synchronised and their results are
+// copied out before the next one runs), so the out pointers, as for
+// wva_ctx_lag_path, are valid until the next wide pass of either kind.
+// launches[3] (or null): init, step and fin launches made. Like the other lag
+// passes it touches none of the buckets, the fused tick's table, done[], the
+// memo, the captured graph. -2: inconsistent tables; -41: the arena could not
+// be allocated (the context is intact).
+extern "C" int wva_ctx_lag_path_wide(void *ctx, const void *tasks, void *wide, const void *segs,
+                                     const void *tiles, const double *desc, int n_tasks,
+                                     int n_segs, int n_tiles, int n_ticks, int n_slots,
+                                     int max_steps, int stride, int halo, double dt,
+                                     const void **out_f, const void **out_violated,
+                                     const void **out_steps, int *launches) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr) return -31;
+  WvaLagPathWideIn in = {(const WvaLagPathTask *)tasks, (WvaLagPathWideTask *)wide,
+                         (const WvaLagSeg *)segs, (const WvaLagTile *)tiles, desc, n_tasks,
+                         n_segs, n_tiles, n_ticks, n_slots, stride, halo, max_steps, dt};
+  size_t slab = 0, off[WVA_LPW_N];
+  int rc = wva_lag_path_wide_plan(in, WVA_LAG_WIDE_SLAB_CAP, &slab);
+  if (rc != 0) return rc;
+  const size_t bytes = wva_lag_path_wide_layout(in, slab, false, off);
+  rc = wva_lag_wide_reserve(c, bytes, off[WVA_LPW_PART]);
+  if (rc != 0) return rc;
+  WvaDeviceGuard on_dev(c->dev_dyn);
+  char *d = (char *)c->lagw_dev, *h = (char *)c->lagw_pin;
+  wva_lag_path_wide_stage(in, off, h);
+  if (hipMemcpyAsync(d, h, off[WVA_LPW_F], hipMemcpyHostToDevice, c->s0) != hipSuccess)
+    return -32;
+  rc = wva_lag_path_wide_launch(in, off, d, false, c->s0, launches);
+  if (rc != 0) return rc;
+  if (hipMemcpyAsync(h + off[WVA_LPW_F], d + off[WVA_LPW_F], off[WVA_LPW_RAW] - off[WVA_LPW_F],
+                     hipMemcpyDeviceToHost, c->s0) != hipSuccess)
+    return -33;
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -34;
+  if (out_f) *out_f = h + off[WVA_LPW_F];
+  if (out_violated) *out_violated = h + off[WVA_LPW_VIOL];
+  if (out_steps) *out_steps = h + off[WVA_LPW_STEPS];
   return 0;
 }
 

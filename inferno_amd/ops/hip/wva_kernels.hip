@@ -3921,6 +3921,11 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_greedy(
 // carried from tick to tick and from launch to launch), a sibling of wva_lag_t.
 #include "wva_lag_path.inc"
 
+// Lag paths for wide cells (wva_lag_path_tile_t: the tiled wide-lag scheme with
+// per-tick rates and the state kept between ticks), siblings of the wide-lag
+// kernels of wva_lag.inc.
+#include "wva_lag_path_wide.inc"
+
 // The native reconcile context (WvaCtx: the per-tick pipeline and the planning
 // passes behind the wva_ctx_* C ABI) launches the kernels above; it is host
 // code of this translation unit.

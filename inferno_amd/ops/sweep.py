@@ -212,6 +212,19 @@ assert (LAG_PATH_TASK_DTYPE.itemsize, LAG_PATH_REC_DTYPE.itemsize) == (64, 16)
 LAG_PATH_STATIONARY, LAG_PATH_EMPTY, LAG_PATH_CARRY, LAG_PATH_STORE = 0, 1, 2, 4
 LAG_PATH_SLAB_CAP = 1 << 30  # bytes of carry of one round (WVA_LAG_WIDE_SLAB_CAP)
 
+
+def _lag_path_wide_dtype():
+    import numpy as np
+
+    return np.dtype([("smax", "<f8"), ("slab", "<i8"), ("tile0", "<i4"), ("n_tiles", "<i4"),
+                     ("seg0", "<i4"), ("n_seg", "<i4"), ("tick0", "<i4"), ("n_run", "<i4"),
+                     ("start", "<i4"), ("pad", "<i4")])
+
+
+# a wide run beside its LAG_PATH_TASK_DTYPE record: WvaLagPathWideTask, 48 bytes
+LAG_PATH_WIDE_DTYPE = _lag_path_wide_dtype()
+assert LAG_PATH_WIDE_DTYPE.itemsize == 48
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -458,6 +471,21 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
     lib.wva_lag_path_probe_launch.restype = ctypes.c_int
     lib.wva_lag_path_probe_launch.argtypes = (
         [ctypes.c_void_p] * 4 + [ctypes.c_int] * 6 + [ctypes.c_double, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_size_t,
+                                                      ctypes.POINTER(ctypes.c_size_t),
+                                                      ctypes.POINTER(ctypes.c_size_t)]
+    )
+    # wide lag paths (FastSweep.lag_path(max_n=...)): the four tables of
+    # lag_path_wide_schedule, the descriptors, their lengths and extents,
+    # max_steps, stride, halo, dt
+    lib.wva_ctx_lag_path_wide.restype = ctypes.c_int
+    lib.wva_ctx_lag_path_wide.argtypes = (
+        [ctypes.c_void_p] * 6 + [ctypes.c_int] * 8 + [ctypes.c_double]
+        + [ctypes.POINTER(ctypes.c_void_p)] * 3 + [ctypes.c_void_p]
+    )
+    lib.wva_lag_path_wide_probe_launch.restype = ctypes.c_int
+    lib.wva_lag_path_wide_probe_launch.argtypes = (
+        [ctypes.c_void_p] * 5 + [ctypes.c_int] * 8 + [ctypes.c_double, ctypes.c_void_p,
                                                       ctypes.c_void_p, ctypes.c_size_t,
                                                       ctypes.POINTER(ctypes.c_size_t),
                                                       ctypes.POINTER(ctypes.c_size_t)]
@@ -1113,6 +1141,129 @@ def run_lag_path_probe(arrays: dict, start, lam, keep, tick_seconds: float,
     at = lambda i, n, t: host[offs[i] - offs[0]:offs[i] - offs[0] + n].view(t)  # noqa: E731
     raw = at(3, cells * 40, np.float64).reshape(n_cells, n_ticks, 5).copy()
     return raw, at(2, cells * 4, np.int32).reshape(n_ticks, n_cells).T.copy(), bounds
+
+
+def lag_path_wide_schedule(fields: dict, tick0, lam, keep, smax, dt: float, n_ticks: int,
+                           stride: int = LAG_WIDE_STRIDE, halo: int = LAG_WIDE_HALO,
+                           n_slots: Optional[int] = None):
+    """The host schedule of a wide lag-path pass. Task t is one run on a cell
+    with LAG_MAX_N < N <= LAG_WIDE_MAX_N: ``fields`` as for lag_path_schedule,
+    the run covers the ticks ``tick0[t]`` .. ``tick0[t] + len(lam[t])`` at the
+    per-replica rates ``lam[t]`` (req/msec) and scale-out factors ``keep[t]``,
+    ``smax[t]`` is its largest service rate and ``dt`` the tick in msec. Every
+    tick's steps (lag_window of (lam + smax) dt) are cut by lag_segments into
+    runs of at most ``halo`` steps, so no segment crosses a tick; a segment's
+    ``j`` is its tick. Tasks are ordered by descending segment count, so that
+    launch l covers a prefix of the tasks and of the tile table. There are no
+    chunks: no block takes more than ``halo`` steps. Returns (task table, wide
+    table, segments, tiles, descriptors float64 [n_slots, n_ticks, 2], the
+    permutation applied)."""
+    import numpy as np
+
+    from ..analyzer.lag import lag_window
+
+    n = np.asarray(fields["N"], dtype=np.int64)
+    if len(n) == 0 or n.min() <= LAG_MAX_N or n.max() > LAG_WIDE_MAX_N:
+        raise HipKernelError(f"wide lag path tasks must have {LAG_MAX_N} < N <= {LAG_WIDE_MAX_N}")
+    c = LAG_WIDE_C
+    if stride % c or halo % c or halo < c or stride < c or stride + 2 * halo > LAG_WIDE_W:
+        raise ValueError(f"stride and halo must be multiples of {c} with "
+                         f"stride + 2 halo <= {LAG_WIDE_W}")
+    slot = np.asarray(fields["slot"], dtype=np.int64)
+    n_slots = int(slot.max()) + 1 if n_slots is None else int(n_slots)
+    tick0 = np.asarray(tick0, dtype=np.int64)
+    desc = np.zeros((n_slots, n_ticks, 2))
+    desc[:, :, 1] = 1.0
+    segs = []
+    for t in range(len(n)):
+        lam_t = np.asarray(lam[t], dtype=np.float64)
+        if len(lam_t) < 1 or tick0[t] < 0 or tick0[t] + len(lam_t) > n_ticks:
+            raise ValueError("a run lies outside the tick axis")
+        ticks = slice(int(tick0[t]), int(tick0[t]) + len(lam_t))
+        desc[slot[t], ticks, 0], desc[slot[t], ticks, 1] = lam_t, keep[t]
+        x = (lam_t + float(smax[t])) * dt
+        lo, hi = lag_window(x)
+        seg = lag_segments(lo, hi, x, halo)
+        seg["j"] += int(tick0[t])
+        segs.append(seg)
+    n_seg = np.array([len(s) for s in segs], dtype=np.int64)
+    order = np.argsort(-n_seg, kind="stable")
+    table = np.zeros(len(n), dtype=LAG_PATH_TASK_DTYPE)
+    for name in LAG_PATH_TASK_DTYPE.names:
+        if name not in ("pad", "carry"):
+            table[name] = np.asarray(fields[name])[order]
+    table["carry"] = -1
+    slots = -(-(11 * n[order] + 1) // c) * c
+    wide = np.zeros(len(n), dtype=LAG_PATH_WIDE_DTYPE)
+    wide["smax"] = np.asarray(smax, dtype=np.float64)[order]
+    wide["n_tiles"] = -(-slots // stride)
+    wide["tile0"] = np.concatenate(([0], np.cumsum(wide["n_tiles"])[:-1]))
+    wide["n_seg"] = n_seg[order]
+    wide["seg0"] = np.concatenate(([0], np.cumsum(wide["n_seg"])[:-1]))
+    wide["tick0"] = tick0[order]
+    wide["n_run"] = [len(lam[t]) for t in order]
+    wide["start"] = np.asarray(fields["start"])[order]
+    tiles = np.zeros(int(wide["n_tiles"].sum()), dtype=LAG_TILE_DTYPE)
+    tiles["task"] = np.repeat(np.arange(len(n)), wide["n_tiles"])
+    tiles["b"] = np.arange(len(tiles)) - np.repeat(wide["tile0"], wide["n_tiles"])
+    return table, wide, np.concatenate([segs[i] for i in order]), tiles, desc, order
+
+
+def run_lag_path_wide_probe(arrays: dict, start, lam, keep, tick_seconds: float,
+                            stride: int = LAG_WIDE_STRIDE, halo: int = LAG_WIDE_HALO,
+                            max_steps: int = 1 << 22, device: str = "cuda"):
+    """One-shot probe of the tiled lag-path kernels (wva_lag_path_wide_init,
+    wva_lag_path_tile_t, wva_lag_path_wide_fin), the sibling of
+    run_lag_path_probe with the tile stride and halo as arguments. Arguments as
+    there; every cell (LAG_MAX_N < N <= LAG_WIDE_MAX_N) is one run over all S
+    ticks. Returns (raw float64 [n_cells, S, 5], steps int32 [n_cells, S], the
+    segments of every cell int64 [n_cells] in place of the chunk bounds)."""
+    import numpy as np
+    import torch
+
+    if not torch.cuda.is_available():
+        raise HipKernelError("run_lag_path_wide_probe requires a GPU")
+    lib = load_library()
+    n_cells = len(arrays["batch_n"])
+    lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(n_cells, -1)
+    keep = np.ascontiguousarray(keep, dtype=np.float64).reshape(n_cells, -1)
+    n_ticks = lam.shape[1]
+    dt = float(tick_seconds) * 1000.0
+    if n_ticks < 1 or keep.shape != lam.shape or not dt > 0 or not np.isfinite(dt):
+        raise ValueError("lam and keep must be [n_cells, S >= 1], tick_seconds finite and > 0")
+    if not ((lam >= 0).all() and (keep >= 0).all() and (keep <= 1).all()):
+        raise ValueError("lam must be non-negative and keep in [0, 1]")
+    fields = {k: np.asarray(arrays[k]) for k in ("in_tok", "out_tok", "alpha", "beta", "gamma",
+                                                  "delta")}
+    fields["N"] = np.asarray(arrays["batch_n"])
+    fields["slot"] = np.arange(n_cells, dtype=np.int32)
+    fields["t_ttft"] = fields["t_itl"] = np.zeros(n_cells, dtype=np.float32)
+    fields["lam0"] = np.array([0.0 if isinstance(s, str) else float(s[1]) for s in start])
+    fields["start"] = np.array([LAG_PATH_EMPTY if isinstance(s, str) else LAG_PATH_STATIONARY
+                                for s in start])
+    smax = np.array([_lag_smax(fields, i) for i in range(n_cells)])
+    table, wide, segs, tiles, desc, order = lag_path_wide_schedule(
+        fields, np.zeros(n_cells, dtype=np.int64), list(lam), list(keep), smax, dt, n_ticks,
+        stride, halo, n_cells)
+    need = ctypes.c_size_t()
+    offs = (ctypes.c_size_t * 4)()
+    args = (table.ctypes.data, wide.ctypes.data, segs.ctypes.data, tiles.ctypes.data,
+            desc.ctypes.data, len(table), len(segs), len(tiles), n_ticks, n_cells, int(max_steps),
+            int(stride), int(halo), dt, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    rc = lib.wva_lag_path_wide_probe_launch(*args, None, 0, ctypes.byref(need), offs)
+    if rc != 0:
+        raise HipKernelError(f"wva_lag_path_wide_probe_launch failed: {rc}")
+    dev = torch.empty(need.value, dtype=torch.uint8, device=device)
+    rc = lib.wva_lag_path_wide_probe_launch(*args, _ptr(dev), need.value, ctypes.byref(need), offs)
+    if rc != 0:
+        raise HipKernelError(f"wva_lag_path_wide_probe_launch failed: {rc}")
+    cells = n_cells * n_ticks
+    host = dev[offs[0]:offs[3] + cells * 40].cpu().numpy()
+    at = lambda i, n, t: host[offs[i] - offs[0]:offs[i] - offs[0] + n].view(t)  # noqa: E731
+    raw = at(3, cells * 40, np.float64).reshape(n_cells, n_ticks, 5).copy()
+    n_seg = np.empty(n_cells, dtype=np.int64)
+    n_seg[order] = wide["n_seg"]
+    return raw, at(2, cells * 4, np.int32).reshape(n_ticks, n_cells).T.copy(), n_seg
 
 
 def _lag_smax(fields: dict, i: int) -> float:
