@@ -1,6 +1,6 @@
 """Measure the lag path on the flagship 512-model fleet.
 
-  python examples/bench_lag_path.py [--reps 5] [--ticks 32] [--max-n N]
+  python examples/bench_lag_path.py [--reps 5] [--ticks 32] [--max-n N] [--averages]
                                     [--out profiles/bench_lag_path.json]
 
 The forecast is --ticks ticks of --tick-seconds (a ramp 1x..3x and back), the
@@ -13,7 +13,11 @@ total steps, the state updates per second, and the heaviest record of any chunk
 runs take part (the tiled path kernels): the golden sample gains the cheapest
 wide server, and the wide pass' tasks, tiles, segments, launches and state
 updates per second (over the time the call takes beyond a default call, timed
-in the same run) are recorded. Needs a GPU; prints one JSON line.
+in the same run) are recorded. With --averages the call with averages=True
+(wva_lag_path_avg_t) is checked against the golden's averages on the same
+sample and timed in alternation with the default call, and the heaviest record
+runs through both probes, also in alternation: the cost of the averages per
+call and per step. Needs a GPU; prints one JSON line.
 """
 from __future__ import annotations
 
@@ -38,6 +42,7 @@ def main() -> int:
     p.add_argument("--tick-seconds", type=float, default=60.0)
     p.add_argument("--sample", type=int, default=8)
     p.add_argument("--max-n", type=int, default=None)
+    p.add_argument("--averages", action="store_true")
     p.add_argument("--out", default="")
     args = p.parse_args()
 
@@ -48,7 +53,8 @@ def main() -> int:
         return 2
     from inferno_amd.core.system import System
     from inferno_amd.engine import LAG_MAX_STEPS, LAG_OK, LAG_STATUS_NAMES, FastSweep
-    from inferno_amd.ops.sweep import (LAG_MAX_N, LAG_WIDE_HALO, LAG_WIDE_STRIDE,
+    from inferno_amd.analyzer.lag import lag_window
+    from inferno_amd.ops.sweep import (LAG_MAX_N, LAG_WIDE_HALO, LAG_WIDE_STRIDE, _lag_smax,
                                        run_lag_path_probe)
     from inferno_amd.utils.synthetic import make_fleet_spec
 
@@ -101,6 +107,21 @@ def main() -> int:
         worst = max(worst, float((np.abs(a[m] - b[m]) / np.maximum(np.abs(a[m]), 1.0)).max()))
     assert np.array_equal(gold.steps[:, servers], res.steps[:, servers])
     assert worst <= 2e-6, worst  # two fp32 roundings of quantities that agree to 1e-12
+    worst_avg = 0.0
+    if args.averages:
+        res_avg = fs.lag_path(averages=True, **kw)  # warm, and against the golden's averages
+        gold = fleets["cpu"].lag_path(**{**kw, "allocation": (sub, roll.winners.num_replicas)},
+                                      start_allocation=(start_acc, start[1][0]), averages=True)
+        for f in ("ttft_avg", "itl_avg", "rho_avg", "blocked_avg"):
+            a, b = getattr(gold, f)[:, servers], getattr(res_avg, f)[:, servers]
+            assert np.array_equal(np.isnan(a), np.isnan(b)), f
+            m = ~np.isnan(a)
+            worst_avg = max(worst_avg,
+                            float((np.abs(a[m] - b[m]) / np.maximum(np.abs(a[m]), 1.0)).max()))
+        assert worst_avg <= 2e-6, worst_avg
+        for f in ("ttft", "itl", "wait", "blocked", "rho", "in_system"):  # the end state: the bits
+            assert np.array_equal(getattr(res, f).view(np.int32),
+                                  getattr(res_avg, f).view(np.int32)), f
 
     # ---- ms per call (and of the wide pass' native call alone, inside it)
     native_ms = []
@@ -114,11 +135,15 @@ def main() -> int:
             return r
 
         fs._gpu.lag_path_wide = timed
-    call_ms = []
+    call_ms, avg_ms = [], []
     for _ in range(args.reps):
         t0 = time.perf_counter()
         fs.lag_path(**kw)
         call_ms.append((time.perf_counter() - t0) * 1e3)
+        if args.averages:  # in alternation with the default call
+            t0 = time.perf_counter()
+            fs.lag_path(averages=True, **kw)
+            avg_ms.append((time.perf_counter() - t0) * 1e3)
     base_ms = []
     if wide_table is not None:
         fs.lag_path(**base_kw)
@@ -145,14 +170,20 @@ def main() -> int:
     rate = (res.arrival[sl, i].astype(np.float64) / 60.0 if tps == 0.0
             else np.full(int(r["n"]), tps / float(t["out_tok"])))
     lam = rate / res.held_replicas[sl, i] / 1000.0
-    probe = lambda: run_lag_path_probe(one, ["empty"], lam[None], np.ones((1, len(lam))),  # noqa: E731
-                                       args.tick_seconds, max_steps=LAG_MAX_STEPS)
+    probe = lambda **k: run_lag_path_probe(one, ["empty"], lam[None], np.ones((1, len(lam))),  # noqa: E731
+                                           args.tick_seconds, max_steps=LAG_MAX_STEPS, **k)
     probe()
-    task_ms = []
+    if args.averages:
+        probe(averages=True)
+    task_ms, task_avg_ms = [], []
     for _ in range(args.reps):
         t0 = time.perf_counter()
         _, probe_steps, _ = probe()
         task_ms.append((time.perf_counter() - t0) * 1e3)
+        if args.averages:
+            t0 = time.perf_counter()
+            probe(averages=True)
+            task_avg_ms.append((time.perf_counter() - t0) * 1e3)
     assert np.array_equal(probe_steps[0], res.steps[sl, i])
     out = {
         "fleet": f"{args.models} models, {len(fs.server_names)} servers", "ticks": args.ticks,
@@ -169,6 +200,21 @@ def main() -> int:
                             / int(probe_steps.sum())},
         "gpu_vs_golden_max_rel": worst, "golden_sample_servers": len(servers),
     }
+    if args.averages:
+        n_steps = int(probe_steps.sum())
+        lo, hi = lag_window((lam + _lag_smax({**one, "N": one["batch_n"]}, 0))
+                            * args.tick_seconds * 1000.0)
+        out["averages"] = {
+            "ms_per_call_median": statistics.median(avg_ms), "ms_per_call": avg_ms,
+            "over_default": statistics.median(avg_ms) / statistics.median(call_ms),
+            "gpu_vs_golden_max_rel": worst_avg,
+            "heaviest_record": {
+                "ms_median_incl_launch_and_copies": statistics.median(task_avg_ms),
+                "us_per_step": statistics.median(task_avg_ms) * 1e3 / n_steps,
+                "over_default": statistics.median(task_avg_ms) / statistics.median(task_ms),
+                # the steps that also update avg inside the window (the LDS
+                # read-modify-write of the widest class), of all steps
+                "window_share_of_steps": float((hi - lo).sum()) / n_steps}}
     if wide_table is not None:
         wide_ms = statistics.median(call_ms) - statistics.median(base_ms)
         out["max_n"] = args.max_n

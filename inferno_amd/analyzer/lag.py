@@ -120,7 +120,8 @@ def lag_transient(rates: np.ndarray, lam0: float, lam1: float, dt_ms) -> np.ndar
     return out
 
 
-def lag_path_transient(rates: np.ndarray, start, lam, keep, dt_ms: float) -> np.ndarray:
+def lag_path_transient(rates: np.ndarray, start, lam, keep, dt_ms: float,
+                       averages: bool = False):
     """Raw functionals [S, 5] (LAG_FUNCS) at the ends of S consecutive
     intervals of ``dt_ms`` msec each, interval j under arrival rate ``lam[j]``
     (req/msec). ``start`` is ("stationary", lam0) or "empty" (all mass in
@@ -128,7 +129,15 @@ def lag_path_transient(rates: np.ndarray, start, lam, keep, dt_ms: float) -> np.
     state, p <- keep[j] p + (1 - keep[j]) e_0 (a scale-out; 1: no change).
     Per interval: lag_transient's uniformization at Lam_j = lam[j] + max s,
     the same window and step count (lag_window), non-negative terms only.
-    ops/hip/wva_lag_path.inc is the device form of exactly this."""
+    ops/hip/wva_lag_path.inc is the device form of exactly this.
+
+    ``averages``: return (the above, the same functionals [S, 5] of the TIME
+    AVERAGE of the distribution over every interval) instead. With x = Lam_j
+    dt and v_k the vector after k steps (v_0 after the mixing),
+    pbar = (1 / x) sum_{k=0..j_hi} T_k v_k, T_k = P(Pois(x) > k): 1 below the
+    window (to within e^-60), T_k = max(T_{k-1} - w_k, 0) inside it, with the
+    weights w_k of the end state's sum. It is what a random arrival of the
+    interval meets; ops/hip/wva_lag_path_avg.inc is the device form."""
     s = np.asarray(rates, dtype=np.float64)
     n_max = len(s)
     k_max = 11 * n_max
@@ -150,6 +159,7 @@ def lag_path_transient(rates: np.ndarray, start, lam, keep, dt_ms: float) -> np.
     lam = np.asarray(lam, dtype=np.float64)
     keep = np.asarray(keep, dtype=np.float64)
     out = np.empty((len(lam), len(LAG_FUNCS)))
+    out_avg = np.empty_like(out)
     for j in range(len(lam)):
         lam_unif = float(lam[j]) + s_max
         dn = s_state / lam_unif
@@ -167,19 +177,34 @@ def lag_path_transient(rates: np.ndarray, start, lam, keep, dt_ms: float) -> np.
         v[0] += 1.0 - float(keep[j])
         x = lam_unif * float(dt_ms)
         lo, hi = (int(b) for b in lag_window(x))
+        avg = np.zeros_like(v)
         for _ in range(lo):
+            if averages:
+                avg += v  # T_k = 1 below the window
             v = step(v)
         w = math.exp(pois_log_pmf(float(lo), x))
         acc = w * v
+        tail = max(1.0 - w, 0.0)  # T_lo
+        if averages:
+            avg += tail * v
         for k in range(lo + 1, hi + 1):
             v = step(v)
             w *= x / k
             acc += w * v
+            if averages:
+                tail = max(tail - w, 0.0)
+                avg += tail * v
         v = acc
         blocked = float(v[k_max])
         wait = float(np.dot(v[n_max:k_max], departures)) / (1.0 - blocked) / float(s[-1])
         out[j] = (blocked, np.dot(v, in_srv), np.dot(v, in_sys), np.dot(v[1:], s_state[1:]), wait)
-    return out
+        if averages:
+            p = avg / x
+            blocked = float(p[k_max])
+            wait = float(np.dot(p[n_max:k_max], departures)) / (1.0 - blocked) / float(s[-1])
+            out_avg[j] = (blocked, np.dot(p, in_srv), np.dot(p, in_sys),
+                          np.dot(p[1:], s_state[1:]), wait)
+    return (out, out_avg) if averages else out
 
 
 def lag_latency(raw: np.ndarray, parms, req, n_max: int):

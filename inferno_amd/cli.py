@@ -578,6 +578,8 @@ def _cmd_plan_lag_path(args) -> int:
     try:
         roll = fs.rollout(scales=scales)
         kw = {} if args.lag_max_n is None else {"max_n": args.lag_max_n}
+        if args.lag_averages:
+            kw["averages"] = True
         res = fs.lag_path(scales=scales, delay=args.lag_delay, tick_seconds=args.tick_seconds,
                           allocation=(roll.winners.acc_idx, roll.winners.num_replicas), **kw)
     except ValueError as e:
@@ -602,7 +604,17 @@ def _cmd_plan_lag_path(args) -> int:
         "itl": [num(x) for x in res.itl[:, i]],
         "blocked": [num(x) for x in res.blocked[:, i]],
     } for i in range(len(fs.server_names))
-        if (res.status[:, i] != LAG_OK).any() or res.first_violation[i] >= 0]
+        if (res.status[:, i] != LAG_OK).any() or res.first_violation[i] >= 0
+        or (args.lag_averages and res.violated_avg[:, i].any())]
+    if args.lag_averages:  # over each tick, beside the state at its end
+        for t in ticks:
+            t["violatedOnAverage"] = int(res.violated_avg[t["tick"]].sum())
+        for b in servers:
+            i = fs.server_names.index(b["server"])
+            b["ticksViolatedOnAverage"] = int(res.violated_avg[:, i].sum())
+            b["ttftAverage"] = [num(x) for x in res.ttft_avg[:, i]]
+            b["itlAverage"] = [num(x) for x in res.itl_avg[:, i]]
+            b["blockedAverage"] = [num(x) for x in res.blocked_avg[:, i]]
     if args.json:
         print(json.dumps({"backend": backend, "servers": len(fs.server_names),
                           "tickSeconds": res.tick_seconds, "delay": args.lag_delay,
@@ -611,12 +623,17 @@ def _cmd_plan_lag_path(args) -> int:
     for t in ticks:
         print(f"tick {t['tick']:>3} (scale {t['scale']:g}): "
               + ", ".join(f"{n} {c}" for n, c in t["status"].items() if c)
-              + f"; servers over their SLO at its end: {t['violated']}")
+              + f"; servers over their SLO at its end: {t['violated']}"
+              + (f", on average over it: {t['violatedOnAverage']}" if args.lag_averages else ""))
     for b in servers:
         first = "-" if b["firstViolation"] is None else f"tick {b['firstViolation']}"
         ttft = " ".join("nan" if x is None else f"{x:.1f}" for x in b["ttft"])
         print(f"  {b['server']:<24} SLO broken from {first:<8} in {b['ticksViolated']} ticks; "
               f"ttft ms {ttft}")
+        if args.lag_averages:
+            ttft = " ".join("nan" if x is None else f"{x:.1f}" for x in b["ttftAverage"])
+            print(f"  {'':<24} on average over the tick in {b['ticksViolatedOnAverage']} ticks; "
+                  f"ttft ms {ttft}")
     print(f"({len(fs.server_names)} servers, backend {backend}; ticks of {res.tick_seconds:g} s, "
           f"the allocation {args.lag_delay} tick(s) behind the rollout's decisions)")
     return 0
@@ -738,6 +755,10 @@ def main() -> None:
                     help="with --lag-path: ticks between a decision and its effect (default 1)")
     pp.add_argument("--tick-seconds", type=float, default=60.0, metavar="SECONDS",
                     help="with --lag-path: length of a tick (default 60)")
+    pp.add_argument("--lag-averages", action="store_true",
+                    help="with --lag-path: also the latencies and the SLO verdict of the "
+                         "distribution averaged over each tick (what a random arrival of the "
+                         "tick meets), beside the state at its end")
     pp.add_argument("--lag-times", default=None, metavar="SECONDS",
                     help="with --hold: lag analysis, the transient latency of the held "
                          "allocation at these checkpoint times after the load steps from the "

@@ -259,6 +259,14 @@ class LagPathResult:
     tick_seconds: float
     arrival: np.ndarray  # float32 [S, n_servers]
     from_arrival: np.ndarray  # float32 [n_servers]: the load before tick 0
+    # lag_path(averages=True): the same quantities of the distribution AVERAGED
+    # over tick j (what a random arrival of the tick meets); None without it.
+    # NaN where the status has no evaluation and on the tiled (wide) runs.
+    ttft_avg: Optional[np.ndarray] = None  # float32 msec
+    itl_avg: Optional[np.ndarray] = None  # float32 msec
+    rho_avg: Optional[np.ndarray] = None  # float32
+    blocked_avg: Optional[np.ndarray] = None  # float32
+    violated_avg: Optional[np.ndarray] = None  # bool: the targets against ttft_avg, itl_avg
 
 
 # Longest forecast one rollout() takes, and the steps one device pass of it
@@ -1393,7 +1401,8 @@ class FastSweep:
 
     def lag_path(self, scales=None, arrival=None, allocation=None, delay: int = 1,
                  start_allocation=None, from_arrival=None, tick_seconds: float = 60.0,
-                 max_steps: int = LAG_MAX_STEPS, max_n: int = LAG_MAX_N) -> LagPathResult:
+                 max_steps: int = LAG_MAX_STEPS, max_n: int = LAG_MAX_N,
+                 averages: bool = False) -> LagPathResult:
         """The transient response ALONG a forecast: what users see, tick by
         tick, while an allocation that is ``delay`` ticks late follows the load.
         lag() takes one load step from a stationary start; here the state of
@@ -1437,9 +1446,19 @@ class FastSweep:
         at most LAG_WIDE_HALO steps, so they need no chunks), on the CPU by the
         same golden; the narrow runs go through the one-block pass as before.
 
+        ``averages``: also ttft_avg, itl_avg, rho_avg, blocked_avg and
+        violated_avg per (tick, server), the same functionals and targets
+        applied to the distribution averaged over the tick, (1 / dt) int p
+        (analyzer/lag.py lag_path_transient(averages=True); on the GPU
+        wva_lag_path_avg_t in the same schedule and step counts). The end state
+        can be fine after a tick mostly spent queueing; the average is what a
+        random arrival of the tick met. Statuses are unchanged; off the LAG_OK
+        ticks the averaged fields hold what the end-state ones hold.
+
         Limits: cells with N > ``max_n`` (at most LAG_WIDE_MAX_N) stay
         LAG_TOO_WIDE, the narrow and the wide pass run one after the other,
-        and there are no time-averaged functionals inside a tick. Chain
+        and the tiled runs (N > LAG_MAX_N) have no averages: their averaged
+        fields are NaN and violated_avg False on both backends. Chain
         analyzer only. On the GPU the narrow runs' ticks
         run in chunks of at most 16 whose step sums stay within ``max_steps``
         per block, the state carried between the launches on the device. The
@@ -1494,6 +1513,8 @@ class FastSweep:
         shape = (n_t, n_srv)
         rec = {k: np.zeros(shape, dtype=np.float32) for k in _LAG_FLOATS}
         violated = np.zeros(shape, dtype=bool)
+        violated_avg = np.zeros(shape, dtype=bool)
+        avg = {}  # the averaged fields of the runs, laid over a copy of rec at the end
         status = np.full(shape, LAG_NOT_HELD, dtype=np.int32)
         steps = np.zeros(shape, dtype=np.int32)
         _, in_tok, out_tok = self._base_load()
@@ -1603,13 +1624,20 @@ class FastSweep:
                         fields, [r[2] for r in sel], [r[7] for r in sel], n_t, max_steps)
                     self.lag_path_pass.update(tasks=len(table), chunks=len(bounds) - 1,
                                               launches=len(launches), records=recs, table=table)
-                    of, ov, osteps = g.lag_path(table, recs, desc, launches, n_t, n_srv,
-                                                max_steps, dt)
+                    if averages:
+                        of, ov, osteps, af, av = g.lag_path_avg(
+                            table, recs, desc, launches, n_t, n_srv, max_steps, dt)
+                    else:
+                        of, ov, osteps = g.lag_path(table, recs, desc, launches, n_t, n_srv,
+                                                    max_steps, dt)
                 for i, _, j, _, _, lam, _, want in sel:
                     sl = slice(j, j + len(lam))
                     for r, f in enumerate(_LAG_FLOATS):
                         rec[f][sl, i] = of[r][sl, i]
                     violated[sl, i] = ov[sl, i] != 0
+                    if averages and part is not is_wide:
+                        avg[i, j] = ({f: af[r][sl, i] for r, f in enumerate(_LAG_FLOATS)},
+                                     av[sl, i] != 0)
                     # the schedule and the OK verdicts come from the host's count
                     if not np.array_equal(osteps[sl, i], want):
                         raise HipKernelError("wva_ctx_lag_path: the device's step counts differ "
@@ -1620,16 +1648,33 @@ class FastSweep:
                 rates, n_max, parms, req = models[k]
                 raw = lag_path_transient(
                     rates, ("stationary", lam0) if start == LAG_PATH_STATIONARY else "empty",
-                    lam, keep, dt)
+                    lam, keep, dt, averages=averages and n_max <= LAG_MAX_N)
                 sl = slice(j, j + len(lam))
+                t_ttft, t_itl = st["t_ttft"][k], st["t_itl"][k]
+                if averages and n_max <= LAG_MAX_N:
+                    raw, raw_avg = raw
+                    ttft, itl, rho = lag_latency(raw_avg, parms, req, n_max)
+                    avg[i, j] = ({"ttft": ttft, "itl": itl, "rho": rho, "blocked": raw_avg[:, 0]},
+                                 ((t_ttft != 0) & (ttft > t_ttft)) | ((t_itl != 0) & (itl > t_itl)))
                 ttft, itl, rho = lag_latency(raw, parms, req, n_max)
                 rec["ttft"][sl, i], rec["itl"][sl, i], rec["rho"][sl, i] = ttft, itl, rho
                 rec["wait"][sl, i], rec["blocked"][sl, i] = raw[:, 4], raw[:, 0]
                 rec["in_system"][sl, i] = raw[:, 2]
-                t_ttft, t_itl = st["t_ttft"][k], st["t_itl"][k]
                 violated[sl, i] = ((t_ttft != 0) & (ttft > t_ttft)) | ((t_itl != 0) & (itl > t_itl))
         counts = np.stack([(status == c).sum(axis=1) for c in range(len(LAG_STATUS_NAMES))],
                           axis=1).astype(np.int64)
+        if averages:
+            # off the runs the averaged fields are the end-state ones (a status'
+            # floats, NaN); on the tiled runs NaN; on the one-block runs the averages
+            names = ("ttft", "itl", "rho", "blocked")
+            for f in names:
+                rec[f + "_avg"] = np.where(status == LAG_OK, np.float32(np.nan), rec[f])
+            for (i, j), (fields, viol) in avg.items():
+                sl = slice(j, j + len(viol))
+                for f in names:
+                    rec[f + "_avg"][sl, i] = fields[f]
+                violated_avg[sl, i] = viol
+            rec["violated_avg"] = violated_avg
         return LagPathResult(
             violated=violated, status=status, steps=steps, held_replicas=rep,
             acc_idx=np.where(status == LAG_NOT_HELD, -1, acc).astype(np.int32),

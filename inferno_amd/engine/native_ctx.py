@@ -600,6 +600,26 @@ class NativeCtx:
                 _copy_out(out[1], ctypes.c_uint8, (n_ticks, n_slots)),
                 _copy_out(out[2], ctypes.c_int32, (n_ticks, n_slots)))
 
+    def lag_path_avg(self, table: np.ndarray, recs: np.ndarray, desc: np.ndarray,
+                     launches: np.ndarray, n_ticks: int, n_slots: int, max_steps: int,
+                     dt_ms: float):
+        """wva_ctx_lag_path_avg: lag_path()'s arguments and its three arrays,
+        then fp32 [6, S, n_slots] of the distribution averaged over each tick
+        and uint8 [S, n_slots] violated_avg. Changes as little as lag()."""
+        out = [ctypes.c_void_p() for _ in range(5)]
+        rc = self._lib.wva_ctx_lag_path_avg(
+            self.ctx, table.ctypes.data, recs.ctypes.data, desc.ctypes.data, launches.ctypes.data,
+            len(table), len(recs), len(launches), n_ticks, n_slots, int(max_steps), float(dt_ms),
+            *[ctypes.byref(p) for p in out],
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_lag_path_avg failed: {rc}")
+        return (_copy_out(out[0], ctypes.c_float, (6, n_ticks, n_slots)),
+                _copy_out(out[1], ctypes.c_uint8, (n_ticks, n_slots)),
+                _copy_out(out[2], ctypes.c_int32, (n_ticks, n_slots)),
+                _copy_out(out[3], ctypes.c_float, (6, n_ticks, n_slots)),
+                _copy_out(out[4], ctypes.c_uint8, (n_ticks, n_slots)))
+
     def lag_path_wide(self, table: np.ndarray, wide: np.ndarray, segs: np.ndarray,
                       tiles: np.ndarray, desc: np.ndarray, n_ticks: int, n_slots: int,
                       max_steps: int, stride: int, halo: int, dt_ms: float):

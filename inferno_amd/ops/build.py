@@ -32,6 +32,7 @@ NATIVE_HDRS = [
     os.path.join(OPS_DIR, "hip", "wva_ctx.inc"),
     os.path.join(OPS_DIR, "hip", "wva_lag.inc"),
     os.path.join(OPS_DIR, "hip", "wva_lag_path.inc"),
+    os.path.join(OPS_DIR, "hip", "wva_lag_path_avg.inc"),
     os.path.join(OPS_DIR, "hip", "wva_lag_path_wide.inc"),
     os.path.join(OPS_DIR, "native", "wva_stage.h"),
     os.path.join(OPS_DIR, "native", "wva_arena.h"),

@@ -1907,6 +1907,20 @@ extern "C" int wva_ctx_lag_wide(void *ctx, const void *tasks, void *wide, const 
   return 0;
 }
 
+// the lag-path arena (lagp_dev, lagp_pin) grown to hold a pass; false: it
+// could not be allocated, the context is intact and holds no arena
+static bool wva_ctx_lagp_reserve(WvaCtx *c, size_t bytes, size_t pin_bytes) {
+  if (bytes <= c->lagp_dev_cap && pin_bytes <= c->lagp_pin_cap) return true;
+  const size_t dev_want = bytes > c->lagp_dev_cap ? bytes : c->lagp_dev_cap;
+  const size_t pin_want = pin_bytes > c->lagp_pin_cap ? pin_bytes : c->lagp_pin_cap;
+  wva_arena_free(c->lagp_dev, c->lagp_pin);
+  c->lagp_dev_cap = c->lagp_pin_cap = 0;
+  if (!wva_arena_alloc(c, dev_want, pin_want, false, &c->lagp_dev, &c->lagp_pin)) return false;
+  c->lagp_dev_cap = dev_want;
+  c->lagp_pin_cap = pin_want;
+  return true;
+}
+
 // One lag-path pass (wva_lag_path.inc): the transient response of n_tasks runs
 // along n_ticks ticks of dt msec. The four tables are the host schedule of
 // ops/sweep.py lag_path_schedule: tasks (one per run, with its carry offset),
@@ -1935,16 +1949,7 @@ extern "C" int wva_ctx_lag_path(void *ctx, const void *tasks, const void *recs,
   int rc = wva_lag_path_plan(in, WVA_LAG_WIDE_SLAB_CAP, &slab);
   if (rc != 0) return rc;
   const size_t bytes = wva_lag_path_layout(in, slab, false, off);
-  const size_t pin_bytes = off[WVA_LP_CARRY];
-  if (bytes > c->lagp_dev_cap || pin_bytes > c->lagp_pin_cap) {
-    const size_t dev_want = bytes > c->lagp_dev_cap ? bytes : c->lagp_dev_cap;
-    const size_t pin_want = pin_bytes > c->lagp_pin_cap ? pin_bytes : c->lagp_pin_cap;
-    wva_arena_free(c->lagp_dev, c->lagp_pin);
-    c->lagp_dev_cap = c->lagp_pin_cap = 0;
-    if (!wva_arena_alloc(c, dev_want, pin_want, false, &c->lagp_dev, &c->lagp_pin)) return -41;
-    c->lagp_dev_cap = dev_want;
-    c->lagp_pin_cap = pin_want;
-  }
+  if (!wva_ctx_lagp_reserve(c, bytes, off[WVA_LP_CARRY])) return -41;
   WvaDeviceGuard on_dev(c->dev_dyn);
   char *d = (char *)c->lagp_dev, *h = (char *)c->lagp_pin;
   wva_lag_path_stage(in, off, h);
@@ -1959,6 +1964,47 @@ extern "C" int wva_ctx_lag_path(void *ctx, const void *tasks, const void *recs,
   if (out_f) *out_f = h + off[WVA_LP_F];
   if (out_violated) *out_violated = h + off[WVA_LP_VIOL];
   if (out_steps) *out_steps = h + off[WVA_LP_STEPS];
+  return 0;
+}
+
+// wva_ctx_lag_path with the time averages over every tick
+// (wva_lag_path_avg.inc): the same tables, checks, streams, rounds and carry
+// slabs in the same arena, and two more pinned blocks, valid as long: fp32
+// [6][n_ticks][n_slots] of the averaged distribution and u8
+// [n_ticks][n_slots] violated_avg. It touches as little, and returns the same
+// codes.
+extern "C" int wva_ctx_lag_path_avg(void *ctx, const void *tasks, const void *recs,
+                                    const double *desc, const int *launches, int n_tasks,
+                                    int n_recs, int n_launches, int n_ticks, int n_slots,
+                                    int max_steps, double dt, const void **out_f,
+                                    const void **out_violated, const void **out_steps,
+                                    const void **out_avg_f, const void **out_avg_violated) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr) return -31;
+  WvaLagPathIn in = {(const WvaLagPathTask *)tasks, (const WvaLagPathRec *)recs, desc,
+                     (const WvaLagPathLaunch *)launches, n_tasks, n_recs, n_launches, n_ticks,
+                     n_slots, max_steps, dt};
+  size_t slab = 0, off[WVA_LPA_N];
+  int rc = wva_lag_path_plan(in, WVA_LAG_WIDE_SLAB_CAP, &slab);
+  if (rc != 0) return rc;
+  const size_t bytes = wva_lag_path_avg_layout(in, slab, false, off);
+  if (!wva_ctx_lagp_reserve(c, bytes, off[WVA_LPA_CARRY])) return -41;
+  WvaDeviceGuard on_dev(c->dev_dyn);
+  char *d = (char *)c->lagp_dev, *h = (char *)c->lagp_pin;
+  wva_lag_path_stage(in, off, h);
+  if (hipMemcpyAsync(d, h, off[WVA_LPA_F], hipMemcpyHostToDevice, c->s0) != hipSuccess) return -32;
+  hipStream_t stream[WVA_LAG_CLASSES] = {c->s0, c->side[0], c->side[1], c->side[2]};
+  rc = wva_lag_path_avg_launch(in, off, d, false, stream, c->e_up, c->e_b);
+  if (rc != 0) return rc;
+  if (hipMemcpyAsync(h + off[WVA_LPA_F], d + off[WVA_LPA_F], off[WVA_LPA_RAW] - off[WVA_LPA_F],
+                     hipMemcpyDeviceToHost, c->s0) != hipSuccess)
+    return -33;
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -34;
+  if (out_f) *out_f = h + off[WVA_LPA_F];
+  if (out_violated) *out_violated = h + off[WVA_LPA_VIOL];
+  if (out_steps) *out_steps = h + off[WVA_LPA_STEPS];
+  if (out_avg_f) *out_avg_f = h + off[WVA_LPA_AF];
+  if (out_avg_violated) *out_avg_violated = h + off[WVA_LPA_AVIOL];
   return 0;
 }
 

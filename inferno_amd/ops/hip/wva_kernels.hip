@@ -3921,6 +3921,10 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_greedy(
 // carried from tick to tick and from launch to launch), a sibling of wva_lag_t.
 #include "wva_lag_path.inc"
 
+// Lag path averages (wva_lag_path_avg_t: wva_lag_path_t with the time average
+// of the distribution over every tick beside its end state).
+#include "wva_lag_path_avg.inc"
+
 // Lag paths for wide cells (wva_lag_path_tile_t: the tiled wide-lag scheme with
 // per-tick rates and the state kept between ticks), siblings of the wide-lag
 // kernels of wva_lag.inc.

@@ -460,12 +460,40 @@ static int wva_lag_path_dispatch(int cls, int n, int rec0, const WvaLagPathArgs 
   return (int)hipGetLastError();
 }
 
-// The launches of a staged pass behind whatever `main` holds. Class k runs on
+// The launches of a staged pass behind whatever `main` holds, each made by
+// dispatch(class, count, rec0, stream). Class k runs on
 // stream[k] (equal streams are fine: the probe passes one four times), forked
 // from and joined back into stream[0] = main with fork / join[k - 1] once per
 // round: a task keeps its class, so stream order alone puts its chunks one
 // after the other, and only the reuse of the slab by the next round needs all
 // classes to have finished.
+template <typename Dispatch>
+static int wva_lag_path_rounds(const WvaLagPathIn &in, hipStream_t *stream, hipEvent_t fork,
+                               hipEvent_t *join, Dispatch dispatch) {
+  hipStream_t main = stream[0];
+  for (int l0 = 0; l0 < in.n_launches;) {
+    int l1 = l0;  // the round's launches
+    while (l1 < in.n_launches && in.launches[l1].round == in.launches[l0].round) ++l1;
+    bool used[WVA_LAG_CLASSES] = {};
+    if (hipEventRecord(fork, main) != hipSuccess) return -10;
+    for (int l = l0; l < l1; ++l) {
+      const WvaLagPathLaunch &L = in.launches[l];
+      hipStream_t s = stream[L.cls];
+      if (!used[L.cls] && s != main && hipStreamWaitEvent(s, fork, 0) != hipSuccess) return -11;
+      used[L.cls] = true;
+      const int rc = dispatch(L.cls, L.count, L.rec0, s);
+      if (rc != 0) return rc;
+    }
+    for (int k = 1; k < WVA_LAG_CLASSES; ++k) {
+      if (!used[k] || stream[k] == main) continue;
+      if (hipEventRecord(join[k - 1], stream[k]) != hipSuccess) return -12;
+      if (hipStreamWaitEvent(main, join[k - 1], 0) != hipSuccess) return -14;
+    }
+    l0 = l1;
+  }
+  return 0;
+}
+
 static int wva_lag_path_launch(const WvaLagPathIn &in, const size_t *off, char *d, bool raw,
                                hipStream_t *stream, hipEvent_t fork, hipEvent_t *join) {
   WvaLagPathArgs a = {};
@@ -481,28 +509,9 @@ static int wva_lag_path_launch(const WvaLagPathIn &in, const size_t *off, char *
   a.violated = (uint8_t *)(d + off[WVA_LP_VIOL]);
   a.steps = (int *)(d + off[WVA_LP_STEPS]);
   a.raw = raw ? (double *)(d + off[WVA_LP_RAW]) : nullptr;
-  hipStream_t main = stream[0];
-  for (int l0 = 0; l0 < in.n_launches;) {
-    int l1 = l0;  // the round's launches
-    while (l1 < in.n_launches && in.launches[l1].round == in.launches[l0].round) ++l1;
-    bool used[WVA_LAG_CLASSES] = {};
-    if (hipEventRecord(fork, main) != hipSuccess) return -10;
-    for (int l = l0; l < l1; ++l) {
-      const WvaLagPathLaunch &L = in.launches[l];
-      hipStream_t s = stream[L.cls];
-      if (!used[L.cls] && s != main && hipStreamWaitEvent(s, fork, 0) != hipSuccess) return -11;
-      used[L.cls] = true;
-      const int rc = wva_lag_path_dispatch(L.cls, L.count, L.rec0, a, s);
-      if (rc != 0) return rc;
-    }
-    for (int k = 1; k < WVA_LAG_CLASSES; ++k) {
-      if (!used[k] || stream[k] == main) continue;
-      if (hipEventRecord(join[k - 1], stream[k]) != hipSuccess) return -12;
-      if (hipStreamWaitEvent(main, join[k - 1], 0) != hipSuccess) return -14;
-    }
-    l0 = l1;
-  }
-  return 0;
+  return wva_lag_path_rounds(in, stream, fork, join, [&](int cls, int n, int rec0, hipStream_t s) {
+    return wva_lag_path_dispatch(cls, n, rec0, a, s);
+  });
 }
 
 // One-shot probe for tests and tools, in the manner of

@@ -475,6 +475,14 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
                                                       ctypes.POINTER(ctypes.c_size_t),
                                                       ctypes.POINTER(ctypes.c_size_t)]
     )
+    # lag path averages (FastSweep.lag_path(averages=True)): as above, with the
+    # averaged records and verdicts as two more outputs
+    lib.wva_ctx_lag_path_avg.restype = ctypes.c_int
+    lib.wva_ctx_lag_path_avg.argtypes = (
+        list(lib.wva_ctx_lag_path.argtypes) + [ctypes.POINTER(ctypes.c_void_p)] * 2
+    )
+    lib.wva_lag_path_avg_probe_launch.restype = ctypes.c_int
+    lib.wva_lag_path_avg_probe_launch.argtypes = lib.wva_lag_path_probe_launch.argtypes
     # wide lag paths (FastSweep.lag_path(max_n=...)): the four tables of
     # lag_path_wide_schedule, the descriptors, their lengths and extents,
     # max_steps, stride, halo, dt
@@ -1085,7 +1093,7 @@ def lag_path_schedule(fields: dict, tick0, tick_steps, n_ticks: int, max_steps: 
 
 
 def run_lag_path_probe(arrays: dict, start, lam, keep, tick_seconds: float,
-                       max_steps: int = 1 << 22, device: str = "cuda"):
+                       max_steps: int = 1 << 22, device: str = "cuda", averages: bool = False):
     """One-shot probe of the lag-path kernel (wva_lag_path_t), for tests and
     tools, in the style of run_lag_probe. ``arrays`` as there; every cell is
     one run over all S ticks of ``tick_seconds``: ``start[i]`` is "empty" or
@@ -1093,7 +1101,9 @@ def run_lag_path_probe(arrays: dict, start, lam, keep, tick_seconds: float,
     per-tick rate (req/msec per replica) and scale-out factor. ``max_steps``
     drives the chunking (lag_path_schedule), so a small one sends the state
     through the carry. Returns (raw float64 [n_cells, S, 5] as run_lag_probe,
-    steps int32 [n_cells, S], the chunk bounds)."""
+    steps int32 [n_cells, S], the chunk bounds). ``averages``: run
+    wva_lag_path_avg_t instead and return (raw, the raw functionals of the
+    time-averaged distribution [n_cells, S, 5], steps, bounds)."""
     import numpy as np
     import torch
 
@@ -1125,22 +1135,27 @@ def run_lag_path_probe(arrays: dict, start, lam, keep, tick_seconds: float,
         fields, np.zeros(n_cells, dtype=np.int64), list(want), n_ticks, int(max_steps))
     desc = np.ascontiguousarray(np.stack([lam, keep], axis=2))
     need = ctypes.c_size_t()
-    offs = (ctypes.c_size_t * 4)()
+    # the offsets the launcher reports: records, violated, steps, (averaged
+    # records and verdicts,) raw functionals (and the averaged ones)
+    n_off, i_raw = (7, 5) if averages else (4, 3)
+    launch = lib.wva_lag_path_avg_probe_launch if averages else lib.wva_lag_path_probe_launch
+    offs = (ctypes.c_size_t * n_off)()
     args = (table.ctypes.data, recs.ctypes.data, desc.ctypes.data, launches.ctypes.data,
             len(table), len(recs), len(launches), n_ticks, n_cells, int(max_steps), dt,
             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    rc = lib.wva_lag_path_probe_launch(*args, None, 0, ctypes.byref(need), offs)
+    rc = launch(*args, None, 0, ctypes.byref(need), offs)
     if rc != 0:
-        raise HipKernelError(f"wva_lag_path_probe_launch failed: {rc}")
+        raise HipKernelError(f"{launch.__name__} failed: {rc}")
     dev = torch.empty(need.value, dtype=torch.uint8, device=device)
-    rc = lib.wva_lag_path_probe_launch(*args, _ptr(dev), need.value, ctypes.byref(need), offs)
+    rc = launch(*args, _ptr(dev), need.value, ctypes.byref(need), offs)
     if rc != 0:
-        raise HipKernelError(f"wva_lag_path_probe_launch failed: {rc}")
+        raise HipKernelError(f"{launch.__name__} failed: {rc}")
     cells = n_cells * n_ticks
-    host = dev[offs[0]:offs[3] + cells * 40].cpu().numpy()
+    host = dev[offs[0]:offs[n_off - 1] + cells * 40].cpu().numpy()
     at = lambda i, n, t: host[offs[i] - offs[0]:offs[i] - offs[0] + n].view(t)  # noqa: E731
-    raw = at(3, cells * 40, np.float64).reshape(n_cells, n_ticks, 5).copy()
-    return raw, at(2, cells * 4, np.int32).reshape(n_ticks, n_cells).T.copy(), bounds
+    raws = [at(i, cells * 40, np.float64).reshape(n_cells, n_ticks, 5).copy()
+            for i in range(i_raw, n_off)]
+    return (*raws, at(2, cells * 4, np.int32).reshape(n_ticks, n_cells).T.copy(), bounds)
 
 
 def lag_path_wide_schedule(fields: dict, tick0, lam, keep, smax, dt: float, n_ticks: int,
