@@ -17,7 +17,11 @@ in the same run) are recorded. With --averages the call with averages=True
 (wva_lag_path_avg_t) is checked against the golden's averages on the same
 sample and timed in alternation with the default call, and the heaviest record
 runs through both probes, also in alternation: the cost of the averages per
-call and per step. Needs a GPU; prints one JSON line.
+call and per step. With both, the combined call runs the wide runs through
+wva_lag_path_avg_tile_t (two blocks per tile); the wide pass' native call is
+timed with and without the averages, beside the bound the schedule gives:
+1 + (block-steps of the average blocks) / (all block-steps). Needs a GPU;
+prints one JSON line.
 """
 from __future__ import annotations
 
@@ -124,17 +128,18 @@ def main() -> int:
                                   getattr(res_avg, f).view(np.int32)), f
 
     # ---- ms per call (and of the wide pass' native call alone, inside it)
-    native_ms = []
+    native_ms, native_avg_ms = [], []
     if wide_table is not None:
-        inner = fs._gpu.lag_path_wide
+        def timed(inner, into):
+            def call(*a):
+                t0 = time.perf_counter()
+                r = inner(*a)
+                into.append((time.perf_counter() - t0) * 1e3)
+                return r
+            return call
 
-        def timed(*a):
-            t0 = time.perf_counter()
-            r = inner(*a)
-            native_ms.append((time.perf_counter() - t0) * 1e3)
-            return r
-
-        fs._gpu.lag_path_wide = timed
+        fs._gpu.lag_path_wide = timed(fs._gpu.lag_path_wide, native_ms)
+        fs._gpu.lag_path_wide_avg = timed(fs._gpu.lag_path_wide_avg, native_avg_ms)
     call_ms, avg_ms = [], []
     for _ in range(args.reps):
         t0 = time.perf_counter()
@@ -230,6 +235,20 @@ def main() -> int:
                        "default_call_ms_median": statistics.median(base_ms),
                        "wide_part_ms": wide_ms,
                        "state_updates_per_s": shape["wide_updates"] / (wide_ms * 1e-3)}
+        if args.averages:
+            # the second block of a tile runs on the segments that touch the
+            # window (its plain steps again, then the window's); block-steps of
+            # the schedule, a segment's steps times its task's tiles
+            segs, rows = shape["wide_segs"], shape["wide_rows"]
+            tiles_of = np.repeat(rows["n_tiles"].astype(np.int64), rows["n_seg"])
+            touches = segs["first"] + segs["count"] > segs["jlo"]
+            all_steps = int((segs["count"] * tiles_of).sum())
+            avg_steps = int((segs["count"] * tiles_of * touches).sum())
+            out["wide"]["averages"] = {
+                "native_pass_ms_median": statistics.median(native_avg_ms),
+                "over_native_pass": statistics.median(native_avg_ms) / statistics.median(native_ms),
+                "block_steps": all_steps, "average_block_steps": avg_steps,
+                "bound_from_schedule": 1.0 + avg_steps / all_steps}
     line = json.dumps(out)
     print(line)
     if args.out:

@@ -261,7 +261,7 @@ class LagPathResult:
     from_arrival: np.ndarray  # float32 [n_servers]: the load before tick 0
     # lag_path(averages=True): the same quantities of the distribution AVERAGED
     # over tick j (what a random arrival of the tick meets); None without it.
-    # NaN where the status has no evaluation and on the tiled (wide) runs.
+    # NaN where the status has no evaluation.
     ttft_avg: Optional[np.ndarray] = None  # float32 msec
     itl_avg: Optional[np.ndarray] = None  # float32 msec
     rho_avg: Optional[np.ndarray] = None  # float32
@@ -1450,16 +1450,16 @@ class FastSweep:
         violated_avg per (tick, server), the same functionals and targets
         applied to the distribution averaged over the tick, (1 / dt) int p
         (analyzer/lag.py lag_path_transient(averages=True); on the GPU
-        wva_lag_path_avg_t in the same schedule and step counts). The end state
+        wva_lag_path_avg_t in the same schedule and step counts, and for the
+        tiled runs wva_lag_path_avg_tile_t, a second block per tile that sums
+        the average inside the window). The end state
         can be fine after a tick mostly spent queueing; the average is what a
         random arrival of the tick met. Statuses are unchanged; off the LAG_OK
         ticks the averaged fields hold what the end-state ones hold.
 
         Limits: cells with N > ``max_n`` (at most LAG_WIDE_MAX_N) stay
-        LAG_TOO_WIDE, the narrow and the wide pass run one after the other,
-        and the tiled runs (N > LAG_MAX_N) have no averages: their averaged
-        fields are NaN and violated_avg False on both backends. Chain
-        analyzer only. On the GPU the narrow runs' ticks
+        LAG_TOO_WIDE, and the narrow and the wide pass run one after the
+        other. Chain analyzer only. On the GPU the narrow runs' ticks
         run in chunks of at most 16 whose step sums stay within ``max_steps``
         per block, the state carried between the launches on the device. The
         pass stages no tick and changes nothing any other call returns."""
@@ -1605,12 +1605,17 @@ class FastSweep:
                         fields, [r[2] for r in sel], [r[5] for r in sel], [r[6] for r in sel],
                         [float(models[k][0].max()) for k in kk], dt, n_t, LAG_WIDE_STRIDE,
                         LAG_WIDE_HALO, n_srv)
-                    of, ov, osteps, made = g.lag_path_wide(
-                        table, wide, segs, tiles, desc, n_t, n_srv, max_steps, LAG_WIDE_STRIDE,
-                        LAG_WIDE_HALO, dt)
+                    if averages:
+                        of, ov, osteps, made, af, av = g.lag_path_wide_avg(
+                            table, wide, segs, tiles, desc, n_t, n_srv, max_steps,
+                            LAG_WIDE_STRIDE, LAG_WIDE_HALO, dt)
+                    else:
+                        of, ov, osteps, made = g.lag_path_wide(
+                            table, wide, segs, tiles, desc, n_t, n_srv, max_steps,
+                            LAG_WIDE_STRIDE, LAG_WIDE_HALO, dt)
                     self.lag_path_pass.update(
                         wide_tasks=len(table), wide_tiles=len(tiles), wide_segments=len(segs),
-                        wide_table=table,
+                        wide_table=table, wide_rows=wide, wide_segs=segs,
                         wide_launches=int(made.sum()), wide_step_launches=int(made[1]),
                         # every step moves the K + 1 states of its task
                         wide_updates=int(((11 * fields["N"].astype(np.int64) + 1)
@@ -1635,7 +1640,7 @@ class FastSweep:
                     for r, f in enumerate(_LAG_FLOATS):
                         rec[f][sl, i] = of[r][sl, i]
                     violated[sl, i] = ov[sl, i] != 0
-                    if averages and part is not is_wide:
+                    if averages:
                         avg[i, j] = ({f: af[r][sl, i] for r, f in enumerate(_LAG_FLOATS)},
                                      av[sl, i] != 0)
                     # the schedule and the OK verdicts come from the host's count
@@ -1648,10 +1653,10 @@ class FastSweep:
                 rates, n_max, parms, req = models[k]
                 raw = lag_path_transient(
                     rates, ("stationary", lam0) if start == LAG_PATH_STATIONARY else "empty",
-                    lam, keep, dt, averages=averages and n_max <= LAG_MAX_N)
+                    lam, keep, dt, averages=averages)
                 sl = slice(j, j + len(lam))
                 t_ttft, t_itl = st["t_ttft"][k], st["t_itl"][k]
-                if averages and n_max <= LAG_MAX_N:
+                if averages:
                     raw, raw_avg = raw
                     ttft, itl, rho = lag_latency(raw_avg, parms, req, n_max)
                     avg[i, j] = ({"ttft": ttft, "itl": itl, "rho": rho, "blocked": raw_avg[:, 0]},
@@ -1665,7 +1670,7 @@ class FastSweep:
                           axis=1).astype(np.int64)
         if averages:
             # off the runs the averaged fields are the end-state ones (a status'
-            # floats, NaN); on the tiled runs NaN; on the one-block runs the averages
+            # floats, NaN); on the runs, one-block and tiled, the averages
             names = ("ttft", "itl", "rho", "blocked")
             for f in names:
                 rec[f + "_avg"] = np.where(status == LAG_OK, np.float32(np.nan), rec[f])

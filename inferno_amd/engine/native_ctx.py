@@ -641,6 +641,29 @@ class NativeCtx:
                 _copy_out(out[1], ctypes.c_uint8, (n_ticks, n_slots)),
                 _copy_out(out[2], ctypes.c_int32, (n_ticks, n_slots)), made)
 
+    def lag_path_wide_avg(self, table: np.ndarray, wide: np.ndarray, segs: np.ndarray,
+                          tiles: np.ndarray, desc: np.ndarray, n_ticks: int, n_slots: int,
+                          max_steps: int, stride: int, halo: int, dt_ms: float):
+        """wva_ctx_lag_path_wide_avg: lag_path_wide()'s arguments and its four
+        results, then fp32 [6, S, n_slots] of the distribution averaged over
+        each tick and uint8 [S, n_slots] violated_avg. Changes as little."""
+        out = [ctypes.c_void_p() for _ in range(5)]
+        made = np.zeros(3, dtype=np.int32)
+        rc = self._lib.wva_ctx_lag_path_wide_avg(
+            self.ctx, table.ctypes.data, wide.ctypes.data, segs.ctypes.data, tiles.ctypes.data,
+            desc.ctypes.data, len(table), len(segs), len(tiles), n_ticks, n_slots,
+            int(max_steps), int(stride), int(halo), float(dt_ms),
+            *[ctypes.byref(p) for p in out[:3]], made.ctypes.data,
+            *[ctypes.byref(p) for p in out[3:]],
+        )
+        if rc != 0:
+            raise HipKernelError(f"wva_ctx_lag_path_wide_avg failed: {rc}")
+        return (_copy_out(out[0], ctypes.c_float, (6, n_ticks, n_slots)),
+                _copy_out(out[1], ctypes.c_uint8, (n_ticks, n_slots)),
+                _copy_out(out[2], ctypes.c_int32, (n_ticks, n_slots)), made,
+                _copy_out(out[3], ctypes.c_float, (6, n_ticks, n_slots)),
+                _copy_out(out[4], ctypes.c_uint8, (n_ticks, n_slots)))
+
     def plan_cells(self, n_scen: int) -> dict:
         """Per-cell outputs [S, n_cells] of the planning pass that just ran."""
         cells = {k: np.empty((n_scen, self.n_cells), dtype=d)

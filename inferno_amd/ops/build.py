@@ -34,6 +34,7 @@ NATIVE_HDRS = [
     os.path.join(OPS_DIR, "hip", "wva_lag_path.inc"),
     os.path.join(OPS_DIR, "hip", "wva_lag_path_avg.inc"),
     os.path.join(OPS_DIR, "hip", "wva_lag_path_wide.inc"),
+    os.path.join(OPS_DIR, "hip", "wva_lag_path_avg_wide.inc"),
     os.path.join(OPS_DIR, "native", "wva_stage.h"),
     os.path.join(OPS_DIR, "native", "wva_arena.h"),
 ]

@@ -159,8 +159,8 @@ struct WvaCtx {
   void *lag_dev;
   void *lag_pin;
   size_t lag_cap;  // bytes each of them holds (0 = not allocated)
-  // wide lag (wva_ctx_lag_wide) and wide lag paths (wva_ctx_lag_path_wide),
-  // which never overlap: their own pair, because the device side also holds
+  // wide lag (wva_ctx_lag_wide) and wide lag paths (wva_ctx_lag_path_wide,
+  // wva_ctx_lag_path_wide_avg), which never overlap: their own pair, because the device side also holds
   // the slabs of a round and the pinned side only tables and records
   void *lagw_dev = nullptr;
   void *lagw_pin = nullptr;
@@ -2035,7 +2035,7 @@ extern "C" int wva_ctx_lag_path_wide(void *ctx, const void *tasks, void *wide, c
                          (const WvaLagSeg *)segs, (const WvaLagTile *)tiles, desc, n_tasks,
                          n_segs, n_tiles, n_ticks, n_slots, stride, halo, max_steps, dt};
   size_t slab = 0, off[WVA_LPW_N];
-  int rc = wva_lag_path_wide_plan(in, WVA_LAG_WIDE_SLAB_CAP, &slab);
+  int rc = wva_lag_path_wide_plan(in, 3, WVA_LAG_WIDE_SLAB_CAP, &slab);
   if (rc != 0) return rc;
   const size_t bytes = wva_lag_path_wide_layout(in, slab, false, off);
   rc = wva_lag_wide_reserve(c, bytes, off[WVA_LPW_PART]);
@@ -2054,6 +2054,51 @@ extern "C" int wva_ctx_lag_path_wide(void *ctx, const void *tasks, void *wide, c
   if (out_f) *out_f = h + off[WVA_LPW_F];
   if (out_violated) *out_violated = h + off[WVA_LPW_VIOL];
   if (out_steps) *out_steps = h + off[WVA_LPW_STEPS];
+  return 0;
+}
+
+// wva_ctx_lag_path_wide with the time averages over every tick
+// (wva_lag_path_avg_wide.inc): the same tables and checks (a task's slab is 4 G
+// doubles), rounds and launch prefixes on s0 with two blocks per tile, in the
+// same arena pair (wva_lag_wide_reserve), and two more pinned blocks, valid as
+// long: fp32 [6][n_ticks][n_slots] of the averaged distribution and u8
+// [n_ticks][n_slots] violated_avg. One upload, one download, one synchronise.
+// It touches as little, and returns the same codes.
+extern "C" int wva_ctx_lag_path_wide_avg(void *ctx, const void *tasks, void *wide,
+                                         const void *segs, const void *tiles, const double *desc,
+                                         int n_tasks, int n_segs, int n_tiles, int n_ticks,
+                                         int n_slots, int max_steps, int stride, int halo,
+                                         double dt, const void **out_f, const void **out_violated,
+                                         const void **out_steps, int *launches,
+                                         const void **out_avg_f, const void **out_avg_violated) {
+  WvaCtx *c = (WvaCtx *)ctx;
+  if (c == nullptr) return -31;
+  WvaLagPathWideIn in = {(const WvaLagPathTask *)tasks, (WvaLagPathWideTask *)wide,
+                         (const WvaLagSeg *)segs, (const WvaLagTile *)tiles, desc, n_tasks,
+                         n_segs, n_tiles, n_ticks, n_slots, stride, halo, max_steps, dt};
+  size_t slab = 0, off[WVA_LPWA_N];
+  int rc = wva_lag_path_wide_plan(in, 4, WVA_LAG_WIDE_SLAB_CAP, &slab);
+  if (rc != 0) return rc;
+  const size_t bytes = wva_lag_path_avg_wide_layout(in, slab, false, off);
+  rc = wva_lag_wide_reserve(c, bytes, off[WVA_LPWA_PART]);
+  if (rc != 0) return rc;
+  WvaDeviceGuard on_dev(c->dev_dyn);
+  char *d = (char *)c->lagw_dev, *h = (char *)c->lagw_pin;
+  wva_lag_path_wide_stage(in, off, h);
+  if (hipMemcpyAsync(d, h, off[WVA_LPWA_F], hipMemcpyHostToDevice, c->s0) != hipSuccess)
+    return -32;
+  rc = wva_lag_path_avg_wide_launch(in, off, d, false, c->s0, launches);
+  if (rc != 0) return rc;
+  if (hipMemcpyAsync(h + off[WVA_LPWA_F], d + off[WVA_LPWA_F],
+                     off[WVA_LPWA_RAW] - off[WVA_LPWA_F], hipMemcpyDeviceToHost,
+                     c->s0) != hipSuccess)
+    return -33;
+  if (hipStreamSynchronize(c->s0) != hipSuccess) return -34;
+  if (out_f) *out_f = h + off[WVA_LPWA_F];
+  if (out_violated) *out_violated = h + off[WVA_LPWA_VIOL];
+  if (out_steps) *out_steps = h + off[WVA_LPWA_STEPS];
+  if (out_avg_f) *out_avg_f = h + off[WVA_LPWA_AF];
+  if (out_avg_violated) *out_avg_violated = h + off[WVA_LPWA_AVIOL];
   return 0;
 }
 

@@ -3930,6 +3930,11 @@ extern "C" __global__ void __launch_bounds__(WVA_WAVE) wva_plan_greedy(
 // kernels of wva_lag.inc.
 #include "wva_lag_path_wide.inc"
 
+// Lag path averages for wide cells (wva_lag_path_avg_tile_t: two blocks per
+// tile, the second one accumulates the time average inside the window),
+// siblings of the wide path kernels.
+#include "wva_lag_path_avg_wide.inc"
+
 // The native reconcile context (WvaCtx: the per-tick pipeline and the planning
 // passes behind the wva_ctx_* C ABI) launches the kernels above; it is host
 // code of this translation unit.

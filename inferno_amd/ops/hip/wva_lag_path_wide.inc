@@ -393,11 +393,13 @@ struct WvaLagPathWideIn {
 
 // Every index a kernel will form lies inside its table, the segment chains
 // partition each tick's steps, and the launch-prefix rule holds (tasks by
-// descending n_seg, tiles and segments in task order). Fills wide[].slab round
-// by round (a round's slabs fit `cap` bytes, a task larger than the cap runs
-// alone) and returns the doubles the largest round needs in *slab_doubles.
-// -2: a table is inconsistent.
-static int wva_lag_path_wide_plan(const WvaLagPathWideIn &in, size_t cap, size_t *slab_doubles) {
+// descending n_seg, tiles and segments in task order). A task's slab is
+// `arrays` x G doubles (3: v twice and acc; 4: avg too, wva_lag_path_avg_wide.inc).
+// Fills wide[].slab round by round (a round's slabs fit `cap` bytes, a task
+// larger than the cap runs alone) and returns the doubles the largest round
+// needs in *slab_doubles. -2: a table is inconsistent.
+static int wva_lag_path_wide_plan(const WvaLagPathWideIn &in, int arrays, size_t cap,
+                                  size_t *slab_doubles) {
   const int C = WVA_LAG_WIDE_C, W = WVA_LAG_WIDE_NT * WVA_LAG_WIDE_C;
   const int S = in.stride, T = in.halo;
   if (!in.tasks || !in.wide || !in.segs || !in.tiles || !in.desc) return -2;
@@ -446,7 +448,7 @@ static int wva_lag_path_wide_plan(const WvaLagPathWideIn &in, size_t cap, size_t
     }
     if (j != w.tick0 + w.n_run || done != 0) return -2;
     seg_at += w.n_seg;
-    const size_t need = 3 * (size_t)G;
+    const size_t need = (size_t)arrays * (size_t)G;
     if (round > 0 && (round + need) * sizeof(double) > cap) round = 0;  // a new round
     w.slab = (long long)round;
     round += need;
@@ -486,10 +488,45 @@ static void wva_lag_path_wide_stage(const WvaLagPathWideIn &in, const size_t *of
          (size_t)in.n_ticks * (size_t)in.n_slots * 2 * sizeof(double));
 }
 
-// the launches of a staged pass, stream-ordered on s: per round one init, then
-// per l the step launch over the tiles of the tasks that have a segment l (a
-// prefix: tasks are by descending n_seg) and a fin launch if one of them
-// closed a tick. launches[3] (or null): init, step and fin launches made.
+// the launch order of a staged pass: per round init(tasks, first task), then
+// per l step(tiles, first tile, l) over the tiles of the tasks that have a
+// segment l (a prefix: tasks are by descending n_seg) and fin(live tasks, first
+// task, l) if one of them closed a tick. launches[3] (or null): init, step and
+// fin launches made.
+template <typename I, typename S, typename F>
+static int wva_lag_path_wide_rounds(const WvaLagPathWideIn &in, int *launches, I init, S step,
+                                    F fin) {
+  int made[3] = {0, 0, 0};
+  for (int t0 = 0; t0 < in.n_tasks;) {
+    int t1 = t0 + 1;  // the round: up to the next task whose slab starts over
+    while (t1 < in.n_tasks && in.wide[t1].slab != 0) ++t1;
+    init(t1 - t0, t0);
+    ++made[0];
+    int live = t1 - t0;  // tasks of the round with a segment l
+    for (int l = 0; l < in.wide[t0].n_seg; ++l) {
+      while (in.wide[t0 + live - 1].n_seg <= l) --live;
+      const WvaLagPathWideTask &end = in.wide[t0 + live - 1];
+      const int tile_base = in.wide[t0].tile0;
+      step(end.tile0 + end.n_tiles - tile_base, tile_base, l);
+      ++made[1];
+      bool closes = false;
+      for (int i = t0; i < t0 + live && !closes; ++i)
+        closes = (in.segs[in.wide[i].seg0 + l].flags & WVA_LAG_SEG_LAST) != 0;
+      if (closes) {
+        fin(live, t0, l);
+        ++made[2];
+      }
+    }
+    const int rc = (int)hipGetLastError();
+    if (rc != 0) return rc;
+    t0 = t1;
+  }
+  if (launches)
+    for (int i = 0; i < 3; ++i) launches[i] = made[i];
+  return 0;
+}
+
+// the launches of a staged pass, stream-ordered on s
 static int wva_lag_path_wide_launch(const WvaLagPathWideIn &in, const size_t *off, char *d,
                                     bool raw, hipStream_t s, int *launches) {
   constexpr int NT = WVA_LAG_WIDE_NT, C = WVA_LAG_WIDE_C;
@@ -516,35 +553,18 @@ static int wva_lag_path_wide_launch(const WvaLagPathWideIn &in, const size_t *of
   g.violated = (uint8_t *)(d + off[WVA_LPW_VIOL]);
   g.steps = (int *)(d + off[WVA_LPW_STEPS]);
   g.raw = raw ? (double *)(d + off[WVA_LPW_RAW]) : nullptr;
-  int made[3] = {0, 0, 0};
-  for (int t0 = 0; t0 < in.n_tasks;) {
-    int t1 = t0 + 1;  // the round: up to the next task whose slab starts over
-    while (t1 < in.n_tasks && in.wide[t1].slab != 0) ++t1;
-    hipLaunchKernelGGL(wva_lag_path_wide_init, dim3(t1 - t0), dim3(NT), 0, s, g, t0);
-    ++made[0];
-    int live = t1 - t0;  // tasks of the round with a segment l
-    for (int l = 0; l < in.wide[t0].n_seg; ++l) {
-      while (in.wide[t0 + live - 1].n_seg <= l) --live;
-      const WvaLagPathWideTask &end = in.wide[t0 + live - 1];
-      const int tile_base = in.wide[t0].tile0;
-      hipLaunchKernelGGL((wva_lag_path_tile_t<NT, C>), dim3(end.tile0 + end.n_tiles - tile_base),
-                         dim3(NT), lds, s, g, tile_base, l);
-      ++made[1];
-      bool closes = false;
-      for (int i = t0; i < t0 + live && !closes; ++i)
-        closes = (in.segs[in.wide[i].seg0 + l].flags & WVA_LAG_SEG_LAST) != 0;
-      if (closes) {
-        hipLaunchKernelGGL(wva_lag_path_wide_fin, dim3(live), dim3(WVA_WAVE), 0, s, g, t0, l);
-        ++made[2];
-      }
-    }
-    rc = (int)hipGetLastError();
-    if (rc != 0) return rc;
-    t0 = t1;
-  }
-  if (launches)
-    for (int i = 0; i < 3; ++i) launches[i] = made[i];
-  return 0;
+  return wva_lag_path_wide_rounds(
+      in, launches,
+      [&](int n, int t0) {
+        hipLaunchKernelGGL(wva_lag_path_wide_init, dim3(n), dim3(NT), 0, s, g, t0);
+      },
+      [&](int n_tiles, int tile_base, int l) {
+        hipLaunchKernelGGL((wva_lag_path_tile_t<NT, C>), dim3(n_tiles), dim3(NT), lds, s, g,
+                           tile_base, l);
+      },
+      [&](int n, int t0, int l) {
+        hipLaunchKernelGGL(wva_lag_path_wide_fin, dim3(n), dim3(WVA_WAVE), 0, s, g, t0, l);
+      });
 }
 
 // One-shot probe of the wide path kernels for tests and tools, the sibling of
@@ -562,7 +582,7 @@ extern "C" int wva_lag_path_wide_probe_launch(const void *tasks, void *wide, con
                          (const WvaLagSeg *)segs, (const WvaLagTile *)tiles, desc, n_tasks,
                          n_segs, n_tiles, n_ticks, n_slots, stride, halo, max_steps, dt};
   size_t slab = 0, off[WVA_LPW_N];
-  int rc = wva_lag_path_wide_plan(in, WVA_LAG_WIDE_SLAB_CAP, &slab);
+  int rc = wva_lag_path_wide_plan(in, 3, WVA_LAG_WIDE_SLAB_CAP, &slab);
   if (rc != 0) return rc;
   const size_t bytes = wva_lag_path_wide_layout(in, slab, true, off);
   if (need) *need = bytes;

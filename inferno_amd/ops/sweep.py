@@ -498,6 +498,15 @@ def load_library(allow_build: bool = True) -> ctypes.CDLL:
                                                       ctypes.POINTER(ctypes.c_size_t),
                                                       ctypes.POINTER(ctypes.c_size_t)]
     )
+    # wide lag path averages (FastSweep.lag_path(max_n=..., averages=True)): as
+    # above, with the averaged records and verdicts as two more outputs
+    lib.wva_ctx_lag_path_wide_avg.restype = ctypes.c_int
+    lib.wva_ctx_lag_path_wide_avg.argtypes = (
+        list(lib.wva_ctx_lag_path_wide.argtypes) + [ctypes.POINTER(ctypes.c_void_p)] * 2
+    )
+    lib.wva_lag_path_avg_wide_probe_launch.restype = ctypes.c_int
+    lib.wva_lag_path_avg_wide_probe_launch.argtypes = (
+        lib.wva_lag_path_wide_probe_launch.argtypes)
     lib.wva_ctx_plan_cells.restype = ctypes.c_int
     lib.wva_ctx_plan_cells.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
     # capacity-limited planning (FastSweep.plan(capacity=...))
@@ -1226,13 +1235,17 @@ def lag_path_wide_schedule(fields: dict, tick0, lam, keep, smax, dt: float, n_ti
 
 def run_lag_path_wide_probe(arrays: dict, start, lam, keep, tick_seconds: float,
                             stride: int = LAG_WIDE_STRIDE, halo: int = LAG_WIDE_HALO,
-                            max_steps: int = 1 << 22, device: str = "cuda"):
+                            max_steps: int = 1 << 22, device: str = "cuda",
+                            averages: bool = False):
     """One-shot probe of the tiled lag-path kernels (wva_lag_path_wide_init,
     wva_lag_path_tile_t, wva_lag_path_wide_fin), the sibling of
     run_lag_path_probe with the tile stride and halo as arguments. Arguments as
     there; every cell (LAG_MAX_N < N <= LAG_WIDE_MAX_N) is one run over all S
     ticks. Returns (raw float64 [n_cells, S, 5], steps int32 [n_cells, S], the
-    segments of every cell int64 [n_cells] in place of the chunk bounds)."""
+    segments of every cell int64 [n_cells] in place of the chunk bounds).
+    ``averages``: run wva_lag_path_avg_tile_t and wva_lag_path_avg_wide_fin
+    instead and return (raw, the raw functionals of the time-averaged
+    distribution [n_cells, S, 5], steps, segments)."""
     import numpy as np
     import torch
 
@@ -1261,24 +1274,29 @@ def run_lag_path_wide_probe(arrays: dict, start, lam, keep, tick_seconds: float,
         fields, np.zeros(n_cells, dtype=np.int64), list(lam), list(keep), smax, dt, n_ticks,
         stride, halo, n_cells)
     need = ctypes.c_size_t()
-    offs = (ctypes.c_size_t * 4)()
+    # the offsets the launcher reports, as in run_lag_path_probe
+    n_off, i_raw = (7, 5) if averages else (4, 3)
+    launch = (lib.wva_lag_path_avg_wide_probe_launch if averages
+              else lib.wva_lag_path_wide_probe_launch)
+    offs = (ctypes.c_size_t * n_off)()
     args = (table.ctypes.data, wide.ctypes.data, segs.ctypes.data, tiles.ctypes.data,
             desc.ctypes.data, len(table), len(segs), len(tiles), n_ticks, n_cells, int(max_steps),
             int(stride), int(halo), dt, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    rc = lib.wva_lag_path_wide_probe_launch(*args, None, 0, ctypes.byref(need), offs)
+    rc = launch(*args, None, 0, ctypes.byref(need), offs)
     if rc != 0:
-        raise HipKernelError(f"wva_lag_path_wide_probe_launch failed: {rc}")
+        raise HipKernelError(f"{launch.__name__} failed: {rc}")
     dev = torch.empty(need.value, dtype=torch.uint8, device=device)
-    rc = lib.wva_lag_path_wide_probe_launch(*args, _ptr(dev), need.value, ctypes.byref(need), offs)
+    rc = launch(*args, _ptr(dev), need.value, ctypes.byref(need), offs)
     if rc != 0:
-        raise HipKernelError(f"wva_lag_path_wide_probe_launch failed: {rc}")
+        raise HipKernelError(f"{launch.__name__} failed: {rc}")
     cells = n_cells * n_ticks
-    host = dev[offs[0]:offs[3] + cells * 40].cpu().numpy()
+    host = dev[offs[0]:offs[n_off - 1] + cells * 40].cpu().numpy()
     at = lambda i, n, t: host[offs[i] - offs[0]:offs[i] - offs[0] + n].view(t)  # noqa: E731
-    raw = at(3, cells * 40, np.float64).reshape(n_cells, n_ticks, 5).copy()
+    raws = [at(i, cells * 40, np.float64).reshape(n_cells, n_ticks, 5).copy()
+            for i in range(i_raw, n_off)]
     n_seg = np.empty(n_cells, dtype=np.int64)
     n_seg[order] = wide["n_seg"]
-    return raw, at(2, cells * 4, np.int32).reshape(n_ticks, n_cells).T.copy(), n_seg
+    return (*raws, at(2, cells * 4, np.int32).reshape(n_ticks, n_cells).T.copy(), n_seg)
 
 
 def _lag_smax(fields: dict, i: int) -> float:
